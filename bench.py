@@ -1,6 +1,8 @@
 """Benchmark of the PIGEON inference hot path on MI355X.
 
     python bench.py                                   # 1 GPU
+    python bench.py --full                            # + per-kernel figures, rooflines, other configs, baselines, parity legs
+    python bench.py --steps K --dump-outputs DIR      # + what the last timed step returned, as DIR/<name>.npy
     python bench.py --gpus 8 --steps K --warmup W     # spawns its 8 ranks itself (one process per GPU)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
            bench.py --gpus N --steps K --warmup W     # or under torchrun (RANK / LOCAL_RANK / WORLD_SIZE from the env)
@@ -25,9 +27,13 @@ during warm-up), so that the synthetic panoramas spread over the geocells the wa
 streams different prototype rows from HBM every step (otherwise every query asks for the same cells and the 256 MB
 Infinity Cache serves them).
 
-Prints ONE JSON line (rank 0) with the driver's contract fields plus
-  certainty           the rule, the calibration's measurements, panoramas re-encoded per step and why; fast_mode / exact_cost_vs_fast:
-                      the 16-bit path alone for a few steps after the timed region; per_rank_split_ms: compute vs gather(-wait);
+A plain run sets up, warms up, times --steps steps, writes --dump-outputs DIR (what the last timed step returned, as .npy) and
+prints ONE JSON line (rank 0): the contract fields (metric, value, unit, higher_is_better, dtype, ms_per_step = the
+milliseconds of one timed step) plus what the timed region itself recorded --
+  certainty           the rule, the calibration's measurements, panoramas re-encoded per step and why; per_rank_split_ms: compute
+                      vs gather(-wait); exact_pass_schedule; gathered_results; graph; rccl.
+Everything below takes runs of its own after the timed region and is measured with --full only (the other mode, `fast_mode` /
+`exact_cost_vs_fast`: the 16-bit path alone for a few steps after the timed region):
   roofline            the dominant kernel (the fc1 GEMM), algorithmic FLOPs per launch / mean launch time measured live with
                       HIP events on the launch stream during the timed region; `frac_rocprof` = the same fraction from the
                       committed rocprofv3 kernel stats of this command (profiles/rNN/traffic.json);
@@ -118,13 +124,22 @@ def parse(argv=None):
     ap.add_argument("--no-extras", action="store_true", help="skip ingest / other configs / secondary baseline (profiling runs)")
     ap.add_argument("--profile", choices=["graph", "all", "dominant", "none"], default="graph",
                     help="graph (default): the timed region runs the product path -- encoder body replayed from its hipGraph, no events "
-                         "inside -- and per-kernel HIP events bracket every launch of --profile-steps extra un-graphed steps right after it; "
+                         "inside -- and (--full) per-kernel HIP events bracket every launch of --profile-steps extra un-graphed steps right after it; "
                          "all / dominant: events around every launch / the dominant GEMM class INSIDE the timed region (graph off); "
                          "none: un-graphed, no events (A/B arm)")
-    ap.add_argument("--profile-steps", type=int, default=5, help="bracketed un-graphed steps after the timed region (--profile graph / none / dominant)")
+    ap.add_argument("--profile-steps", type=int, default=5, help="bracketed un-graphed steps after the timed region (--full; --profile graph / none / dominant)")
     ap.add_argument("--dry-run", action="store_true",
                     help="no GPU: stub model / refiner on the CPU, gloo collectives, tiny tensors -- the launch, sharding, gather, "
                          "timing and JSON control flow of the real run (CPU contract test)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, also run everything the headline does not need: the per-kernel steps and rooflines, the "
+                         "all-gather and refinement timings, the ingest leg, the other BASELINE configs, the other certainty mode, the CPU "
+                         "baselines, the parity legs and the stock-PyTorch baseline (--profile-steps, --fast-steps, --cpu-images, "
+                         "--cpu-port-images, --cpu-workers and --no-extras shape them).  Without it a run sets up, warms up, times "
+                         "--steps steps, writes --dump-outputs and prints the result line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (rank 0: the gathered batch, rank-major) "
+                         "as DIR/<name>.npy: floating-point arrays as float32 (float64 stays float64), integer and boolean ones as float64")
     return ap.parse_args(argv)
 
 
@@ -727,6 +742,34 @@ def secondary_baseline(dev, vit_sd, layers):
     return out
 
 
+# ------------------------------------------------------------------------------------------------------ --dump-outputs
+DUMP_LIMIT = 64 << 20                # bytes, all files of --dump-outputs together
+
+
+def dump_outputs(out_dir, res):
+    """--dump-outputs: every tensor of one step's result dict (see pigeon_amd.deferred.DeferredExact.submit) as <name>.npy.  Floating
+    point is written as float32 (float64 as float64); integer / boolean arrays as float64, which holds their values exactly.  Should the
+    batch not fit DUMP_LIMIT, every array keeps the same fixed, seeded sample of its rows, listed in sample_rows.npy."""
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    arrs = {}
+    for name in sorted(res):
+        t = res[name]
+        if torch.is_tensor(t):
+            a = t.detach().cpu()
+            arrs[name] = (a.double() if (a.dtype == torch.float64 or not a.is_floating_point()) else a.float()).numpy()
+    n = max((a.shape[0] for a in arrs.values() if a.ndim), default=0)
+    total = sum(a.nbytes for a in arrs.values())
+    if total > DUMP_LIMIT and n > 1:
+        keep = max(1, int(n * (DUMP_LIMIT - 8 * n - 256 * (len(arrs) + 1)) / total))      # (npy headers: < 256 B each)
+        rows = np.sort(np.random.default_rng(0).choice(n, size=keep, replace=False))
+        arrs = {k: (a[rows] if a.ndim and a.shape[0] == n else a) for k, a in arrs.items()}
+        arrs["sample_rows"] = rows.astype(np.float64)
+    for name, a in arrs.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+    return sorted(arrs)
+
+
 # ------------------------------------------------------------------------------------------------------ dry-run stubs
 def _cause_counts(causes):
     """certain_forward's `cause` codes of the timed steps -> {cause: panoramas}, summed over the steps."""
@@ -984,6 +1027,8 @@ def _worker(args, comm):
     out = outs_by_batch[(args.steps - 1) % nb]
     if len(info_by_step) != args.steps:
         raise SystemExit(f"rank {rank}: {len(info_by_step)} of {args.steps} steps were handed out")
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out)                      # what the caller of the last timed step received
     flush_log = pipe.engine.flush_log[flushes_before:]
     prof = {}
     ungraphed = None
@@ -991,7 +1036,7 @@ def _worker(args, comm):
         g1 = enc.graph()
         enc.profile_enable(False)
         prof = enc.profile_read()
-        if args.profile != "all":
+        if args.full and args.profile != "all":
             # per-kernel timing: --profile-steps extra steps right after the timed region, every encoder launch bracketed with HIP
             # events on the launch stream (which also switches the graph replay off for them); not part of `value`
             live = {k: v for k, v in prof.items() if v[0]}
@@ -1054,7 +1099,7 @@ def _worker(args, comm):
     # process); rank 0 then goes on alone with the roofline / CPU-baseline / parity legs.
     rccl_ranks = comm.rccl_ranks()
     gather_us = None
-    if not dry and rccl_ranks:
+    if args.full and not dry and rccl_ranks:
         # what the step's two grouped all-gathers cost on this rank (RCCL group launch + copies), on the launch stream
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         own_rows = [out[k][own].contiguous() for k in ("embedding", "topk_indices", "topk_values", "preds_LLH", "index")]
@@ -1108,25 +1153,6 @@ def _worker(args, comm):
         return
 
     from pigeon_amd import _lib
-    kernels = {}
-    prof_steps = args.steps if args.profile == "all" else max(1, args.profile_steps)
-    for name, (cnt, ms) in prof.items():
-        if cnt:
-            in_region = args.profile == "all" or (args.profile == "dominant" and name == "gemm_fc1")
-            kernels[name] = {"launches": cnt, "avg_ms": ms / cnt, "launches_per_step": cnt / (args.steps if in_region else prof_steps)}
-    # per-launch rows: the encoder processes <= max_chunk (512) images per internal pass, so a 512-image step launches
-    # every layer kernel once with M = 512*577 rows
-    chunk_rows = min(args.panoramas * 4, enc.max_chunk) * 577
-    for name in GEMM_FLOPS:
-        if name in kernels:
-            kernels[name]["tflops"] = GEMM_FLOPS[name] * chunk_rows / (kernels[name]["avg_ms"] * 1e-3) / 1e12
-    if "attention" in kernels:
-        kernels["attention"]["tflops"] = 4.0 * 577 * 577 * 64 * 16 * (chunk_rows / 577) / (kernels["attention"]["avg_ms"] * 1e-3) / 1e12
-    dom = max((k for k in kernels if k in GEMM_FLOPS), key=lambda k: kernels[k]["avg_ms"] * kernels[k].get("launches_per_step", 1))
-    if args.profile == "dominant":
-        dom = "gemm_fc1"                  # the class that was bracketed INSIDE the timed region (it is the dominant one: checked by `all`)
-    achieved = kernels[dom]["tflops"]
-    traffic, traffic_detail = _committed_traffic(dom, chunk_rows)
     result["mfma_frac_end_to_end"] = value * FLOP_PER_IMAGE / (world * PEAK_MFMA)
     result["graph"] = {"encoder_body_replays_in_timed_region": g1[0] - g0[0], "captures_total": g1[1],
                        "what": "pg_vit_forward replays the ~250 launches between im2col and the token mean from a hipGraph captured at the "
@@ -1138,69 +1164,90 @@ def _worker(args, comm):
         result["certain_frac"] = float(np.mean(cf))               # after the exact re-encode (product mode) / as flagged (--fast)
     if pinned:
         result["config"]["rank0_cores"] = f"{len(pinned)} cores next to GPU {local} (sched_setaffinity)"
-    result["roofline"] = {"bound": "mfma", "kernel": f"gemm16 {dom}: M={chunk_rows} rows x {GEMM_FLOPS[dom]} FLOP/row per launch",
-                          "achieved": achieved, "peak": PEAK_MFMA / 1e12, "unit": "TFLOP/s", "frac": achieved / (PEAK_MFMA / 1e12),
-                          "traffic": traffic, "traffic_detail": traffic_detail,
-                          "timing": {"all": "HIP events around every encoder launch on the launch stream, inside the timed region (in-process number)",
-                                     "dominant": "HIP events around the dominant class's launches (gemm_fc1) inside the timed region; the other "
-                                                 "classes of `kernels` from one extra bracketed step after it",
-                                     "graph": f"HIP events around every encoder launch on the launch stream during {prof_steps} un-graphed steps run right "
-                                              "after the timed region (same process, same resident inputs); the timed region itself replays the "
-                                              "encoder body from its hipGraph and carries no events",
-                                     "none": "no events inside the timed region (A/B arm); `kernels` from extra bracketed steps after it"}[args.profile]}
-    if traffic_detail and traffic_detail.get("rocprof_avg_ms"):
-        # the committed rocprofv3 --kernel-trace --stats average of the same kernel (another box of the pool: +-4 %)
-        # (persistent kernel + its small-tile tail launch: one GEMM of the model is both)
-        t_roc = traffic_detail["rocprof_avg_ms"] + (traffic_detail.get("rocprof_tail_avg_ms") or 0.0)
-        result["roofline"]["frac_rocprof"] = GEMM_FLOPS[dom] * chunk_rows / (t_roc * 1e-3) / PEAK_MFMA
-    result["kernels"] = kernels
     result["fp16_range_alarm_rows"] = enc.range_alarm_read()       # always-on: residual rows that came near the fp16 limit (0 = none)
     if rccl_ranks:
         result["rccl"] = {"nranks": rccl_ranks, "version": _lib.load().pg_comm_rccl_version(),
                           "collective": "pg_allgather_many (C ABI, csrc/comm.hip): 5 buffers before refinement + 2 after, one grouped launch each",
-                          "inside_timed_region": True, "both_gathers_us_per_step": gather_us,
-                          "forced_at_one_rank": bool(world == 1)}
+                          "inside_timed_region": True, "forced_at_one_rank": bool(world == 1)}
+        if gather_us is not None:
+            result["rccl"]["both_gathers_us_per_step"] = gather_us
     if rccl_error is not None:
         result["rccl"] = {"error": rccl_error, "forced_at_one_rank": False,
                           "note": "the 1-rank RCCL communicator could not be created; the step ran with the identity gather"}
-    if refiner is not None:
-        # The refinement against the HBM roofline.  Timed here, back to back on the launch stream (the host runs ahead), over the
-        # candidate sets of the resident pixel batches in turn (different cells every launch: ~1 GB of distinct bank rows, nothing
-        # comes from the 256 MB Infinity Cache).  Inside the step the exact mode's host synchronisation leaves the launch thread only
-        # microseconds ahead of the GPU at this point, so stream events around the step's own refinement would time the launch
-        # latency (measured: 0.115 ms against 0.058 ms of kernel time in profiles/r05/bench_kernel_stats.csv).
-        sets = [outs_by_batch[j] for j in sorted(outs_by_batch)]
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        rows, n_it = [], 20
-        for it in range(2 + n_it):
-            o_ = sets[it % len(sets)]
-            if it == 2:
-                e0.record()
-            refiner(o_["embedding"][own], initial_preds=o_["preds_LLH"][own], candidate_cells=o_["topk_indices"][own],
-                    candidate_probs=o_["topk_values"][own], quiet=True)
-            if it >= 2:
-                rows.append(refiner.last_scratch)
-        e1.record()
-        torch.cuda.synchronize()
-        t = e0.elapsed_time(e1) * 1e-3 / n_it
-        bytes_per_launch = 4096.0 * float(np.mean([float(s_[..., 3].sum()) for s_ in rows]))
-        result["roofline_refine"] = {
-            "bound": "hbm", "kernel": "refine_candidates_kernel + refine_select_kernel (one refinement of the rank's 128 queries)",
-            "achieved": bytes_per_launch / t / 1e9, "peak": PEAK_HBM / 1e9, "unit": "GB/s", "frac": bytes_per_launch / t / PEAK_HBM,
-            "algorithmic_bytes_per_launch": bytes_per_launch, "avg_ms": t * 1e3,
-            "traffic": _committed_traffic("refine_candidates", chunk_rows)[0],
-            "timing": f"{n_it} refinements back to back on the launch stream after the timed region, the candidate sets of the {len(sets)} resident "
-                      "pixel batches in turn",
-            "note": "bytes = 4096 B x bank rows streamed (prototypes of the top-k cells + members of the chosen clusters), counted by the "
-                    f"kernel; {distinct_cells} distinct argmax cells in the last step.  A 128-query launch (640 blocks, 2.5 per CU) is over "
-                    "before it reaches a steady state: the same kernels stream 0.70 of the HBM peak at 1024 queries and 0.75 at 2048 "
-                    "(profiles/r05/refine_bandwidth_vs_batch.txt).  `traffic` (2 x FETCH_SIZE of the committed PMC pass) is below the "
-                    "algorithmic bytes: that pass runs few steps on few pixel batches, so part of what it streams is still in the "
-                    "256 MB Infinity Cache and never reaches the fabric counters"}
+    if args.full:
+        kernels = {}
+        prof_steps = args.steps if args.profile == "all" else max(1, args.profile_steps)
+        for name, (cnt, ms) in prof.items():
+            if cnt:
+                in_region = args.profile == "all" or (args.profile == "dominant" and name == "gemm_fc1")
+                kernels[name] = {"launches": cnt, "avg_ms": ms / cnt, "launches_per_step": cnt / (args.steps if in_region else prof_steps)}
+        # per-launch rows: the encoder processes <= max_chunk (512) images per internal pass, so a 512-image step launches
+        # every layer kernel once with M = 512*577 rows
+        chunk_rows = min(args.panoramas * 4, enc.max_chunk) * 577
+        for name in GEMM_FLOPS:
+            if name in kernels:
+                kernels[name]["tflops"] = GEMM_FLOPS[name] * chunk_rows / (kernels[name]["avg_ms"] * 1e-3) / 1e12
+        if "attention" in kernels:
+            kernels["attention"]["tflops"] = 4.0 * 577 * 577 * 64 * 16 * (chunk_rows / 577) / (kernels["attention"]["avg_ms"] * 1e-3) / 1e12
+        dom = max((k for k in kernels if k in GEMM_FLOPS), key=lambda k: kernels[k]["avg_ms"] * kernels[k].get("launches_per_step", 1))
+        if args.profile == "dominant":
+            dom = "gemm_fc1"                  # the class that was bracketed INSIDE the timed region (it is the dominant one: checked by `all`)
+        achieved = kernels[dom]["tflops"]
+        traffic, traffic_detail = _committed_traffic(dom, chunk_rows)
+        result["roofline"] = {"bound": "mfma", "kernel": f"gemm16 {dom}: M={chunk_rows} rows x {GEMM_FLOPS[dom]} FLOP/row per launch",
+                              "achieved": achieved, "peak": PEAK_MFMA / 1e12, "unit": "TFLOP/s", "frac": achieved / (PEAK_MFMA / 1e12),
+                              "traffic": traffic, "traffic_detail": traffic_detail,
+                              "timing": {"all": "HIP events around every encoder launch on the launch stream, inside the timed region (in-process number)",
+                                         "dominant": "HIP events around the dominant class's launches (gemm_fc1) inside the timed region; the other "
+                                                     "classes of `kernels` from one extra bracketed step after it",
+                                         "graph": f"HIP events around every encoder launch on the launch stream during {prof_steps} un-graphed steps run right "
+                                                  "after the timed region (same process, same resident inputs); the timed region itself replays the "
+                                                  "encoder body from its hipGraph and carries no events",
+                                         "none": "no events inside the timed region (A/B arm); `kernels` from extra bracketed steps after it"}[args.profile]}
+        if traffic_detail and traffic_detail.get("rocprof_avg_ms"):
+            # the committed rocprofv3 --kernel-trace --stats average of the same kernel (measured on another MI355X: +-4 %)
+            # (persistent kernel + its small-tile tail launch: one GEMM of the model is both)
+            t_roc = traffic_detail["rocprof_avg_ms"] + (traffic_detail.get("rocprof_tail_avg_ms") or 0.0)
+            result["roofline"]["frac_rocprof"] = GEMM_FLOPS[dom] * chunk_rows / (t_roc * 1e-3) / PEAK_MFMA
+        result["kernels"] = kernels
+        if refiner is not None:
+            # The refinement against the HBM roofline.  Timed here, back to back on the launch stream (the host runs ahead), over the
+            # candidate sets of the resident pixel batches in turn (different cells every launch: ~1 GB of distinct bank rows, nothing
+            # comes from the 256 MB Infinity Cache).  Inside the step the exact mode's host synchronisation leaves the launch thread only
+            # microseconds ahead of the GPU at this point, so stream events around the step's own refinement would time the launch
+            # latency (measured: 0.115 ms against 0.058 ms of kernel time in profiles/r05/bench_kernel_stats.csv).
+            sets = [outs_by_batch[j] for j in sorted(outs_by_batch)]
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            rows, n_it = [], 20
+            for it in range(2 + n_it):
+                o_ = sets[it % len(sets)]
+                if it == 2:
+                    e0.record()
+                refiner(o_["embedding"][own], initial_preds=o_["preds_LLH"][own], candidate_cells=o_["topk_indices"][own],
+                        candidate_probs=o_["topk_values"][own], quiet=True)
+                if it >= 2:
+                    rows.append(refiner.last_scratch)
+            e1.record()
+            torch.cuda.synchronize()
+            t = e0.elapsed_time(e1) * 1e-3 / n_it
+            bytes_per_launch = 4096.0 * float(np.mean([float(s_[..., 3].sum()) for s_ in rows]))
+            result["roofline_refine"] = {
+                "bound": "hbm", "kernel": "refine_candidates_kernel + refine_select_kernel (one refinement of the rank's 128 queries)",
+                "achieved": bytes_per_launch / t / 1e9, "peak": PEAK_HBM / 1e9, "unit": "GB/s", "frac": bytes_per_launch / t / PEAK_HBM,
+                "algorithmic_bytes_per_launch": bytes_per_launch, "avg_ms": t * 1e3,
+                "traffic": _committed_traffic("refine_candidates", chunk_rows)[0],
+                "timing": f"{n_it} refinements back to back on the launch stream after the timed region, the candidate sets of the {len(sets)} resident "
+                          "pixel batches in turn",
+                "note": "bytes = 4096 B x bank rows streamed (prototypes of the top-k cells + members of the chosen clusters), counted by the "
+                        f"kernel; {distinct_cells} distinct argmax cells in the last step.  A 128-query launch (640 blocks, 2.5 per CU) is over "
+                        "before it reaches a steady state: the same kernels stream 0.70 of the HBM peak at 1024 queries and 0.75 at 2048 "
+                        "(profiles/r05/refine_bandwidth_vs_batch.txt).  `traffic` (2 x FETCH_SIZE of the committed PMC pass) is below the "
+                        "algorithmic bytes: that pass runs few steps on few pixel batches, so part of what it streams is still in the "
+                        "256 MB Infinity Cache and never reaches the fabric counters"}
     pipe.refine_events = None
     enc.profile_reset()
 
-    if not args.no_extras and world == 1:
+    if args.full and not args.no_extras and world == 1:
         # ---- ingest: uint8 host images -> side-stream H2D -> GPU preprocessing -> step (overlapped), and round 2's fp32 leg ----
         try:
             result["h2d_inclusive"] = ingest_leg(args, dev, pipe, index, step_ms)
@@ -1266,7 +1313,7 @@ def _worker(args, comm):
         "uncertain_by_cause": _cause_counts([inf["cause"] for inf in info_by_step]),
         "boundary_checked": bool(pipe.engine.boundary_checked),
         "rows_that_did_not_fit_the_queue": pipe.engine.check_nothing_dropped()}
-    if world == 1 and args.fast_steps > 0:
+    if args.full and world == 1 and args.fast_steps > 0:
         try:
             model.exact_top1 = not headline_exact
             if model.exact_top1:
@@ -1313,7 +1360,7 @@ def _worker(args, comm):
             model.exact_top1 = headline_exact
     other_name = "fast_mode" if headline_exact else "exact_mode"
 
-    if world == 1 and args.cpu_images > 0:
+    if args.full and world == 1 and args.cpu_images > 0:
         try:
             # sample: the first panoramas of EVERY resident pixel batch the timed region used, in turn
             used = sorted(outs_by_batch)
@@ -1346,7 +1393,7 @@ def _worker(args, comm):
         except Exception as e:  # noqa
             import traceback
             result["cpu_baseline"] = {"error": str(e), "trace": traceback.format_exc()[-800:]}
-    if world == 1 and not args.no_extras:
+    if args.full and world == 1 and not args.no_extras:
         try:
             used = sorted(outs_by_batch)
             result["parity_vs_reference_module_gpu_fp32"] = gpu_module_parity(
@@ -1355,7 +1402,7 @@ def _worker(args, comm):
         except Exception as e:  # noqa
             import traceback
             result["parity_vs_reference_module_gpu_fp32"] = {"error": repr(e), "trace": traceback.format_exc()[-600:]}
-    if world == 1 and not args.no_extras:
+    if args.full and world == 1 and not args.no_extras:
         del pixel_batches
         torch.cuda.empty_cache()
         result["secondary_baseline"] = secondary_baseline(dev, vit_sd, args.layers)

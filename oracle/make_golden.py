@@ -1,7 +1,7 @@
 """Generate tests/golden/*.npz by running the REAL reference (from /root/reference) on seeded synthetic
 inputs.  Authoring-container only (the GPU box has no /root/reference); the outputs are committed.
 
-    python oracle/make_golden.py [--only vit2|vit24|vit24_trained|head|pipeline|pipeline24|pipeline24_wide|pipeline24_spread|refine|geo|refiner_cache]
+    python oracle/make_golden.py [--only vit2|vit24|vit24_trained|head|pipeline|pipeline24|pipeline24_wide|pipeline24_spread|refine|geo|refiner_cache|host_cpu]
 
 Every fixture stores only small tensors (inputs are regenerated from their seeds by
 ``pigeon_amd.synthetic`` on both sides).  What runs for each fixture:
@@ -621,6 +621,50 @@ def main():
         np.savez(os.path.join(GOLD, "refiner_cache.npz"), meta=np.array([C, ppc, bseed, 3]),
                  n_empty=np.array(int((np.diff(bank_rc.cell_off) == 0).sum())))
         print("refiner_cache: pickled reference refiner,", os.path.getsize(os.path.join(GOLD, "proto.refiner")), "bytes")
+
+    if want("host_cpu"):
+        # What tests/test_host_cpu.py takes from the reference, recorded so that the tests need no reference tree:
+        # (1) the layout of torch.save(reference SuperGuessr(HF CLIPVisionModel, 1 layer).state_dict()) -- keys, shapes, dtypes, and the
+        #     values of its non-float buffers (the float values are seeded noise in the test: only the layout is the reference's);
+        # (2) the reference's metric helpers (evaluation/metrics.py) on seeded inputs, inputs stored beside the outputs;
+        # (3) `refiner.protos` as the reference's ProtoRefiner builds it from the bank files of make_bank(30, 6, seed=2,
+        #     empty_frac=0.1), moved into memory as for proto.refiner above, pickled as the plain list (host_protos.pkl).
+        import pickle
+        from transformers import CLIPVisionConfig, CLIPVisionModel
+        geo_h = os.path.join(tmp, "geocells_h.csv")
+        synthetic.write_geocell_csv(geo_h, synthetic.make_geocells(37, seed=0))
+        ns = reference_loader.load(geo_h, "unused.csv", "unused_dir")
+        cfg = CLIPVisionConfig(hidden_size=1024, intermediate_size=4096, num_hidden_layers=1, num_attention_heads=16,
+                               image_size=336, patch_size=14, projection_dim=768)
+        torch.manual_seed(7)
+        sd = ns.SuperGuessr(CLIPVisionModel(cfg), panorama=True, freeze_base=True, num_candidates=5).state_dict()
+        keys = list(sd)
+        extra = {f"ckpt_value_{i}": v.numpy() for i, (k, v) in enumerate(sd.items()) if not v.is_floating_point()}
+        mt = reference_loader.load_metrics()
+        rng = np.random.default_rng(5)
+        d = np.exp(rng.uniform(-3, 9, 1000))
+        lab, top = rng.integers(0, 9, 200), rng.integers(0, 9, (200, 5))
+        km = np.array([1, 25, 750])
+        np.savez(os.path.join(GOLD, "host_cpu.npz"), ckpt_keys=np.array(keys), ckpt_dtypes=np.array([str(sd[k].dtype) for k in keys]),
+                 ckpt_ndim=np.array([sd[k].dim() for k in keys]), ckpt_dims=np.array([n for k in keys for n in sd[k].shape], dtype=np.int64),
+                 metrics_d=d, metrics_labels=lab, metrics_top5=top, metrics_km=km,
+                 metrics_score=np.array(mt.geoguessr_score(d), dtype=np.float64),
+                 metrics_within=np.array([mt.percentage_within_radius(d, int(r)) for r in km], dtype=np.float64),
+                 metrics_topk=np.array(mt.topk_geocell_accuracy(lab, top), dtype=np.float64), **extra)
+        C = 30
+        bank_h = synthetic.make_bank(C, 6, seed=2, empty_frac=0.1)
+        csv_h, ds_h = os.path.join(tmp, "protos_h.csv"), os.path.join(tmp, "hf_train_h")
+        synthetic.write_bank_reference_files(bank_h, csv_h, ds_h)
+        synthetic.write_geocell_csv(geo_h, synthetic.make_geocells(C, seed=0))
+        ns = reference_loader.load(geo_h, csv_h, ds_h)
+        ref = ns.ProtoRefiner(topk=5, proto_path=csv_h, dataset_path=ds_h)
+        import datasets as _ds
+        protos = [None if p is None else _ds.Dataset.from_dict(p.with_format(None)[:], features=p.features).with_format(**p.format)
+                  for p in ref.protos]
+        with open(os.path.join(GOLD, "host_protos.pkl"), "wb") as f:
+            pickle.dump(protos, f)
+        print("host_cpu: checkpoint layout of", len(keys), "tensors, metrics, protos of", C, "cells,",
+              os.path.getsize(os.path.join(GOLD, "host_protos.pkl")), "bytes")
 
     print("golden fixtures written to", GOLD)
 

@@ -117,6 +117,49 @@ def test_bench_single_rank_dry_run_and_world_mismatch():
     assert p.returncode != 0 and "--gpus 2 but WORLD_SIZE is 1" in p.stderr
 
 
+def test_bench_dump_outputs_of_the_last_timed_step(tmp_path):
+    """--dump-outputs DIR: rank 0 writes what the last timed step returned (the gathered batch) as float32 / float64 .npy files; the
+    same arguments give the same inputs, so two runs write the same arrays."""
+    import numpy as np
+    dumps = []
+    for run in range(2):
+        d = os.path.join(str(tmp_path), f"out{run}")
+        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dry-run", "--panoramas", "6", "--cells", "50",
+                            "--steps", "3", "--warmup", "1", "--dump-outputs", d], capture_output=True, text=True, timeout=300, env=_env())
+        assert p.returncode == 0, p.stderr[-2000:]
+        _check(p.stdout, 2, 3, 1, "self")
+        dumps.append({f[:-4]: np.load(os.path.join(d, f)) for f in sorted(os.listdir(d))})
+    a, b = dumps
+    for name in ("embedding", "index", "preds_geocell", "preds_LLH", "topk_indices", "topk_values", "refined_LLH", "refined_geocell", "certain"):
+        assert name in a, sorted(a)
+    assert sorted(a) == sorted(b)
+    for name, x in a.items():
+        assert x.dtype in (np.float32, np.float64), (name, x.dtype)
+        assert np.array_equal(x, b[name]), name
+    assert a["embedding"].shape == (12, 4, 1024) and sorted(a["index"].tolist()) == list(range(12))
+    assert sum(os.path.getsize(os.path.join(str(tmp_path), "out0", f)) for f in os.listdir(os.path.join(str(tmp_path), "out0"))) <= 64 << 20
+
+
+def test_dump_outputs_keeps_a_seeded_sample_of_a_large_batch(tmp_path):
+    """A batch larger than 64 MB is written as the same fixed, seeded sample of rows in every array (listed in sample_rows.npy)."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    n = 5000
+    res = {"embedding": torch.arange(n, dtype=torch.float32)[:, None, None].expand(n, 4, 1024).contiguous(),
+           "index": torch.arange(n), "certain": torch.ones(n, dtype=torch.bool), "queued": [0], "step": 7}
+    for d in ("a", "b"):
+        bench.dump_outputs(os.path.join(str(tmp_path), d), res)
+    files = sorted(os.listdir(os.path.join(str(tmp_path), "a")))
+    assert files == ["certain.npy", "embedding.npy", "index.npy", "sample_rows.npy"]
+    assert sum(os.path.getsize(os.path.join(str(tmp_path), "a", f)) for f in files) <= 64 << 20
+    ld = lambda d, f: np.load(os.path.join(str(tmp_path), d, f + ".npy"))      # noqa: E731
+    rows = ld("a", "sample_rows")
+    assert 0 < len(rows) < n and np.array_equal(rows, ld("b", "sample_rows")) and np.all(np.diff(rows) > 0)
+    assert np.array_equal(ld("a", "index"), rows) and np.array_equal(ld("a", "embedding")[:, 0, 0], rows.astype(np.float32))
+
+
 def test_bench_self_launch_propagates_a_rank_failure():
     """A rank that dies (here: more ranks than the stub allows via an impossible flag) must fail the launcher, not hang it."""
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dry-run", "--panoramas", "6", "--cells", "3",

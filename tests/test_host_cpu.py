@@ -5,8 +5,8 @@
   compute_geoguessr_metrics                      reference evaluation/metrics.py:89-181
   shard_batches / compute_embeddings on disk     reference preprocessing/embed.py:16-43,68, dataset_preprocessing.py:294-300
   evaluate() argument handling                   reference evaluation/evaluate.py:42-47
-Where the reference tree is present (/root/reference, authoring container) the inputs come from the reference's own
-classes through oracle/reference_loader.py; the committed fixtures (tests/golden/geo.npz) cover the rest.
+What comes from the reference's own classes and functions is recorded in committed fixtures (tests/golden/geo.npz, host_cpu.npz,
+host_protos.pkl, proto.refiner; oracle/make_golden.py writes them).
 """
 import os
 import sys
@@ -15,10 +15,7 @@ import numpy as np
 import pytest
 import torch
 
-from oracle import reference_loader
 from pigeon_amd import synthetic
-
-needs_reference = pytest.mark.skipif(not reference_loader.available(), reason="reference tree not present")
 
 
 def _geo_csv(tmp_path, C=37):
@@ -88,23 +85,31 @@ def test_load_state_dict_layouts(prefix, embedder):
     assert torch.equal(m2.state_dict()["encoder.layers.0.mlp.fc1.weight"], src["encoder.layers.0.mlp.fc1.weight"])
 
 
-@needs_reference
-def test_load_state_reads_a_checkpoint_written_by_the_reference(tmp_path):
+def _reference_checkpoint(golden_dir):
+    """A state dict in the layout torch.save(reference SuperGuessr(HF CLIPVisionModel, 1 layer).state_dict()) writes: keys, shapes,
+    dtypes and non-float buffers as tests/golden/host_cpu.npz recorded them from the reference; float values seeded."""
+    from collections import OrderedDict
+    g = np.load(os.path.join(golden_dir, "host_cpu.npz"))
+    gen = torch.Generator().manual_seed(7)
+    sd, dims = OrderedDict(), iter(g["ckpt_dims"].tolist())
+    for i, (k, dt, nd) in enumerate(zip(g["ckpt_keys"].tolist(), g["ckpt_dtypes"].tolist(), g["ckpt_ndim"].tolist())):
+        shape = tuple(next(dims) for _ in range(nd))
+        dtype = getattr(torch, dt.split(".")[-1])
+        sd[k] = (torch.randn(shape, generator=gen, dtype=dtype) if dtype.is_floating_point
+                 else torch.from_numpy(g[f"ckpt_value_{i}"]).to(dtype).reshape(shape))
+    return sd
+
+
+def test_load_state_reads_a_checkpoint_written_by_the_reference(tmp_path, golden_dir):
     """torch.save(reference SuperGuessr(HF CLIPVisionModel).state_dict()) -> our load_state: every tensor arrives."""
-    from transformers import CLIPVisionConfig, CLIPVisionModel
     from pigeon_amd.clip_embedder import HipCLIPVisionModel
     from pigeon_amd.super_guessr import SuperGuessr
     geo = _geo_csv(tmp_path)
-    ns = reference_loader.load(geo, "unused.csv", "unused_dir")
-    cfg = CLIPVisionConfig(hidden_size=1024, intermediate_size=4096, num_hidden_layers=1, num_attention_heads=16,
-                           image_size=336, patch_size=14, projection_dim=768)
-    torch.manual_seed(7)
-    ref_model = ns.SuperGuessr(CLIPVisionModel(cfg), panorama=True, freeze_base=True, num_candidates=5)
+    ref_sd = _reference_checkpoint(golden_dir)
     path = os.path.join(str(tmp_path), "ref.model")
-    torch.save(ref_model.state_dict(), path)
+    torch.save(ref_sd, path)
     ours = SuperGuessr(HipCLIPVisionModel(_vit_sd(seed=3), layers=1), panorama=True, freeze_base=True, geocell_path=geo)
     ours.load_state(path)
-    ref_sd = ref_model.state_dict()
     mine = ours.state_dict()
     n_base = 0
     for k, v in ref_sd.items():
@@ -136,51 +141,36 @@ def test_host_bank_save_load_roundtrip(tmp_path):
     assert back.num_cells == 23 and back.proto_emb.dtype == np.float32 and back.cell_off.dtype == np.int64
 
 
-@needs_reference
-def test_bank_from_protos_on_the_references_own_protos(tmp_path):
+def test_bank_from_protos_on_the_references_own_protos(tmp_path, golden_dir):
     """`refiner.protos` as the REFERENCE builds it (list of per-cell HF Datasets / None, the object
-    evaluation/evaluate.py:66-75 pickles) -> bank_from_protos -> exactly the CSR bank the files were written from."""
+    evaluation/evaluate.py:66-75 pickles) -> bank_from_protos -> exactly the CSR bank the files were written from.
+    tests/golden/host_protos.pkl is that list, built by the reference's ProtoRefiner from the files written here."""
+    import pickle
     from pigeon_amd.proto_refiner import bank_from_protos
     C = 30
     bank = synthetic.make_bank(C, 6, seed=2, empty_frac=0.1)
     proto_csv = os.path.join(str(tmp_path), "protos.csv")
     ds_dir = os.path.join(str(tmp_path), "hf_train")
     synthetic.write_bank_reference_files(bank, proto_csv, ds_dir)
-    ns = reference_loader.load(_geo_csv(tmp_path, C), proto_csv, ds_dir)
-    ref = ns.ProtoRefiner(topk=5, proto_path=proto_csv, dataset_path=ds_dir)
-    assert sum(p is None for p in ref.protos) == int((np.diff(bank.cell_off) == 0).sum()) > 0
-    hb = bank_from_protos(ref.protos, ds_dir)
+    with open(os.path.join(golden_dir, "host_protos.pkl"), "rb") as f:
+        protos = pickle.load(f)
+    assert len(protos) == C
+    assert sum(p is None for p in protos) == int((np.diff(bank.cell_off) == 0).sum()) > 0
+    hb = bank_from_protos(protos, ds_dir)
     _arrays_equal(hb, bank)
 
 
-@needs_reference
-def test_load_refiner_cache_reads_the_references_pickle(tmp_path):
+def test_load_refiner_cache_reads_the_references_pickle(tmp_path, golden_dir):
     """evaluation/evaluate.py:64-75: the reference caches the whole refiner with `torch.save(refiner, proto_model_path)` and
-    reads `torch.load(...).protos` back.  Written here by the reference's OWN class exactly that way; read back without the
-    reference package importable (the loader must not need `models.proto_refiner`), converted to the CSR bank."""
-    import types
+    reads `torch.load(...).protos` back.  tests/golden/proto.refiner was written by the reference's OWN class exactly that way
+    (ProtoRefiner(20, False, 10000, ..., temperature=1), evaluate.py:73-74; oracle/make_golden.py --only refiner_cache); read
+    back without the reference package importable (the loader must not need `models.proto_refiner`), converted to the CSR bank."""
     from pigeon_amd.proto_refiner import bank_from_protos, load_refiner_cache
-    C = 24
-    bank = synthetic.make_bank(C, 5, seed=3, empty_frac=0.1)
-    proto_csv = os.path.join(str(tmp_path), "protos.csv")
+    C, ppc, bseed, maxm = [int(x) for x in np.load(os.path.join(golden_dir, "refiner_cache.npz"))["meta"]]
+    bank = synthetic.make_bank(C, ppc, seed=bseed, empty_frac=0.05, max_members=maxm)
     ds_dir = os.path.join(str(tmp_path), "hf_train")
-    synthetic.write_bank_reference_files(bank, proto_csv, ds_dir)
-    ns = reference_loader.load(_geo_csv(tmp_path, C), proto_csv, ds_dir)
-    ref = ns.ProtoRefiner(20, False, 10000, proto_path=proto_csv, dataset_path=ds_dir, temperature=1)     # evaluate.py:73-74
-    path = os.path.join(str(tmp_path), "proto.refiner")
-    # pickle locates classes by module path: expose the reference's module under its real name for the duration of the save
-    mods = {"models": types.ModuleType("models"), "models.proto_refiner": types.ModuleType("models.proto_refiner")}
-    mods["models.proto_refiner"].ProtoRefiner = ns.ProtoRefiner
-    saved = {k: sys.modules.get(k) for k in mods}
-    sys.modules.update(mods)
-    try:
-        torch.save(ref, path)                                                                            # evaluate.py:75
-    finally:
-        for k, v in saved.items():
-            if v is None:
-                sys.modules.pop(k, None)
-            else:
-                sys.modules[k] = v
+    synthetic.write_bank_reference_files(bank, os.path.join(str(tmp_path), "protos.csv"), ds_dir)
+    path = os.path.join(golden_dir, "proto.refiner")
     assert "models.proto_refiner" not in sys.modules                     # the read below cannot lean on the reference's code
     protos = load_refiner_cache(path)
     assert isinstance(protos, list) and len(protos) == C
@@ -188,9 +178,10 @@ def test_load_refiner_cache_reads_the_references_pickle(tmp_path):
     _arrays_equal(bank_from_protos(protos, ds_dir), bank)
     with pytest.raises(FileNotFoundError):                               # what the reference's `except FileNotFoundError` relies on
         load_refiner_cache(os.path.join(str(tmp_path), "nope.refiner"))
-    torch.save({"not": "a refiner"}, path + ".bad")
+    bad = os.path.join(str(tmp_path), "proto.refiner.bad")
+    torch.save({"not": "a refiner"}, bad)
     with pytest.raises(ValueError):
-        load_refiner_cache(path + ".bad")
+        load_refiner_cache(bad)
 
 
 # ------------------------------------------------------------------------------------------------ metrics
@@ -215,17 +206,17 @@ def test_compute_geoguessr_metrics_matches_reference_fixture(golden_dir):
     assert res2["Geocell_top5_accuracy"] == res["Geocell_top5_accuracy"]
 
 
-@needs_reference
-def test_metrics_against_live_reference_functions():
+def test_metrics_against_live_reference_functions(golden_dir):
+    """The reference's geoguessr_score / percentage_within_radius / topk_geocell_accuracy (evaluation/metrics.py) on seeded inputs,
+    inputs and outputs as tests/golden/host_cpu.npz recorded them: equal, not close."""
     from pigeon_amd import evaluate as ev
-    mt = reference_loader.load_metrics()
-    rng = np.random.default_rng(5)
-    d = np.exp(rng.uniform(-3, 9, 1000))
-    assert ev.geoguessr_score(d) == mt.geoguessr_score(d)
-    for km in (1, 25, 750):
-        assert ev.percentage_within_radius(d, km) == mt.percentage_within_radius(d, km)
-    lab, top = rng.integers(0, 9, 200), rng.integers(0, 9, (200, 5))
-    assert ev.topk_geocell_accuracy(lab, top) == mt.topk_geocell_accuracy(lab, top)
+    g = np.load(os.path.join(golden_dir, "host_cpu.npz"))
+    d = g["metrics_d"]
+    assert ev.geoguessr_score(d) == g["metrics_score"]
+    for km, want in zip(g["metrics_km"].tolist(), g["metrics_within"]):
+        assert ev.percentage_within_radius(d, km) == want
+    lab, top = g["metrics_labels"], g["metrics_top5"]
+    assert ev.topk_geocell_accuracy(lab, top) == g["metrics_topk"]
 
 
 # ------------------------------------------------------------------------------------------------ embedding files
@@ -265,40 +256,6 @@ def test_evaluate_raises_on_missing_checkpoint(tmp_path):
     with pytest.raises(FileNotFoundError):
         evaluate(os.path.join(str(tmp_path), "missing.model"), [], yfcc=False, landmarks=False, refine=False,
                  geocell_path=_geo_csv(tmp_path))
-
-
-# ------------------------------------------------------------------------------------------------ fixtures are current
-@needs_reference
-def test_fast_golden_fixtures_regenerate_bit_identically(tmp_path, golden_dir, monkeypatch):
-    """oracle/make_golden.py --only head|geo|refine re-run against /root/reference reproduces the committed files: integer /
-    index arrays exactly, floating-point arrays bit for bit on the authoring CPU and to the last ulps elsewhere (the 24-layer
-    fixtures take minutes and are checked by hand when they change)."""
-    import importlib
-    import sys
-    from oracle import make_golden
-    importlib.reload(make_golden)
-    out = os.path.join(str(tmp_path), "golden")
-    os.makedirs(out)
-    monkeypatch.setattr(make_golden, "GOLD", out)
-    for name in ("head", "geo", "refine"):
-        monkeypatch.setattr(sys, "argv", ["make_golden.py", "--only", name])
-        make_golden.main()
-        a, b = np.load(os.path.join(out, f"{name}.npz")), np.load(os.path.join(golden_dir, f"{name}.npz"))
-        assert sorted(a.files) == sorted(b.files), name
-        for k in a.files:
-            if k in ("matrix_f32x", "pairs_f32y"):          # torch's CPU fp32 cos: last ulp depends on the thread partition
-                m = ~(np.isnan(a[k]) | np.isnan(b[k]))
-                np.testing.assert_allclose(a[k][m], b[k][m], rtol=3e-5, atol=0.5)
-                continue
-            if a[k].dtype.kind == "f":
-                # bit-identical on the CPU type the fixtures were written on; torch's CPU kernels choose vector width and
-                # summation order by CPU, so elsewhere the last ulps of a K = 1024 fp32 dot product / an fp64 sin-cos chain move
-                assert a[k].shape == b[k].shape and np.array_equal(np.isnan(a[k]), np.isnan(b[k])), (name, k)
-                m = ~np.isnan(a[k])
-                tol = dict(rtol=2e-5, atol=2e-4) if a[k].dtype == np.float32 else dict(rtol=1e-11, atol=1e-6)
-                np.testing.assert_allclose(a[k][m], b[k][m], err_msg=f"{name}/{k}", **tol)
-                continue
-            assert np.array_equal(a[k], b[k]), (name, k)
 
 
 def test_load_refiner_cache_committed_reference_pickle(golden_dir, tmp_path):
