@@ -37,9 +37,10 @@ extern "C" {
 #define PG_DTYPE_F16     2
 #define PG_DTYPE_F64     3
 
-#define PG_ABI_VERSION   5   /* 2: pg_vit_cfg.precise, pg_vit_forward_precise, pg_head_margin (round 4); 3: pg_head_certainty, pg_refine_forward_ex,
+#define PG_ABI_VERSION   6   /* 2: pg_vit_cfg.precise, pg_vit_forward_precise, pg_head_margin (round 4); 3: pg_head_certainty, pg_refine_forward_ex,
                               * pg_refine_certainty, pg_tune_gemm_raster (round 5); 4: the deferred exact tier -- pg_requeue_append,
-                              * pg_rows_to_slots, pg_requeue_take, pg_scatter_rows, pg_head_wstats (round 6); 5: pg_embedding_debias (round 6) */
+                              * pg_rows_to_slots, pg_requeue_take, pg_scatter_rows, pg_head_wstats (round 6); 5: pg_embedding_debias (round 6);
+                              * 6: pg_gemm_plan replaces pg_gemm_route */
 
 const char* pg_last_error(void);
 int pg_abi_version(void);
@@ -148,14 +149,16 @@ int pg_tune_gemm_tail_shape(int min_k, int min_n);
 int pg_tune_gemm_raster(int gn);
 /* Small and middle batches (round 6; also env PIGEON_GEMM_MID=0 / 1 / 2): a GEMM launch of up to ~64 images (40 000 token rows) is
  * routed between the variant's own persistent kernel (384 x 256 tiles where they exist), the 256 x 256 persistent kernel and a 128 x 128
- * one-tile-per-block kernel (csrc/gemm_mid.hip) by a cost model of how their row panels fill rounds of the CUs (csrc/gemm_bf16.hip
+ * one-tile-per-block kernel (csrc/gemm_mid.hip) by a cost model of how their row panels fill rounds of the CUs (csrc/gemm_plan.hip
  * gemm_model_us).  1 = on (default), 0 = a variant always means its own kernel, 2 = gemm_mid.hip is the only alternative (A/B arm).
  * All GEMM kernels produce the same bits for a row: timing only, never results. */
 int pg_tune_gemm_mid(int on);
-/* Which kernel pg_op_gemm16* / the encoder would launch for this shape under the current knobs: *kind = 0 the 384 x 256 persistent
- * kernel, 1 the 256 x 256 one, 2 csrc/gemm_mid.hip, -1 none of them (a non-persistent variant or shape).  variant 0 = the default.
+/* What pg_op_gemm16* / the encoder would launch for this shape under the current knobs (variant 0 = the default): *kernel takes rows
+ * [0, *rows_main) -- 0 the 384 x 256 persistent kernel, 1 the 256 x 256 one, 2 csrc/gemm_mid.hip, 3 csrc/gemm_tail.hip, 4 the
+ * one-tile-per-block kernel of csrc/gemm_bf16.hip -- and *rest the remaining rows: -1 none, 2 gemm_mid, 3 gemm_tail.  PG_EINVAL where
+ * the GEMM launch refuses the variant / shape / epilogue (a persistent schedule the build lacks is refused by the launch only).
  * Host arithmetic only: no launch, no device work (tests/test_host_cpu.py checks the picks against profiles/r06/gemm_three_sweep.txt). */
-int pg_gemm_route(int variant, int epi, int M, int N, int K, int* kind);
+int pg_gemm_plan(int variant, int epi, int M, int N, int K, int* kernel, int* rows_main, int* rest);
 /* Exact mode's attention (also env PIGEON_EXACT_ATTN=f32): 0 = split-fp16 operands on v_mfma_f32_32x32x16_f16 (default, round 5),
  * 1 = plain fp32 on v_mfma_f32_32x32x2_f32 (round 4's kernel; the A/B arm).  Both are fp32-grade (6e-7 / 8e-7 against fp64). */
 int pg_tune_exact_attention(int use_f32_mfma);

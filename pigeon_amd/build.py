@@ -15,14 +15,8 @@ CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(CSRC, "build")
 LIB = os.path.join(HERE, "libpigeon_hip.so")
 # the product library: production kernels only
-SOURCES = ["vit.hip", "gemm_bf16.hip", "gemm_pp.hip", "gemm_pp6.hip", "gemm_tail.hip", "gemm_mid.hip", "attention.hip", "rowops.hip", "precise.hip",
+SOURCES = ["vit.hip", "gemm_plan.hip", "gemm_bf16.hip", "gemm_pp.hip", "gemm_pp6.hip", "gemm_tail.hip", "gemm_mid.hip", "attention.hip", "rowops.hip", "precise.hip",
            "preprocess.hip", "geo_proto.hip", "head.hip", "refine.hip", "certainty.hip", "requeue.hip", "comm.hip"]
-# additionally in the tools build (--dev), from tools/csrc/: kernel generations the product superseded, kept for A/B work
-# (gemm variant 64 = gemm_w4.hip; attention variants 1, 4..15 = attention_old.hip)
-DEV_DIR = os.path.join(os.path.dirname(HERE), "tools", "csrc")
-# (round 5: the two files moved to the branch archive/kernel-generations-r04; a checkout that has them under tools/csrc/ again gets
-# them compiled in with -DPIGEON_OLD_GENERATIONS)
-DEV_SOURCES = [f for f in (os.path.join(DEV_DIR, "gemm_w4.hip"), os.path.join(DEV_DIR, "attention_old.hip")) if os.path.exists(f)]
 HEADERS = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "pigeon_internal.h"), os.path.join(CSRC, "gemm_epi.h"),
            os.path.join(CSRC, "attention_common.h"),
            os.path.join(os.path.dirname(HERE), "include", "pigeon_hip.h")]
@@ -45,14 +39,14 @@ def _stale(target: str, deps) -> bool:
 
 def build(force: bool = False, verbose: bool = True, dev: bool = False) -> str:
     """dev=False: the product library libpigeon_hip.so -- production kernels only.
-    dev=True:  libpigeon_hip_dev.so, compiled with -DPIGEON_ABLATIONS: additionally the superseded kernel generations, A/B arms
+    dev=True:  libpigeon_hip_dev.so, compiled with -DPIGEON_ABLATIONS: additionally the older schedules and tilings, A/B arms
                and the timing-only ablation kernels (which compute WRONG results by construction) that tools/ selects through
                PIGEON_GEMM_VARIANT / PIGEON_ATTN_VARIANT; load it with PIGEON_HIP_LIB=pigeon_amd/libpigeon_hip_dev.so."""
     global OBJ, LIB
     obj_dir = os.path.join(CSRC, "build_dev" if dev else "build")
     lib = os.path.join(HERE, "libpigeon_hip_dev.so" if dev else "libpigeon_hip.so")
-    flags = FLAGS + (["-DPIGEON_ABLATIONS"] if dev else []) + (["-DPIGEON_OLD_GENERATIONS"] if dev and len(DEV_SOURCES) == 2 else [])
-    return _build(obj_dir, lib, flags, force, verbose, SOURCES + (DEV_SOURCES if dev else []))
+    flags = FLAGS + (["-DPIGEON_ABLATIONS"] if dev else [])
+    return _build(obj_dir, lib, flags, force, verbose, SOURCES)
 
 
 def _build(OBJ: str, LIB: str, FLAGS, force: bool, verbose: bool, SOURCES) -> str:

@@ -436,90 +436,6 @@ static int launch_a3w2(const GemmArgs& g0, int epi, hipStream_t s) {
 #undef PG_LAUNCH
 }
 
-// EPI_RESID_STAT on the 384 x 256 kernel (round 3): bit 0 = long-K GEMMs (fc2, K >= 2048), bit 1 = short-K ones (out-projection).
-// Results are bit-identical either way; this only selects the tile shape.  Env PIGEON_GEMM_RESID6 (A/B).  Measured on the 512-image
-// step (profiles/r03/pp6_resid_stat_ab.txt): fc2 2.224 -> 2.152 ms (-3.2 %; W is re-streamed through every XCD's L2 12 instead of 18
-// times), out-projection 0.90 -> 0.976 ms (its epilogue is 43 % of a tile, first build): the default takes fc2 only, +0.9 % end to end.
-#ifndef PG_DEFAULT_GEMM_RESID6
-#define PG_DEFAULT_GEMM_RESID6 1
-#endif
-static bool resid6_enabled(int K) {
-    static int mask = -1;
-    if (mask < 0) { const char* e = getenv("PIGEON_GEMM_RESID6"); mask = e ? atoi(e) : PG_DEFAULT_GEMM_RESID6; if (mask < 0) mask = 0; }
-    return (mask & (K >= 2048 ? 1 : 2)) != 0;
-}
-// cost model of the small-batch choice (pg_gemm_launch): microseconds per 64-wide K tile of one tile period
-#define PG_MID_US_KT_P6 1.75     // 384 x 256 persistent tile on a mostly idle chip (2.4 GHz)
-#define PG_MID_US_KT_PP 1.25     // 256 x 256
-#define PG_TAIL_US 36.0          // gemm_tail.hip on a <= 768-row tail, either shape (profiles/r02/gemm_tail.txt, profiles/r06/step_kernel_stats.csv)
-#define PG_MID_US_KT_MID 0.44    // 128 x 128 through the 3-stage ring with the producer wave (0.41 measured on fc2's 64 K tiles, profiles/r06/
-                                 // gemm_three_sweep_producer.txt; 0.58 - 0.62 while the MFMA waves issued their own DMAs: gemm_mid_sweep.txt)
-static bool use_pp6(int variant, int epi, int N, int K) {
-    return variant == 56 && pg_gemm_pp6_supported(epi, N, K) && (epi != EPI_RESID_STAT || resid6_enabled(K));
-}
-
-// Modelled time (us) of one GEMM launch on `ncu` CUs through kernel `kind` (0 = 384 x 256 persistent, 1 = 256 x 256 persistent,
-// 2 = gemm_mid.hip), for batches of up to ~64 images: the routing of pg_gemm_launch below.  A persistent launch is a sequence of
-// rounds; a round's tile period grows with the share f of the CUs it keeps busy (the power cap: 2.4 GHz on an idle chip, ~1.7 GHz on
-// a full one), c(f) = ci + (cf - ci) f^2 microseconds per 64-wide K tile, plus an epilogue the first round pays in full and the later
-// ones partly (the next tile's operands are in flight under it).  Constants fitted to profiles/r06/gemm_three_sweep.txt (the model's
-// four GEMM shapes x 1 .. 64 images x the three kernels): the pick is the measured best, or within 0.4 % of it, in all 36 cells.
-// (Second session: gemm_mid's two constants refitted to gemm_three_sweep_producer.txt -- its producer wave; the pick is within 9 %
-// of the best in every cell of the first file and of the two residual shapes of the second, tests/test_host_cpu.py.)
-static double gemm_model_us(int kind, int M, int N, int K, int epi, int ncu) {
-    const bool resid = epi == EPI_RESID || epi == EPI_RESID_STAT;
-    const bool gelu = epi == EPI_GELU || epi == EPI_GELU_LN;
-    const double kt = K / 64;
-    if (kind == 2) {
-        const int64_t tiles = (int64_t)((M + 127) / 128) * (N / 128);
-        return (double)((tiles + ncu - 1) / ncu) * (kt * PG_MID_US_KT_MID + (resid ? 8.0 : 5.5));
-    }
-    const int bm = kind == 0 ? 384 : 256;
-    const double ci = kind == 0 ? 1.6 : 1.1, cf = kind == 0 ? 3.0 : 1.8;
-    const double e1 = kind == 0 ? (resid ? 7.0 : (gelu ? 9.0 : 6.0)) : (resid ? 12.0 : (gelu ? 9.0 : 7.0));
-    const double e2 = kind == 0 ? 3.0 : 6.0;
-    const int64_t tiles = (int64_t)((M + bm - 1) / bm) * (N / 256);
-    const int64_t full = tiles / ncu;
-    const double f = (double)(tiles % ncu) / (double)ncu;
-    double t = 0.0;
-    if (full > 0) t += kt * cf + e1 + (double)(full - 1) * (kt * cf + e2);
-    if (f > 0.0) t += kt * (ci + (cf - ci) * f * f) + (full > 0 ? e2 : e1);
-    return t;
-}
-#define PG_ROUTE_MAX_ROWS 40000   // the routing model is fitted up to 64 images (36 928 token rows); above that a variant means its kernel
-static int route_max_rows() {     // (env PIGEON_GEMM_ROUTE_MAX_ROWS: experiments beyond the fitted range)
-    static int v = -1;
-    if (v < 0) { const char* e = getenv("PIGEON_GEMM_ROUTE_MAX_ROWS"); v = e ? atoi(e) : PG_ROUTE_MAX_ROWS; if (v < 0) v = 0; }
-    return v;
-}
-
-// Which kernel a launch of the persistent variants takes: 0 = 384 x 256 persistent, 1 = 256 x 256 persistent, 2 = gemm_mid.hip; -1 = not
-// a persistent variant / shape (the caller's dispatch decides).  A pure function of the shape, the knobs and the CU count.
-static int gemm_route(int variant, int epi, int M, int N, int K) {
-    const bool six = use_pp6(variant, epi, N, K);
-    const bool pp = !six && (variant == 56 || (variant >= 30 && variant < 50)) && N % 256 == 0 && K % 128 == 0;
-    if (!six && !pp) return -1;
-    const int own = six ? 0 : 1;
-    if (!(pg_gemm_mid_on() && M <= route_max_rows() && epi != EPI_PATCH && epi >= EPI_QKV && epi <= EPI_GELU_LN)) return own;
-    int ncu = pg_num_cus();
-    if (pg_gemm_block_cap() > 0 && pg_gemm_block_cap() < ncu) ncu = pg_gemm_block_cap();
-    const double t_own = gemm_model_us(own, M, N, K, epi, ncu);
-    const double t_pp = (six && pg_gemm_route_pp256()) ? gemm_model_us(1, M, N, K, epi, ncu) : 1e30;
-    const double t_mid = pg_gemm_mid_supported(epi, N, K) ? gemm_model_us(2, M, N, K, epi, ncu) : 1e30;
-    // the 256 x 256 kernel has to win by a margin: where the model calls it level with the 384 x 256 kernel (64 images) or with
-    // gemm_mid (2 and 8 images) the encoder measured 1 - 3 % SLOWER with it in place (profiles/r06/latency_route_ab.txt: a
-    // launch in a forward is not a launch in a loop of its own); where it wins by more, the encoder gains 3 - 9 %
-    const bool pp_wins = t_pp < 0.90 * t_own && t_pp < 0.90 * t_mid;
-    if (pp_wins) return 1;
-    return t_mid < t_own ? 2 : own;
-}
-// (exported for the host-logic tests and tools: no launch, no device work)
-extern "C" int pg_gemm_route(int variant, int epi, int M, int N, int K, int* kind) {
-    if (!kind || M <= 0 || N <= 0 || K <= 0) { pg_set_error("gemm_route: bad argument"); return PG_EINVAL; }
-    *kind = gemm_route(variant ? variant : pg_default_gemm_variant(), epi, M, N, K);
-    return PG_OK;
-}
-
 template <typename T>
 static int gemm_dispatch(GemmArgs& g, int epi, int variant, hipStream_t s) {
     switch (variant) {
@@ -540,142 +456,23 @@ static int gemm_dispatch(GemmArgs& g, int epi, int variant, hipStream_t s) {
         case 22: g.gn = 1 << 20; return launch_cfg<T, 256, 256, 2, 4, false, true, 2>(g, epi, s);   // no ds_reads
         case 23: g.gn = 1 << 20; return launch_cfg<T, 256, 256, 2, 4, false, true, 3>(g, epi, s);   // neither
 #endif
-        default: pg_set_error("gemm: variant %d is not part of this build (product variants: 8, 33, 36, 56, 70; the rest needs the "
-                              "-DPIGEON_ABLATIONS tools build, python -m pigeon_amd.build --dev)", variant); return PG_EINVAL;
+        default: pg_set_error("gemm: variant %d is not part of this build", variant); return PG_EINVAL;
     }
 }
 
+// the N tile of the one-tile variant (the `case`s above), 0 = not part of this build
+int pg_gemm_one_tile_bn(int variant) {
+    switch (variant) {
+        case 8: return 256;
 #ifdef PIGEON_ABLATIONS
-static void* g_dbg_ts = nullptr;
-// tools build: arm (buf != null) / disarm the PG_TS time stamps of the persistent kernels; buf = 2 * 16 * 8 * 12 uint64 on the device
-extern "C" int pg_dbg_timestamps(void* buf) { g_dbg_ts = buf; return PG_OK; }
+        case 1: case 4: case 5: case 6: case 7: case 11: case 21: case 22: case 23: return 256;
+        case 2: case 3: return 128;
 #endif
+        default: return 0;
+    }
+}
 
-int pg_gemm_launch(int dtype, const void* A, int64_t lda, const void* W, int64_t ldw, const float* bias, void* out, int64_t ldc,
-                   int M, int N, int K, int epi, float qscale, int qcols, const float* aux, int variant,
-                   hipStream_t s, const PgGemmExtra* extra) {
-    if (M <= 0) return PG_OK;
-    GemmArgs g;
-    g.A = (const uint16_t*)A; g.lda = lda; g.W = (const uint16_t*)W; g.ldw = ldw > 0 ? ldw : K; g.bias = bias; g.out = out; g.ldc = ldc;
-    g.M = M; g.N = N; g.K = K; g.qscale = qscale; g.qcols = qcols; g.aux = aux;
-    g.tilesM = 0; g.tilesN = 0; g.ntiles = 0; g.part_tiles = 0; g.gn = 0; g.stagger = 0; g.xcd_stagger_ticks = 0;
-    if (extra) g.ex = *extra;
-    if (g.ex.parts > 1) {                                    // several products in one launch: 256 x 256 persistent kernel, EPI_F32 only
-        if (epi != EPI_F32 || N % 256 != 0 || K % 128 != 0) { pg_set_error("gemm: parts > 1 needs EPI_F32, N %% 256 == 0, K %% 128 == 0"); return PG_EINVAL; }
-        return pg_gemm_pp_launch(dtype, g, epi, 36, s);
-    }
-    if ((epi == EPI_GELU || epi == EPI_RESID || epi >= EPI_RESID_STAT) && !bias) { pg_set_error("gemm: epilogue %d needs a bias", epi); return PG_EINVAL; }
-    if (epi == EPI_RESID_STAT && (!g.ex.x16 || !g.ex.statpart || g.ex.ldx != ldc)) { pg_set_error("gemm: EPI_RESID_STAT needs x16 / statpart and ldx == ldc"); return PG_EINVAL; }
-    if ((epi == EPI_QKV_LN || epi == EPI_GELU_LN) && (!g.ex.colsum || !g.ex.rowstat)) { pg_set_error("gemm: LN epilogue needs colsum / rowstat"); return PG_EINVAL; }
-    if (epi == EPI_PATCH && !aux) { pg_set_error("gemm: patch epilogue needs aux"); return PG_EINVAL; }
-    if (epi == EPI_GELU_X3 && (ldc != 3 * (int64_t)N || dtype != PG_DTYPE_F16 || N % 256 != 0 || K % 128 != 0)) {
-        pg_set_error("gemm: EPI_GELU_X3 writes the fp16 triple [M][3N]: ldc == 3 N, fp16 operands, N %% 256 == 0, K %% 128 == 0 (ldc=%lld N=%d K=%d)",
-                     (long long)ldc, N, K);
-        return PG_EINVAL;
-    }
-    if (epi < EPI_QKV || epi > EPI_GELU_X3) { pg_set_error("gemm: bad epilogue %d", epi); return PG_EINVAL; }
-    if ((lda % 8) || (ldc % 8) || (qcols % 8) || (g.ldw % 8) || g.ldw < K) { pg_set_error("gemm: lda/ldw/ldc/qcols must be multiples of 8, ldw >= K"); return PG_EINVAL; }
-    if (variant == 0) variant = pg_default_gemm_variant();
-    {
-        // XCD stagger (gemm_epi.h): total spread = fraction x estimated tile period.  Tile periods measured on MI355X
-        // (profiles/r02): 256x256 tiles 25 us + 1.63 us per 64-wide K tile (fp32 residual epilogues), 384x256 tiles
-        // 8 us (+4 us with the GELU) + 2.44 us per K tile.
-        const float f = pg_gemm_stagger_fraction();
-        if (f > 0.f && M >= 256 * 64) {
-            const bool six = use_pp6(variant, epi, N, K);
-            const float period_us = six ? ((epi == EPI_GELU || epi == EPI_GELU_LN ? 12.f : 8.f) + 2.44f * (K / 64))
-                                        : ((epi == EPI_RESID || epi == EPI_RESID_STAT ? 25.f : 10.f) + 1.63f * (K / 64));
-            g.xcd_stagger_ticks = (int)(f * period_us * 100.f);              // 100 ticks per us
-        }
-    }
-    if (g.ex.stat_rows <= 0) g.ex.stat_rows = M;
-#ifdef PIGEON_ABLATIONS
-    if (g_dbg_ts && epi != EPI_PATCH) { g.aux = (const float*)g_dbg_ts; g.stagger = -7; }
-    else if (epi == EPI_RESID_STAT) { static const bool abl = getenv("PIGEON_EPI_ABL") != nullptr; if (abl) g.stagger = -11; }
-#endif
-    if (variant == 71) {                                     // the whole problem through the 128 x 128 kernel of small batches (tests, tools)
-        if (!pg_gemm_mid_supported(epi, N, K)) { pg_set_error("gemm: variant 71 (gemm_mid) does not support epi=%d N=%d K=%d", epi, N, K); return PG_EINVAL; }
-        return pg_gemm_mid_launch(dtype, g, epi, s);
-    }
-    if (variant == 70) {                                     // the whole problem through the small-tile tail kernel (tests, tools)
-        if (!pg_gemm_tail_supported(epi, N, K)) { pg_set_error("gemm: variant 70 (gemm_tail) does not support epi=%d N=%d K=%d", epi, N, K); return PG_EINVAL; }
-        return pg_gemm_tail_launch(dtype, g, epi, 0, s);
-    }
-    {
-        // Small and middle batches (round 6).  The product variant (56) means "384 x 256 tiles where they exist, 256 x 256 elsewhere",
-        // chosen for the 512-image step, where a launch is 12 - 50 rounds.  Up to ~64 images a launch is 1 - 7 rounds and what
-        // decides is how the row panels of a tile shape fill whole rounds of the CUs: one panorama (2308 rows) is 7 panels of 384
-        // or 10 of 256 or 19 of 128; 16 images leave the 384-row kernel a second round with 44 of 256 CUs busy.  All three kernels
-        // produce the same bits for a row (tests/test_gpu_parity.py), so the choice is a timing decision, taken by gemm_model_us
-        // above (pg_tune_gemm_mid(0) / PIGEON_GEMM_MID=0: the variant's own kernel, always).  Measured
-        // (profiles/r06/gemm_three_sweep.txt, latency_route.txt): 16 images QKV 79.7 -> 64.6 us, fc2 123.5 -> 94.6; one panorama fc1
-        // 38.7 -> 31.7.
-        const int kind = gemm_route(variant, epi, M, N, K);
-        if (kind == 2) return pg_gemm_mid_launch(dtype, g, epi, s);
-        if (kind == 1 && use_pp6(variant, epi, N, K)) return pg_gemm_pp_launch(dtype, g, epi, 36, s);
-    }
-    {
-        // Tail split: if the tiles do not fill the persistent kernel's last round and the rows beyond the last whole round are
-        // few, the persistent kernel gets the rows that make whole rounds and a small-tile kernel the rest.  All three produce
-        // the same bits for a row, so the cut changes timing only.  WHERE to cut is round 2's measurement (vit.hip, the MIN_K /
-        // MIN_N thresholds: fc2 and fc1; for out-projection and QKV the extra launch costs what the 8-tile last round did --
-        // measured again in round 6 with the cheaper tail kernel below, profiles/r06/tail_mid_ab.txt: still nothing end to end).
-        // WHICH kernel takes the tail is a cost model: gemm_tail.hip (32 x 64 one-wave tiles) needs ~36 us for the benchmark
-        // batch's 512 rows whatever the shape; gemm_mid.hip (round 6) does a K = 1024 tail in 15 - 19 us
-        // (profiles/r06/gemm_mid_sweep.txt, the n = 1 column) and a K = 4096 one in 44: fc1's tail goes through it (the fc1
-        // launch pair 2.257 -> 2.237 ms, 0.4347 -> 0.4384 of the MFMA peak on one box), fc2's stays.
-        const bool six = use_pp6(variant, epi, N, K);
-        const bool pp = !six && (variant == 56 || (variant >= 30 && variant < 50)) && N % 256 == 0 && K % 128 == 0;
-        const int tail_max = pg_gemm_tail_rows();
-        if ((six || pp) && tail_max > 0) {
-            const int bm = six ? 384 : 256;
-            int ncu = pg_num_cus();
-            if (pg_gemm_block_cap() > 0 && pg_gemm_block_cap() < ncu) ncu = pg_gemm_block_cap();
-            const int tilesN = N / 256;
-            const int64_t ntiles = (int64_t)((M + bm - 1) / bm) * tilesN;
-            const int64_t rounds = ntiles / ncu;
-            if (rounds >= 1 && ntiles % ncu != 0) {
-                const int64_t m_main = (rounds * ncu / tilesN) * bm;         // row panels that fit into `rounds` whole rounds
-                if (m_main > 0 && m_main < M && M - m_main <= tail_max) {
-                    const bool resid = epi == EPI_RESID || epi == EPI_RESID_STAT;
-                    const double kt = K / 64;
-                    // the round the cut removes (constants of the small-batch model above: a lower bound on a busy chip)
-                    const double t_round = six ? kt * PG_MID_US_KT_P6 + (resid ? 14.0 : 9.0) : kt * PG_MID_US_KT_PP + (resid ? 20.0 : 8.0);
-                    const int64_t tiles_m = (int64_t)((M - m_main + 127) / 128) * (N / 128);
-                    const double t_mid = (double)((tiles_m + ncu - 1) / ncu) * (kt * PG_MID_US_KT_MID + (resid ? 6.0 : 5.0)) + 3.0;   // + a launch
-                    const bool cut = K >= pg_gemm_tail_min_k() || N >= pg_gemm_tail_min_n();
-                    const bool by_mid = cut && pg_gemm_mid_on() && pg_gemm_mid_supported(epi, N, K) && t_mid < PG_TAIL_US && t_mid < t_round;
-                    const bool by_tail = cut && !by_mid && pg_gemm_tail_supported(epi, N, K);
-                    if (by_mid || by_tail) {
-                        GemmArgs gm = g;
-                        gm.M = (int)m_main;
-                        const int rc = six ? pg_gemm_pp6_launch(dtype, gm, epi, s) : pg_gemm_pp_launch(dtype, gm, epi, variant == 56 ? 36 : variant, s);
-                        if (rc != PG_OK) return rc;
-                        return by_mid ? pg_gemm_mid_launch(dtype, g, epi, s, (int)m_main) : pg_gemm_tail_launch(dtype, g, epi, (int)m_main, s);
-                    }
-                }
-            }
-        }
-    }
-    if (variant == 64) {                                     // one-wave-per-SIMD persistent kernel (gemm_w4.hip: archived, branch archive/kernel-generations-r04)
-#if defined(PIGEON_ABLATIONS) && defined(PIGEON_OLD_GENERATIONS)
-        if (pg_gemm_w4_supported(epi, N, K)) return pg_gemm_w4_launch(dtype, g, epi, s);
-        variant = 36;
-#else
-        pg_set_error("gemm: variant 64 (gemm_w4) is experimental and not part of the product library (python -m pigeon_amd.build --dev)");
-        return PG_EINVAL;
-#endif
-    }
-    if (variant == 56) {                                     // 384 x 256 tiles where they exist, the product kernel elsewhere
-        if (use_pp6(variant, epi, N, K)) return pg_gemm_pp6_launch(dtype, g, epi, s);
-        variant = 36;
-    }
-    if (variant >= 30 && variant < 50) {
-        // the persistent kernel needs N % 256 == 0 and an even number of K tiles; everything the model launches qualifies
-        if (N % 256 == 0 && K % 128 == 0) return pg_gemm_pp_launch(dtype, g, epi, variant, s);
-        variant = 8;
-    }
-    if (epi >= EPI_RESID_STAT) { pg_set_error("gemm: epilogue %d exists only in the persistent kernel (variants 30..49, N %% 256 == 0, K %% 128 == 0)", epi); return PG_EINVAL; }
+int pg_gemm_one_tile_launch(int dtype, GemmArgs g, int epi, int variant, hipStream_t s) {
     if (dtype == PG_DTYPE_F16) return gemm_dispatch<T_F16>(g, epi, variant, s);
     if (dtype == PG_DTYPE_BF16) return gemm_dispatch<T_BF16>(g, epi, variant, s);
     pg_set_error("gemm: operand dtype must be PG_DTYPE_F16 or PG_DTYPE_BF16 (got %d)", dtype);

@@ -23,9 +23,14 @@ struct GemmArgs {
     PgGemmExtra ex;               // LayerNorm-fold epilogues (EPI_RESID_STAT / EPI_QKV_LN / EPI_GELU_LN)
 };
 
-// gemm_pp.hip: persistent ping-pong kernel (variants 30..39); tilesM/tilesN/ntiles are filled in by the callee
+// The kernels' launchers (gemm_plan.hip's pg_gemm_launch calls them); tilesM/tilesN/ntiles are filled in by the callee.
+// gemm_bf16.hip: the one-tile-per-block kernel (variant 8; the older tilings in the tools build).  pg_gemm_one_tile_bn: its N tile
+// for `variant`, 0 = not part of this build.
+int pg_gemm_one_tile_bn(int variant);
+int pg_gemm_one_tile_launch(int dtype, GemmArgs g, int epi, int variant, hipStream_t s);
+// gemm_pp.hip: persistent ping-pong kernel (variants 30..49)
 int pg_gemm_pp_launch(int dtype, GemmArgs g, int epi, int variant, hipStream_t s);
-// gemm_pp6.hip: the same kernel with a 384 x 256 block tile, 16-bit-output epilogues only (variant 56, experimental)
+// gemm_pp6.hip: the same kernel with a 384 x 256 block tile, 16-bit-output epilogues and EPI_RESID_STAT (variant 56)
 bool pg_gemm_pp6_supported(int epi, int N, int K);
 int pg_gemm_pp6_launch(int dtype, GemmArgs g, int epi, hipStream_t s);
 
@@ -44,13 +49,6 @@ __device__ __forceinline__ void xcd_stagger_wait(int ticks) {
     while (__builtin_amdgcn_s_memrealtime() < until) __builtin_amdgcn_s_sleep(16);
 }
 
-// gemm_w4.hip (tools build only, variant 64, experimental): persistent kernel with one wave per SIMD (4 waves, 128 x 128 wave
-// tiles, accumulators in AGPRs).  Level with the ping-pong kernels per K tile, slower end to end.
-#ifdef PIGEON_ABLATIONS
-bool pg_gemm_w4_supported(int epi, int N, int K);
-int pg_gemm_w4_launch(int dtype, GemmArgs g, int epi, hipStream_t s);
-#endif
-
 // gemm_tail.hip: rows [m_begin, M) of a problem in 32 x 64 one-wave tiles, bit-identical to the persistent kernels (variant 70
 // runs a whole problem through it; pg_gemm_launch uses it for the rows that do not fill the persistent kernels' last round)
 bool pg_gemm_tail_supported(int epi, int N, int K);
@@ -61,7 +59,7 @@ bool pg_gemm_mid_supported(int epi, int N, int K);
 int pg_gemm_mid_launch(int dtype, GemmArgs g, int epi, hipStream_t s, int m_begin = 0);
 
 // Tools build only: wall-clock stamps (100 MHz) from inside the persistent kernels, blocks 0 and 100, every wave, first 16 tiles:
-// buf[((blk * 16 + tile) * 8 + wave) * 12 + slot].  Armed by pg_dbg_timestamps(buf) (gemm_bf16.hip), read by tools/epi_timeline.py.
+// buf[((blk * 16 + tile) * 8 + wave) * 12 + slot].  Armed by pg_dbg_timestamps(buf) (gemm_plan.hip), read by tools/epi_timeline.py.
 #ifdef PIGEON_ABLATIONS
 #define PG_TS(g, iter, wave, slot)                                                                                             \
     do {                                                                                                                       \
@@ -110,8 +108,7 @@ __device__ __forceinline__ f32x4 quick_gelu4(f32x4 v) {
     return f32x4{a0[0], a0[1], a1[0], a1[1]};
 }
 
-// ==== ONE definition of the fused epilogue ARITHMETIC for the slab-transposing kernels (gemm_pp / gemm_pp6 / gemm_tail, and
-// gemm_w4 in the tools build).  Round 2 kept a hand copy of these expressions in every file and held them together with
+// ==== ONE definition of the fused epilogue ARITHMETIC for the slab-transposing kernels (gemm_pp / gemm_pp6 / gemm_tail / gemm_mid).  Round 2 kept a hand copy of these expressions in every file and held them together with
 // bit-compare tests only; a row's value must not depend on which kernel (persistent tile, tail tile) computed it, so the
 // expressions -- including the association order of the row statistics -- live here and nowhere else.  A lane holds 8 outputs of
 // one row as two f32x4 (`lo`, `hi`); which columns those are (8 consecutive, or 4k.. and 32+4k.. for EPI_RESID_STAT) is the

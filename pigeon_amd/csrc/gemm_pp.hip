@@ -866,17 +866,6 @@ int dispatch_pp(GemmArgs& g, int epi, int variant, int nblk, hipStream_t s) {
     }
 }
 
-int num_cus() {
-    static int n = 0;
-    if (n == 0) {
-        int dev = 0;
-        hipDeviceProp_t p;
-        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&p, dev) == hipSuccess) n = p.multiProcessorCount;
-        if (n <= 0) n = 256;
-    }
-    return n;
-}
-
 }  // namespace
 
 int pg_gemm_pp_launch(int dtype, GemmArgs g, int epi, int variant, hipStream_t s) {
@@ -895,8 +884,7 @@ int pg_gemm_pp_launch(int dtype, GemmArgs g, int epi, int variant, hipStream_t s
     if (g.ex.parts > 1 && epi != EPI_F32) { pg_set_error("gemm_pp: parts > 1 exists for EPI_F32 only (epi = %d)", epi); return PG_EINVAL; }
     if ((int64_t)g.part_tiles * g.ex.parts >= (1ll << 30)) { pg_set_error("gemm_pp: too many tiles"); return PG_EINVAL; }
     g.ntiles = g.part_tiles * g.ex.parts;
-    int cap = num_cus();
-    if (pg_gemm_block_cap() > 0 && pg_gemm_block_cap() < cap) cap = pg_gemm_block_cap();   // tuning: share the chip between streams
+    const int cap = pg_gemm_grid_cus();
     const int nblk = g.ntiles < cap ? g.ntiles : cap;
     if (dtype == PG_DTYPE_F16) return dispatch_pp<T_F16>(g, epi, variant, nblk, s);
     if (dtype == PG_DTYPE_BF16) return dispatch_pp<T_BF16>(g, epi, variant, nblk, s);

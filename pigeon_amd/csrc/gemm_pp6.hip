@@ -643,16 +643,6 @@ bool park16_enabled() {
 #endif
 }
 
-int cus6() {
-    static int n = 0;
-    if (n == 0) {
-        int dev = 0;
-        hipDeviceProp_t p;
-        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&p, dev) == hipSuccess) n = p.multiProcessorCount;
-    }
-    return n > 0 ? n : 256;
-}
-
 }  // namespace
 
 // true if this (epilogue, shape) has a 384 x 256 kernel
@@ -679,8 +669,7 @@ int pg_gemm_pp6_launch(int dtype, GemmArgs g, int epi, hipStream_t s) {
         if (rg == -1 || rg >= g.tilesN) g.gn = g.tilesN;
         else if (rg > 0 && g.tilesN % rg == 0) g.gn = rg;
     }
-    int cap = cus6();
-    if (pg_gemm_block_cap() > 0 && pg_gemm_block_cap() < cap) cap = pg_gemm_block_cap();   // tuning: share the chip between streams
+    const int cap = pg_gemm_grid_cus();
     const int nblk = g.ntiles < cap ? g.ntiles : cap;
     if ((epi == EPI_QKV_LN || epi == EPI_GELU_LN) && (!g.ex.colsum || !g.ex.rowstat)) { pg_set_error("gemm_pp6: LN epilogue needs colsum / rowstat"); return PG_EINVAL; }
     if (epi == EPI_RESID_STAT && (!g.ex.x16 || !g.ex.statpart || g.ex.ldx != g.ldc || !g.bias)) { pg_set_error("gemm_pp6: EPI_RESID_STAT needs bias, x16 / statpart and ldx == ldc"); return PG_EINVAL; }

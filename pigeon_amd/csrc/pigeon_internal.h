@@ -31,17 +31,19 @@ struct PgGemmExtra {
 
 void pg_set_error(const char* fmt, ...) __attribute__((format(printf, 1, 2)));
 int pg_check_launch(const char* what);          // hipGetLastError -> PG_EHIP + message
+// gemm_plan.hip: the GEMM knobs, the CU count and the planner of pg_gemm_launch
 int pg_default_gemm_variant();                   // env PIGEON_GEMM_VARIANT or the built-in default
-int pg_gemm_block_cap();                         // env PIGEON_GEMM_BLOCKS: cap on the persistent GEMMs' grid (0 = one block per CU)
-int pg_num_cus();                               // compute units of the current device (256 on MI355X)
-int pg_gemm_tail_min_n();                        // env PIGEON_GEMM_TAIL_MIN_N: ... or smallest N
-int pg_gemm_tail_min_k();                        // env PIGEON_GEMM_TAIL_MIN_K: smallest K for which the tail split is used
-int pg_gemm_tail_rows();                         // env PIGEON_GEMM_TAIL_ROWS / pg_tune_gemm_tail_rows: most rows handed to gemm_tail.hip (0 = never)
+int pg_gemm_grid_cus();                         // the persistent GEMMs' grid: compute units of the device, capped by env PIGEON_GEMM_BLOCKS
 int pg_gemm_raster_gn();                       // pg_tune_gemm_raster / env PIGEON_GEMM_RASTER_GN: N tiles per raster group of the 384 x 256 kernel (0 = default 4, -1 = all)
-bool pg_gemm_route_pp256();                     // the small-batch routing may also swap the 384 x 256 kernel for the 256 x 256 one (PIGEON_GEMM_MID=2: no)
-bool pg_gemm_mid_on();                          // pg_tune_gemm_mid / env PIGEON_GEMM_MID: small batches through gemm_mid.hip when the cost model says so
-unsigned long long pg_tune_epoch();             // bumped by every pg_tune_* call: captured hipGraphs of an older epoch are stale
-float pg_gemm_stagger_fraction();                // env PIGEON_GEMM_STAGGER / pg_tune_gemm_stagger: XCD start spread, fraction of a tile period
+unsigned long long pg_tune_epoch();             // bumped by every pg_tune_gemm_* call: captured hipGraphs of an older epoch are stale
+// the exact tier's form of one GEMM (vit.hip precise_gemm): 0 = gemm_mid.hip, S >= 1 = the 256 x 256 persistent kernel in S K-parts
+int pg_gemm_precise_route(int M, int N, int Ktot, bool resid, const int* cand, int ncand);
+
+// GEMM variants (env PIGEON_GEMM_VARIANT, the `variant` argument of pg_op_gemm16*): the numbers are ABI.  30..49 are the schedules
+// and rasters of the 256 x 256 persistent kernel (33 and 36 in the product library, the rest in the tools build).
+enum { PG_GEMM_V_ONE_TILE = 8, PG_GEMM_V_PP = 36, PG_GEMM_V_PP6 = 56, PG_GEMM_V_TAIL = 70, PG_GEMM_V_MID = 71 };
+// the kernels of a GEMM plan (pg_gemm_plan's `kernel` / `rest` codes)
+enum PgGemmKernel { PG_GK_NONE = -1, PG_GK_PP6 = 0, PG_GK_PP = 1, PG_GK_MID = 2, PG_GK_TAIL = 3, PG_GK_ONE_TILE = 4 };
 
 #define PG_HIP(call)                                                                          \
     do {                                                                                      \
@@ -52,7 +54,7 @@ float pg_gemm_stagger_fraction();                // env PIGEON_GEMM_STAGGER / pg
         }                                                                                     \
     } while (0)
 
-// gemm_bf16.hip
+// gemm_plan.hip: every GEMM; argument checks, the plan, at most two kernel launches
 int pg_gemm_launch(int dtype, const void* A, int64_t lda, const void* W, int64_t ldw, const float* bias, void* out, int64_t ldc,
                    int M, int N, int K, int epi, float qscale, int qcols, const float* aux, int variant,
                    hipStream_t s, const PgGemmExtra* extra = nullptr);

@@ -40,102 +40,9 @@ int pg_check_launch(const char* what) {
     if (e != hipSuccess) { pg_set_error("launch of %s failed: %s", what, hipGetErrorString(e)); return PG_EHIP; }
     return PG_OK;
 }
-int pg_default_gemm_variant() {
-    static int v = -1;
-    if (v < 0) {
-        const char* e = getenv("PIGEON_GEMM_VARIANT");
-        // 56: persistent ping-pong kernel with 384 x 256 tiles for the QKV / fc1 GEMMs (gemm_pp6.hip), 256 x 256 (variant 36:
-        // 8x4 super-tile raster, gemm_pp.hip) for everything else
-        v = e ? atoi(e) : 56;
-        if (v <= 0) v = 56;
-    }
-    return v;
-}
-
 #ifndef PG_DEFAULT_VIT_STREAMS
 #define PG_DEFAULT_VIT_STREAMS 1
 #endif
-#ifndef PG_DEFAULT_GEMM_STAGGER
-#define PG_DEFAULT_GEMM_STAGGER 0.0f
-#endif
-int pg_gemm_block_cap() {
-    static int v = -1;
-    if (v < 0) { const char* e = getenv("PIGEON_GEMM_BLOCKS"); v = e ? atoi(e) : 0; if (v < 0) v = 0; }
-    return v;
-}
-int pg_num_cus() {
-    static int n = 0;
-    if (n == 0) {
-        int dev = 0;
-        hipDeviceProp_t p;
-        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&p, dev) == hipSuccess) n = p.multiProcessorCount;
-        if (n <= 0) n = 256;
-    }
-    return n;
-}
-// Tail split of pg_gemm_launch (gemm_tail.hip).  ROWS: most rows handed to the small-tile kernel instead of giving them a (mostly
-// idle) last round of the persistent kernels; 768 = two 384-row panels.  The split is used only where it measured positive on the
-// 512-image step (profiles/r02/gemm_tail.txt): K >= 2048 (fc2: a 120 us round saved for a 43 us tail launch, +0.4 % end to end)
-// or N >= 4096 (fc1, +0.1 %); for out-projection and QKV the tail launch costs what the half-idle round did (-0.2 % with all four).
-#define PG_DEFAULT_GEMM_TAIL_ROWS 768
-#define PG_DEFAULT_GEMM_TAIL_MIN_K 2048
-#define PG_DEFAULT_GEMM_TAIL_MIN_N 4096
-static int g_tail_rows = -1, g_tail_min_k = -1, g_tail_min_n = -1;
-// every pg_tune_* call bumps the epoch: the knobs are baked into captured launches, so a hipGraph of an older epoch is re-captured
-static unsigned long long g_tune_epoch = 1;
-unsigned long long pg_tune_epoch() { return g_tune_epoch; }
-static int g_raster_gn = -2;
-int pg_gemm_raster_gn() {
-    if (g_raster_gn == -2) { const char* e = getenv("PIGEON_GEMM_RASTER_GN"); g_raster_gn = e ? atoi(e) : 0; if (g_raster_gn < -1) g_raster_gn = 0; }
-    return g_raster_gn;
-}
-extern "C" int pg_tune_gemm_raster(int gn) {
-    if (gn < -1 || gn > 64) { pg_set_error("tune_gemm_raster: gn must be -1 (all N tiles), 0 (default) or 1..64"); return PG_EINVAL; }
-    g_raster_gn = gn; ++g_tune_epoch;
-    return PG_OK;
-}
-static int env_int(const char* name, int dflt) {
-    const char* e = getenv(name);
-    const int v = e ? atoi(e) : dflt;
-    return v < 0 ? 0 : v;
-}
-int pg_gemm_tail_rows() { if (g_tail_rows < 0) g_tail_rows = env_int("PIGEON_GEMM_TAIL_ROWS", PG_DEFAULT_GEMM_TAIL_ROWS); return g_tail_rows; }
-int pg_gemm_tail_min_k() { if (g_tail_min_k < 0) g_tail_min_k = env_int("PIGEON_GEMM_TAIL_MIN_K", PG_DEFAULT_GEMM_TAIL_MIN_K); return g_tail_min_k; }
-int pg_gemm_tail_min_n() { if (g_tail_min_n < 0) g_tail_min_n = env_int("PIGEON_GEMM_TAIL_MIN_N", PG_DEFAULT_GEMM_TAIL_MIN_N); return g_tail_min_n; }
-extern "C" int pg_tune_gemm_tail_rows(int rows) {
-    if (rows < 0 || rows > (1 << 20)) { pg_set_error("tune_gemm_tail_rows: rows must be in [0, 2^20]"); return PG_EINVAL; }
-    g_tail_rows = rows; ++g_tune_epoch;
-    return PG_OK;
-}
-extern "C" int pg_tune_gemm_tail_shape(int min_k, int min_n) {
-    if (min_k < 0 || min_n < 0) { pg_set_error("tune_gemm_tail_shape: negative threshold"); return PG_EINVAL; }
-    g_tail_min_k = min_k; g_tail_min_n = min_n; ++g_tune_epoch;
-    return PG_OK;
-}
-static int g_gemm_mid = -1;
-bool pg_gemm_mid_on() {
-    if (g_gemm_mid < 0) { const char* e = getenv("PIGEON_GEMM_MID"); g_gemm_mid = (e && e[0] == '0') ? 0 : ((e && e[0] == '2') ? 2 : 1); }
-    return g_gemm_mid != 0;
-}
-bool pg_gemm_route_pp256() { return pg_gemm_mid_on() && g_gemm_mid != 2; }   // 2 (A/B arm): gemm_mid.hip is the only alternative
-extern "C" int pg_tune_gemm_mid(int on) {
-    g_gemm_mid = on == 2 ? 2 : (on ? 1 : 0); ++g_tune_epoch;
-    return PG_OK;
-}
-static float g_stagger = -1.f;
-float pg_gemm_stagger_fraction() {
-    if (g_stagger < 0.f) {
-        const char* e = getenv("PIGEON_GEMM_STAGGER");
-        g_stagger = e ? (float)atof(e) : PG_DEFAULT_GEMM_STAGGER;
-        if (!(g_stagger >= 0.f && g_stagger <= 4.f)) g_stagger = 0.f;
-    }
-    return g_stagger;
-}
-extern "C" int pg_tune_gemm_stagger(float fraction) {
-    if (!(fraction >= 0.f && fraction <= 4.f)) { pg_set_error("tune_gemm_stagger: fraction must be in [0, 4]"); return PG_EINVAL; }
-    g_stagger = fraction; ++g_tune_epoch;
-    return PG_OK;
-}
 
 extern "C" const char* pg_last_error(void) { return g_err; }
 extern "C" int pg_abi_version(void) { return PG_ABI_VERSION; }
@@ -718,7 +625,7 @@ extern "C" int pg_vit_forward(pg_vit* h, const void* pixels, int pix_dtype, int 
 // buffers, which sum_parts_kernel then adds in a fixed order.  The exact tier runs on the handful of panoramas a step finds
 // uncertain -- 4 to 16 images, 10 to 40 row panels: a K' = 12288 launch then puts 40 tiles of 192 K tiles each on 256 CUs (326 us per
 // layer for fc2 alone: latency, not work); 240 tiles of 32 K tiles fill the chip instead.  S is chosen per shape by a small cost
-// model (precise_parts).  (First tried as S concurrent launches on side streams: the launches did not overlap -- 4 images 15.9
+// model (gemm_plan.hip precise_parts).  (First tried as S concurrent launches on side streams: the launches did not overlap -- 4 images 15.9
 // against 14.3 ms, 52 images 112 against 76 ms, gpurun_out/r05/exact_small_batches_ksplit.txt -- hence the in-kernel form.)
 #define PG_PRECISE_CHUNK 128   // images per internal pass (98 KB of workspace per token row: 7.2 GB at 128); a longer batch is cut into EQUAL chunks
 // pg_tune_exact_products (round 6): how many of the three partial products hi.Wh | lo.Wh | hi.Wl the exact mode's weight GEMMs run.
@@ -744,68 +651,24 @@ extern "C" int pg_vit_precise_workspace_bytes(const pg_vit* h, int n_images, siz
     return PG_OK;
 }
 
-// How many K-parts for one GEMM of the exact mode: the S (out of `cand`) with the smallest modelled time on `ncu` CUs --
-//   rounds(S) x (K tiles per part x 1.7 us + epilogue) + the sum pass (S + 1 or S + 2 streams of M x N floats at ~4 TB/s).
-// A pure function of the shape: the same batch size always takes the same path (results differ between S only in fp32 summation
-// order, ~1e-7 relative, two orders below the exact tier's own floor).  Measured on MI355X (gpurun_out/r05/exact8_kernel_stats.csv,
-// 8 images): out-projection 107 -> 54 us, fc2 351 -> 158 us with S = 3 / 6; QKV and fc1 (216 / 288 tiles of 48 K tiles) gain nothing
-// from a split at that size and lose at larger ones, which the model reproduces.
-static int precise_parts(int M, int N, int Ktot, bool resid, const int* cand, int ncand, double* best_us_out = nullptr) {
-    const double ncu = (double)pg_num_cus();
-    const double tiles = (double)((M + 255) / 256) * (N / 256);
-    int best = 1; double best_us = 1e30;
-    for (int i = 0; i < ncand; ++i) {
-        const int S = cand[i];
-        if (Ktot % S || (Ktot / S) % 128) continue;
-        const double rounds = ceil(S * tiles / ncu);
-        const double epi = (S == 1 && resid) ? 25.0 : 12.0;
-        double us = rounds * ((Ktot / S / 64) * 1.7 + epi);
-        if (S > 1) us += 4.0 + (double)(S + (resid ? 2 : 1)) * M * N * 4.0 / 4.0e6;
-        if (us < best_us) { best_us = us; best = S; }
-    }
-    if (best_us_out) *best_us_out = best_us;
-    return best;
-}
-
 // One GEMM of the exact mode.  S = 1: the plain launch (EPI_F32 into dst / EPI_RESID onto dst).  S > 1: cut along K' into S parts
 // that run as ONE persistent launch (PgGemmExtra::parts: S x tilesM x tilesN tiles on the 256 CUs): part p multiplies columns
 // [p Kp, (p + 1) Kp) of the triple operands into the fp32 partial buffer p (the bias rides in part 0); then
 // dst = (resid ? dst : 0) + sum of the parts, in part order (sum_parts_kernel).
-// Which of the three forms a shape takes (a pure function of the shape): 0 = gemm_mid.hip, S >= 1 = the persistent kernel in S parts.
-#ifndef PG_EXACT_MID_US_KT
-#define PG_EXACT_MID_US_KT 0.6
-#endif
-static double precise_mid_us_kt() {     // microseconds per K tile of a gemm_mid round in the exact tier's routing (env PIGEON_EXACT_MID_US: A/B)
-    static double v = -1.0;
-    if (v < 0.0) { const char* e = getenv("PIGEON_EXACT_MID_US"); v = e ? atof(e) : PG_EXACT_MID_US_KT; if (!(v > 0.0)) v = PG_EXACT_MID_US_KT; }
-    return v;
-}
-static int precise_route(int M, int N, int Ktot, bool resid, const int* cand, int ncand) {
-    double parts_us = 0.0;
-    const int S = precise_parts(M, N, Ktot, resid, cand, ncand, &parts_us);
-    // Round 6: a handful of images (a settled-at-once exact pass: serving, certain_forward) -- the 128 x 128 one-tile-per-block kernel
-    // (gemm_mid.hip) keeps the whole K' in one chain like S = 1 and still fills the chip; same cost model as pg_gemm_launch
-    // (0.6 us per K tile of a round + epilogue).  Bit-identical to the S = 1 persistent launch.
-    if (pg_gemm_mid_on() && N % 128 == 0) {
-        const double rounds_m = ceil((double)((M + 127) / 128) * (N / 128) / (double)pg_num_cus());
-        const double mid_us = rounds_m * ((Ktot / 64) * precise_mid_us_kt() + (resid ? 6.0 : 5.0));
-        if (mid_us < parts_us) return 0;
-    }
-    return S;
-}
+// Which of the three forms a shape takes: pg_gemm_precise_route (gemm_plan.hip), 0 = gemm_mid.hip, S >= 1 = the persistent kernel in S parts.
 static int precise_gemm(pg_vit* h, const uint16_t* A3, int64_t lda, const uint16_t* W3, int64_t ldw, const float* bias, float* parts,
                         float* dst, bool resid, int M, int N, int Ktot, const int* cand, int ncand, hipStream_t s) {
     (void)h;
-    const int S = precise_route(M, N, Ktot, resid, cand, ncand);
+    const int S = pg_gemm_precise_route(M, N, Ktot, resid, cand, ncand);
     if (S == 0)
-        return pg_gemm_launch(PG_DTYPE_F16, A3, lda, W3, ldw, bias, dst, N, M, N, Ktot, resid ? EPI_RESID : EPI_F32, 1.f, 0, nullptr, 71, s);
+        return pg_gemm_launch(PG_DTYPE_F16, A3, lda, W3, ldw, bias, dst, N, M, N, Ktot, resid ? EPI_RESID : EPI_F32, 1.f, 0, nullptr, PG_GEMM_V_MID, s);
     if (S == 1)
-        return pg_gemm_launch(PG_DTYPE_F16, A3, lda, W3, ldw, bias, dst, N, M, N, Ktot, resid ? EPI_RESID : EPI_F32, 1.f, 0, nullptr, 36, s);
+        return pg_gemm_launch(PG_DTYPE_F16, A3, lda, W3, ldw, bias, dst, N, M, N, Ktot, resid ? EPI_RESID : EPI_F32, 1.f, 0, nullptr, PG_GEMM_V_PP, s);
     const int Kp = Ktot / S;
     const int64_t part_elems = (int64_t)M * N;
     PgGemmExtra ex;
     ex.parts = S; ex.a_part = Kp; ex.w_part = Kp; ex.c_part = part_elems;
-    RC(pg_gemm_launch(PG_DTYPE_F16, A3, lda, W3, ldw, bias, parts, N, M, N, Kp, EPI_F32, 1.f, 0, nullptr, 36, s, &ex));
+    RC(pg_gemm_launch(PG_DTYPE_F16, A3, lda, W3, ldw, bias, parts, N, M, N, Kp, EPI_F32, 1.f, 0, nullptr, PG_GEMM_V_PP, s, &ex));
     return pg_sum_parts_launch(parts, S, part_elems, dst, part_elems, resid ? 1 : 0, s);
 }
 
@@ -835,13 +698,13 @@ static int vit_precise_chunk(pg_vit* h, const void* pixels, int pix_dtype, int n
     float* O = (float*)G3;                                    // fp32 attention output, dead before G3 is written
     float* PP = (float*)((char*)G3 + align_up((size_t)M * 3 * F * 2, 256));     // K-split partial products of one GEMM
     const float eps = h->cfg.ln_eps;
-    const int dt = PG_DTYPE_F16, V = 36;                      // the 256 x 256 persistent kernel takes every epilogue used here
+    const int dt = PG_DTYPE_F16, V = PG_GEMM_V_PP;            // the 256 x 256 persistent kernel takes every epilogue used here
     static const int S3[2] = {1, 3}, S6[4] = {1, 2, 3, 6};    // K-part counts precise_parts may choose from (K' = 3072 / 12288)
     static const int S2[2] = {1, 2}, S4[3] = {1, 2, 4};       // ... with two products (K' = 2048 / 8192)
     const int np = g_exact_products;                          // partial products per weight GEMM (3; 2: pg_tune_exact_products)
     const int* c1 = np == 3 ? S3 : S2; const int* c2 = np == 3 ? S6 : S4; const int n2 = np == 3 ? 4 : 3;
     const bool fuse = exact_fusion_on();
-    const bool fuse_fc1 = fuse && precise_route((int)M, F, np * D, false, c1, 2) == 1;    // one persistent launch: the epilogue can finish the job
+    const bool fuse_fc1 = fuse && pg_gemm_precise_route((int)M, F, np * D, false, c1, 2) == 1;    // one persistent launch: the epilogue can finish the job
     RC(pg_x3_im2col_launch(pixels, pix_dtype, G3, n, s));
     RC(pg_gemm_launch(dt, G3, 3 * VIT_PATCH_KPAD, h->wpatch3, 3 * VIT_PATCH_KPAD, nullptr, X, D, n * VIT_PATCHES, D, np * VIT_PATCH_KPAD,
                       EPI_PATCH, 1.f, 0, h->pos, V, s));
@@ -1021,7 +884,7 @@ extern "C" int pg_op_gemm16_resid_stat(int dtype, const void* A, int64_t lda, co
                                        void* stream) {
     if (!A || !W || !X || !x16 || !statpart) { pg_set_error("op_gemm16_resid_stat: null argument"); return PG_EINVAL; }
     PgGemmExtra ex; ex.x16 = x16; ex.ldx = ldx; ex.statpart = statpart;
-    return pg_gemm_launch(dtype, A, lda, W, ldw, bias, X, ldc, M, N, K, EPI_RESID_STAT, 1.f, 0, nullptr, variant ? variant : 36,
+    return pg_gemm_launch(dtype, A, lda, W, ldw, bias, X, ldc, M, N, K, EPI_RESID_STAT, 1.f, 0, nullptr, variant ? variant : PG_GEMM_V_PP,
                           (hipStream_t)stream, &ex);
 }
 extern "C" int pg_op_gemm16_ln(int dtype, const void* A, int64_t lda, const void* W, int64_t ldw, const float* bias,
@@ -1030,7 +893,7 @@ extern "C" int pg_op_gemm16_ln(int dtype, const void* A, int64_t lda, const void
     if (!A || !W || !out || !colsum || !rowstat) { pg_set_error("op_gemm16_ln: null argument"); return PG_EINVAL; }
     if (epi != EPI_QKV_LN && epi != EPI_GELU_LN) { pg_set_error("op_gemm16_ln: epi must be 6 or 7"); return PG_EINVAL; }
     PgGemmExtra ex; ex.colsum = colsum; ex.rowstat = rowstat;
-    return pg_gemm_launch(dtype, A, lda, W, ldw, bias, out, ldc, M, N, K, epi, qscale, qcols, nullptr, variant ? variant : 36,
+    return pg_gemm_launch(dtype, A, lda, W, ldw, bias, out, ldc, M, N, K, epi, qscale, qcols, nullptr, variant ? variant : PG_GEMM_V_PP,
                           (hipStream_t)stream, &ex);
 }
 extern "C" int pg_op_layernorm(const float* x, const float* gamma, const float* beta, void* y, int out_dtype,
@@ -1061,7 +924,7 @@ extern "C" int pg_op_gemm16_parts(int dtype, const void* A, int64_t lda, const v
     if (S < 1 || S > 8) { pg_set_error("op_gemm16_parts: 1 <= S <= 8"); return PG_EINVAL; }
     PgGemmExtra ex;
     ex.parts = S; ex.a_part = Kp; ex.w_part = Kp; ex.c_part = (int64_t)M * N;
-    return pg_gemm_launch(dtype, A, lda, W, ldw, bias, parts, N, M, N, Kp, EPI_F32, 1.f, 0, nullptr, 36, (hipStream_t)stream, &ex);
+    return pg_gemm_launch(dtype, A, lda, W, ldw, bias, parts, N, M, N, Kp, EPI_F32, 1.f, 0, nullptr, PG_GEMM_V_PP, (hipStream_t)stream, &ex);
 }
 
 // exact-mode building blocks (precise.hip), exported for the parity tests

@@ -22,10 +22,10 @@ def test_header_symbols_exported(hip_lib):
         assert hasattr(hip_lib, s), f"{s} declared in pigeon_hip.h but not exported"
 
 
-def test_ctypes_signatures_cover_header(hip_lib):
+def test_ctypes_signatures_and_abi_version(hip_lib):
     from pigeon_amd import _lib
     assert sorted(_lib.SIGNATURES) == declared_symbols()
-    assert hip_lib.pg_abi_version() == 5
+    assert hip_lib.pg_abi_version() == 6
 
 
 def test_no_gpu_fails_loudly(hip_lib):

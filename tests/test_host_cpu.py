@@ -436,8 +436,8 @@ def test_evaluate_accepts_the_references_base_model_strings(tmp_path, monkeypatc
         ev.evaluate("none", None, False, False, base_model=cfg.CLIP_MODEL)
 
 
-def test_gemm_routing_model_against_the_measured_sweep():
-    """pg_gemm_route (host arithmetic, no launch): which of the three bit-identical GEMM kernels a launch of up to ~64 images takes.
+def test_gemm_plan_model_against_the_measured_sweep():
+    """pg_gemm_plan (host arithmetic, no launch): which of the three bit-identical GEMM kernels a launch of up to ~64 images takes.
     Checked against the sweeps the model was fitted to (profiles/r06/gemm_three_sweep.txt, gemm_three_sweep_producer.txt: the model's four GEMM shapes x 1 .. 64 images
     x 384 x 256 persistent / 256 x 256 persistent / gemm_mid.hip, microseconds on MI355X): the pick is never more than 10 % off the
     measured best of its cell (the 256 x 256 kernel must win by 10 % in the model to be taken -- in a forward the ties went the other
@@ -449,8 +449,8 @@ def test_gemm_routing_model_against_the_measured_sweep():
     L = _lib.load()
 
     def route(variant, epi, M, N, K):
-        k = C.c_int(-9)
-        assert L.pg_gemm_route(variant, epi, M, N, K, C.byref(k)) == 0
+        k, rows, rest = C.c_int(-9), C.c_int(-9), C.c_int(-9)
+        assert L.pg_gemm_plan(variant, epi, M, N, K, C.byref(k), C.byref(rows), C.byref(rest)) == 0
         return k.value
 
     shapes = {"qkv": (3072, 1024, _lib.EPI_QKV_LN), "out": (1024, 1024, _lib.EPI_RESID_STAT), "fc1": (4096, 1024, _lib.EPI_GELU_LN),
@@ -486,7 +486,7 @@ def test_gemm_routing_model_against_the_measured_sweep():
     assert picks[("out", 8)] == 2 and picks[("out", 12)] == 2          # (the 256 x 256 kernel until the producer wave made gemm_mid the faster one there)
     # the benchmark step (295 424 rows) is outside the routed range: the variant's own kernel (fc2 / QKV / fc1 384 x 256, out-projection 256 x 256)
     assert [route(56, shapes[s][2], 295424, shapes[s][0], shapes[s][1]) for s in ("qkv", "out", "fc1", "fc2")] == [0, 1, 0, 0]
-    assert route(36, _lib.EPI_F32, 16156, 1024, 3072) == 1 and route(8, _lib.EPI_QKV, 577, 3072, 1024) == -1
+    assert route(36, _lib.EPI_F32, 16156, 1024, 3072) == 1 and route(8, _lib.EPI_QKV, 577, 3072, 1024) == 4
     try:
         assert L.pg_tune_gemm_mid(0) == 0
         assert route(56, _lib.EPI_QKV_LN, 577, 3072, 1024) == 0 and route(56, _lib.EPI_RESID_STAT, 577, 1024, 1024) == 1
@@ -494,3 +494,35 @@ def test_gemm_routing_model_against_the_measured_sweep():
         assert route(56, _lib.EPI_QKV_LN, 16 * 577, 3072, 1024) == 0 and route(56, _lib.EPI_QKV_LN, 577, 3072, 1024) == 2
     finally:
         L.pg_tune_gemm_mid(1)
+
+
+def test_gemm_plan_pins_the_tail_split():
+    """pg_gemm_plan's row split of the benchmark step (512 images, 295 424 rows) and of configs[1]'s 256 images (147 712 rows), variant
+    56: fc2 and fc1 leave the 384 x 256 kernel the rows of whole rounds (294 912 / 147 456 on 256 CUs) and hand the rest to gemm_tail
+    (fc2) or gemm_mid (fc1); QKV and out-projection take no split.  With pg_tune_gemm_tail_rows(0) nothing is split."""
+    import ctypes as C
+    from pigeon_amd import _lib
+    L = _lib.load()
+
+    def plan(epi, M, N, K):
+        k, rows, rest = C.c_int(-9), C.c_int(-9), C.c_int(-9)
+        assert L.pg_gemm_plan(56, epi, M, N, K, C.byref(k), C.byref(rows), C.byref(rest)) == 0
+        return k.value, rows.value, rest.value
+
+    for M, cut in ((295424, 294912), (147712, 147456)):
+        assert plan(_lib.EPI_RESID_STAT, M, 1024, 4096) == (0, cut, 3)          # fc2: 384 x 256 + gemm_tail
+        assert plan(_lib.EPI_GELU_LN, M, 4096, 1024) == (0, cut, 2)             # fc1: 384 x 256 + gemm_mid
+        assert plan(_lib.EPI_QKV_LN, M, 3072, 1024) == (0, M, -1)               # QKV
+        assert plan(_lib.EPI_RESID_STAT, M, 1024, 1024) == (1, M, -1)           # out-projection: 256 x 256
+    try:
+        assert L.pg_tune_gemm_tail_rows(0) == 0
+        for M in (295424, 147712):
+            assert plan(_lib.EPI_RESID_STAT, M, 1024, 4096) == (0, M, -1)
+            assert plan(_lib.EPI_GELU_LN, M, 4096, 1024) == (0, M, -1)
+    finally:
+        L.pg_tune_gemm_tail_rows(768)
+    # what the launch refuses, the plan refuses
+    k, rows, rest = C.c_int(), C.c_int(), C.c_int()
+    assert L.pg_gemm_plan(64, _lib.EPI_QKV, 577, 3072, 1024, C.byref(k), C.byref(rows), C.byref(rest)) == -1     # PG_EINVAL
+    assert L.pg_gemm_plan(8, _lib.EPI_RESID_STAT, 577, 1024, 1024, C.byref(k), C.byref(rows), C.byref(rest)) == -1     # PG_EINVAL
+    assert L.pg_gemm_plan(70, _lib.EPI_PATCH, 577, 1024, 640, C.byref(k), C.byref(rows), C.byref(rest)) == -1     # PG_EINVAL
