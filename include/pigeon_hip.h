@@ -156,7 +156,7 @@ int pg_tune_gemm_mid(int on);
 /* What pg_op_gemm16* / the encoder would launch for this shape under the current knobs (variant 0 = the default): *kernel takes rows
  * [0, *rows_main) -- 0 the 384 x 256 persistent kernel, 1 the 256 x 256 one, 2 csrc/gemm_mid.hip, 3 csrc/gemm_tail.hip, 4 the
  * one-tile-per-block kernel of csrc/gemm_bf16.hip -- and *rest the remaining rows: -1 none, 2 gemm_mid, 3 gemm_tail.  PG_EINVAL where
- * the GEMM launch refuses the variant / shape / epilogue (a persistent schedule the build lacks is refused by the launch only).
+ * the GEMM launch refuses the variant / shape / epilogue.
  * Host arithmetic only: no launch, no device work (tests/test_host_cpu.py checks the picks against profiles/r06/gemm_three_sweep.txt). */
 int pg_gemm_plan(int variant, int epi, int M, int N, int K, int* kernel, int* rows_main, int* rest);
 /* Exact mode's attention (also env PIGEON_EXACT_ATTN=f32): 0 = split-fp16 operands on v_mfma_f32_32x32x16_f16 (default, round 5),

@@ -39,13 +39,13 @@ def _stale(target: str, deps) -> bool:
 
 def build(force: bool = False, verbose: bool = True, dev: bool = False) -> str:
     """dev=False: the product library libpigeon_hip.so -- production kernels only.
-    dev=True:  libpigeon_hip_dev.so, compiled with -DPIGEON_ABLATIONS: additionally the older schedules and tilings, A/B arms
-               and the timing-only ablation kernels (which compute WRONG results by construction) that tools/ selects through
-               PIGEON_GEMM_VARIANT / PIGEON_ATTN_VARIANT; load it with PIGEON_HIP_LIB=pigeon_amd/libpigeon_hip_dev.so."""
+    dev=True:  libpigeon_hip_dev.so, compiled with -DPIGEON_PROBES: the same kernels plus the time-stamp and stall probes of the
+               persistent GEMMs (PG_TS, pg_dbg_timestamps, pg_dbg_*_read) that tools/epi_timeline.py and tools/stall_probe.py read;
+               load it with PIGEON_HIP_LIB=pigeon_amd/libpigeon_hip_dev.so."""
     global OBJ, LIB
     obj_dir = os.path.join(CSRC, "build_dev" if dev else "build")
     lib = os.path.join(HERE, "libpigeon_hip_dev.so" if dev else "libpigeon_hip.so")
-    flags = FLAGS + (["-DPIGEON_ABLATIONS"] if dev else [])
+    flags = FLAGS + (["-DPIGEON_PROBES"] if dev else [])
     return _build(obj_dir, lib, flags, force, verbose, SOURCES)
 
 
@@ -85,8 +85,8 @@ def _build(OBJ: str, LIB: str, FLAGS, force: bool, verbose: bool, SOURCES) -> st
 
 
 def build_variant(name: str, defines, verbose: bool = True) -> str:
-    """A/B arm of the PRODUCT library with extra -D defines (kernel knobs that are compile-time constants, e.g. -DPG_P6_EARLY=8):
-    libpigeon_hip_<name>.so; select it with PIGEON_HIP_LIB.  `python -m pigeon_amd.build --variant e8 -DPG_P6_EARLY=8`."""
+    """A/B arm of the PRODUCT library with extra -D defines (kernel knobs that are compile-time constants, e.g. -DPG_MID_STAGES=2):
+    libpigeon_hip_<name>.so; select it with PIGEON_HIP_LIB.  `python -m pigeon_amd.build --variant s2 -DPG_MID_STAGES=2`."""
     return _build(os.path.join(CSRC, f"build_{name}"), os.path.join(HERE, f"libpigeon_hip_{name}.so"), FLAGS + list(defines), False,
                   verbose, SOURCES)
 

@@ -21,9 +21,6 @@
 //   * 577 = 9*64 + 1: nine full tiles through the MFMAs, key 576 as a single-key VALU step at the end.
 #include "attention_common.h"
 
-#include <cstdlib>
-#include <type_traits>
-
 //
 // Why: at the 1400 W package cap the 16x16x32 form moves half as many accumulator registers per flop and sustains 2.06-2.09
 // PFLOP/s where 32x32x16 sustains 1.72-1.74 (tools/mfma_issue.hip, profiles/r02/mfma_issue.txt) -- the persistent GEMMs gained
@@ -40,20 +37,21 @@
 //   A lane therefore holds NQB queries (one per 16-query block), 16 keys of each per tile; the 64 keys of a query are spread
 //   over the 4 lanes r16 + 16 g4.  The row sum comes out of the matrix pipe: a fifth 16-row "d" block whose V^T rows are (1, 0, ..., 0)
 //   -- two more MFMAs per tile and query block instead of 16 v_dot2c per tile, which share the matrix pipe and cost more than the
-//   MFMAs do (-2 %, profiles/r03/attention_v7_v8_ab.txt); with LSUM = false it is a per-lane partial (combined once at the end); the reference maximum (first
-//   tile / careful path) needs two lane exchanges (xor 16, xor 32).
+//   MFMAs do (-2 %, profiles/r03/attention_v7_v8_ab.txt); the reference maximum (first tile / careful path) needs two lane
+//   exchanges (xor 16, xor 32).
 // LDS: K tile as before (row = key, 16-byte chunk c at c ^ ((key >> 1) & 7)).  V tile row-major with the 32-byte column block
 //   db stored at db ^ ((key >> 1) & 3): one transposing read pass (lanes 0-31) then covers 8 key rows x 32 B = all 64 banks once.
-// NQB x WAVES = 2 x 4 (32 queries per wave, 3 waves per SIMD, as v5) or 4 x 2 (64 queries per wave, 2 waves per SIMD: each K / V
-//   fragment read from LDS feeds twice the MFMAs).  Block = 128 queries either way, 5 blocks per (image, head) on one XCD.
+// Block = 4 waves x 32 queries (ATT8_NQB 16-query blocks per wave, 3 waves per SIMD) = 128 queries, 5 blocks per (image, head) on
+//   one XCD.  64 queries per wave measured 1 % slower, 192-query blocks slower still (profiles/r04/attention_192_query_blocks_ab.txt);
+//   both were removed (see git history).
 // ================================================================================================================
-// LSUM: true = the row sums come out of the matrix pipe (an extra "ones" row block in the PV product, attention8_kernel) and this
-// function only exponentiates and packs; false = v_dot2c on the packed P (16 per tile and wave; v_dot2c shares the matrix pipe).
-template <typename T, int NQB, bool LSUM = false>
-__device__ __forceinline__ void att8_exp_pack(const f32x4 (&S)[4][NQB], float (&l)[NQB], typename T::v8 (&pf)[NQB][2]) {
+constexpr int ATT8_NQB = 2, ATT8_WAVES = 4, ATT8_WPS = 3;
+
+// exponentiate the tile's scores and pack them into the P operand of the PV MFMAs
+template <typename T, int NQB>
+__device__ __forceinline__ void att8_exp_pack(const f32x4 (&S)[4][NQB], typename T::v8 (&pf)[NQB][2]) {
 #pragma unroll
     for (int qb = 0; qb < NQB; ++qb) {
-        float l0 = l[qb], l1 = 0.f;
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
             u32x4 pw;
@@ -63,21 +61,16 @@ __device__ __forceinline__ void att8_exp_pack(const f32x4 (&S)[4][NQB], float (&
                 for (int w = 0; w < 2; ++w) {
                     const f32x4& sv = S[2 * j + h][qb];
                     pw[2 * h + w] = T::pack2(__builtin_amdgcn_exp2f(sv[2 * w]), __builtin_amdgcn_exp2f(sv[2 * w + 1]));
-                    if constexpr (!LSUM) {
-                        if (w) l1 = T::dot2(pw[2 * h + w], AttOnes<T>::v, l1);
-                        else l0 = T::dot2(pw[2 * h + w], AttOnes<T>::v, l0);
-                    }
                 }
             pf[qb][j] = __builtin_bit_cast(typename T::v8, pw);
         }
-        if constexpr (!LSUM) l[qb] = l0 + l1;
     }
 }
 
 // careful softmax step: per-query maximum of the tile (relative to the reference, the scores arrive as s - m), lazy rescale
-template <typename T, int NQB, bool LSUM = false>
-__device__ __forceinline__ void att8_softmax(f32x4 (&S)[4][NQB], f32x4 (&O)[4][NQB], f32x4 (&negm)[NQB], float (&l)[NQB],
-                                             typename T::v8 (&pf)[NQB][2], bool first, f32x4 (&L)[NQB]) {
+template <typename T, int NQB>
+__device__ __forceinline__ void att8_softmax(f32x4 (&S)[4][NQB], f32x4 (&O)[4][NQB], f32x4 (&negm)[NQB], typename T::v8 (&pf)[NQB][2],
+                                             bool first, f32x4 (&L)[NQB]) {
     float tmax[NQB];
     bool over = false;
 #pragma unroll
@@ -106,11 +99,10 @@ __device__ __forceinline__ void att8_softmax(f32x4 (&S)[4][NQB], f32x4 (&O)[4][N
             for (int kb = 0; kb < 4; ++kb) S[kb][qb] -= delta;
 #pragma unroll
             for (int db = 0; db < 4; ++db) O[db][qb] *= alpha;
-            if constexpr (LSUM) L[qb] *= alpha;
-            else l[qb] *= alpha;
+            L[qb] *= alpha;
         }
     }
-    att8_exp_pack<T, NQB, LSUM>(S, l, pf);
+    att8_exp_pack<T, NQB>(S, pf);
 }
 
 // Everything that is not valid HOST code lives in __device__ functions, not in the kernel body or its lambdas: those are also
@@ -145,17 +137,11 @@ __device__ __forceinline__ void att8_wait_v(u32x4 (&vf)[4][2]) {
                  :: "memory");
 }
 
-// QB = NQB * WAVES * 16 queries per block:
-//   128 (4 waves x 32)  5 blocks per (image, head) cover 640 query slots (63 idle in the last block), 5 K/V streams per head;
-//   192 (6 waves x 32)  round 4: 577 = 3 x 192 + 1 -- 3 blocks cover queries 0..575 with no idle slot and 3 K/V streams per head;
-//                       token 576's query is left to attention_last_query_kernel below.  Same 32 queries per wave, same registers
-//                       (3 waves per SIMD: two 6-wave blocks per CU where three 4-wave blocks ran); waves 0..3 issue the tile DMAs.
-template <typename T, int NQB, int WAVES, int WPS, bool LSUM = false>
-__global__ __launch_bounds__(WAVES * 64, WPS) void attention8_kernel(const uint16_t* __restrict__ qkv, uint16_t* __restrict__ out) {
+template <typename T>
+__global__ __launch_bounds__(ATT8_WAVES * 64, ATT8_WPS) void attention8_kernel(const uint16_t* __restrict__ qkv, uint16_t* __restrict__ out) {
+    constexpr int NQB = ATT8_NQB, WAVES = ATT8_WAVES;
     constexpr int QB = NQB * WAVES * 16;
-    static_assert(QB == 128 || QB == 192, "a block covers 128 or 192 queries");
-    constexpr int NQBLK = QB == 192 ? 3 : ATT_NQB;
-    constexpr int DW = WAVES < 4 ? WAVES : 4;               // waves that stage the K / V tiles
+    static_assert(QB * ATT_NQB >= VIT_TOKENS, "the blocks of an (image, head) cover every query");
     static_assert(VIT_TOKENS == 9 * ATT_KT + 1, "key tail assumes 577 tokens");
     __shared__ __attribute__((aligned(16))) char smem[4 * K_TILE_BYTES];              // K0 K1 V0 V1, 8 KB each
     char* ks0 = smem;
@@ -165,13 +151,12 @@ __global__ __launch_bounds__(WAVES * 64, WPS) void attention8_kernel(const uint1
     const int r16 = lane & 15, g4 = lane >> 4;
     const int bid = blockIdx.x;
     const int xcd = bid & 7, slot = bid >> 3;
-    const int qblk = slot % NQBLK;
-    const int pair = (slot / NQBLK) * 8 + xcd;
+    const int qblk = slot % ATT_NQB;
+    const int pair = (slot / ATT_NQB) * 8 + xcd;
     const int img = pair >> 4, head = pair & 15;
     const int64_t base = (int64_t)img * VIT_TOKENS;
     const int q_first = qblk * QB + wave * (NQB * 16);       // wave-uniform
     const bool wave_active = q_first < VIT_TOKENS;
-    constexpr int Q_END = QB == 192 ? VIT_TOKENS - 1 : VIT_TOKENS;   // 192-query blocks stop at query 575
 
     typename T::v8 qf[NQB][2];
 #pragma unroll
@@ -183,14 +168,12 @@ __global__ __launch_bounds__(WAVES * 64, WPS) void attention8_kernel(const uint1
             qf[qb][ks] = *(const typename T::v8*)(qkv + (base + qr) * QKV_LD + head * 64 + ks * 32 + g4 * 8);
     }
     f32x4 O[4][NQB], negm[NQB];
-    f32x4 L[NQB];                                            // LSUM: row sums as a fifth "d" block whose V^T rows are (1, 0, 0, ...): l = L[qb][0] in lanes g4 == 0
-    float l[NQB];
+    f32x4 L[NQB];                                            // row sums as a fifth "d" block whose V^T rows are (1, 0, 0, ...): L[qb][0] in lanes g4 == 0
     // A fragment of that block: row m = 0 is all ones (lanes r16 == 0 hold eight 1.0), rows 1..15 zero
     const u32x4 ones_rows = r16 == 0 ? u32x4{AttOnes<T>::v, AttOnes<T>::v, AttOnes<T>::v, AttOnes<T>::v} : u32x4{0u, 0u, 0u, 0u};
 #pragma unroll
     for (int qb = 0; qb < NQB; ++qb) {
         negm[qb] = f32x4{0.f, 0.f, 0.f, 0.f};
-        l[qb] = 0.f;
         L[qb] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int db = 0; db < 4; ++db) O[db][qb] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -211,28 +194,28 @@ __global__ __launch_bounds__(WAVES * 64, WPS) void attention8_kernel(const uint1
         const_cast<uint16_t*>(qkv + base * QKV_LD + 1024 + head * 64), (short)0, (int)(VIT_TOKENS * QKV_LD * 2), 0x00020000);
     __amdgpu_buffer_rsrc_t rv = __builtin_amdgcn_make_buffer_rsrc(
         const_cast<uint16_t*>(qkv + base * QKV_LD + 2048 + head * 64), (short)0, (int)(VIT_TOKENS * QKV_LD * 2), 0x00020000);
-    constexpr int NDMA = 8 / DW;                             // 8-key groups of a 64-key tile a staging wave moves, per operand
-    const bool stager = wave < DW;
+    constexpr int NDMA = 8 / WAVES;                          // 8-key groups of a 64-key tile a wave moves, per operand
+    const bool stager = wave < WAVES;                        // always true; without the test hipcc allocates registers differently
     int dvo_k[NDMA], dvo_v[NDMA];
 #pragma unroll
     for (int i = 0; i < NDMA; ++i) {
-        const int row = ((wave & (DW - 1)) + DW * i) * 8 + (lane >> 3);
+        const int row = ((wave & (WAVES - 1)) + WAVES * i) * 8 + (lane >> 3);
         dvo_k[i] = row * (QKV_LD * 2) + (((lane & 7) ^ ((row >> 1) & 7)) << 4);
         dvo_v[i] = row * (QKV_LD * 2) + (((lane & 7) ^ (((row >> 1) & 3) << 1)) << 4);
     }
     constexpr int NFULL = 9;
 
     if (stager) {
-        att8_dma(rk, ks0, wave, dvo_k, NDMA, DW, 0);
-        att8_dma(rv, vs0, wave, dvo_v, NDMA, DW, 0);
+        att8_dma(rk, ks0, wave, dvo_k, NDMA, WAVES, 0);
+        att8_dma(rv, vs0, wave, dvo_v, NDMA, WAVES, 0);
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
     for (int t = 0; t < NFULL; ++t) {
         const int cur = t & 1;
         if (t + 1 < NFULL && stager) {                        // both tiles of step t+1 land under this tile's math
-            att8_dma(rk, ks0 + (cur ^ 1) * K_TILE_BYTES, wave, dvo_k, NDMA, DW, t + 1);
-            att8_dma(rv, vs0 + (cur ^ 1) * K_TILE_BYTES, wave, dvo_v, NDMA, DW, t + 1);
+            att8_dma(rk, ks0 + (cur ^ 1) * K_TILE_BYTES, wave, dvo_k, NDMA, WAVES, t + 1);
+            att8_dma(rv, vs0 + (cur ^ 1) * K_TILE_BYTES, wave, dvo_v, NDMA, WAVES, t + 1);
         }
         const char* ks = ks0 + cur * K_TILE_BYTES;
         const char* vs = vs0 + cur * K_TILE_BYTES;
@@ -257,7 +240,7 @@ __global__ __launch_bounds__(WAVES * 64, WPS) void attention8_kernel(const uint1
             // the 16 transposing V reads, right behind the last QK^T MFMA (inline asm: see att5_load_v)
             u32x4 vf[4][2];
             att8_load_v(vf, vs, vb);
-            att8_softmax<T, NQB, LSUM>(S, O, negm, l, pf, t == 0, L);
+            att8_softmax<T, NQB>(S, O, negm, pf, t == 0, L);
             att8_wait_v(vf);
 #pragma unroll
             for (int j = 0; j < 2; ++j)
@@ -266,13 +249,11 @@ __global__ __launch_bounds__(WAVES * 64, WPS) void attention8_kernel(const uint1
 #pragma unroll
                     for (int qb = 0; qb < NQB; ++qb)
                         O[db][qb] = T::mfma16(__builtin_bit_cast(typename T::v8, vf[db][j]), pf[qb][j], O[db][qb]);
-            if constexpr (LSUM) {
 #pragma unroll
-                for (int j = 0; j < 2; ++j)
+            for (int j = 0; j < 2; ++j)
 #pragma unroll
-                    for (int qb = 0; qb < NQB; ++qb)
-                        L[qb] = T::mfma16(__builtin_bit_cast(typename T::v8, ones_rows), pf[qb][j], L[qb]);
-            }
+                for (int qb = 0; qb < NQB; ++qb)
+                    L[qb] = T::mfma16(__builtin_bit_cast(typename T::v8, ones_rows), pf[qb][j], L[qb]);
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // this wave's DMAs of step t+1 have landed
         __syncthreads();
@@ -300,12 +281,12 @@ __global__ __launch_bounds__(WAVES * 64, WPS) void attention8_kernel(const uint1
         }
         sp += __shfl_xor(sp, 16, 64);
         const float sc = sp + __shfl_xor(sp, 32, 64);
-        if constexpr (LSUM) l[qb] = L[qb][0];                // lanes g4 == 0: the row sum; the others: 0
         const float m = -negm[qb][0];
         const float m_new = fmaxf(m, sc);
         const float alpha = __builtin_amdgcn_exp2f(m - m_new);
         const float pk = __builtin_amdgcn_exp2f(sc - m_new);
-        l[qb] = l[qb] * alpha + (g4 == 0 ? pk : 0.f);        // the 4 lanes of a query are summed below: count the key once
+        // lanes g4 == 0 hold the row sum, the others 0; the 4 lanes of a query are summed below: count the key once
+        const float l = L[qb][0] * alpha + (g4 == 0 ? pk : 0.f);
 #pragma unroll
         for (int db = 0; db < 4; ++db)
 #pragma unroll
@@ -313,11 +294,11 @@ __global__ __launch_bounds__(WAVES * 64, WPS) void attention8_kernel(const uint1
                 const uint16_t hb = (uint16_t)(vv[db][e >> 1] >> (16 * (e & 1)));
                 O[db][qb][e] = fmaf(pk, T::val(hb), O[db][qb][e] * alpha);
             }
-        float lt = l[qb] + __shfl_xor(l[qb], 16, 64);
+        float lt = l + __shfl_xor(l, 16, 64);
         lt += __shfl_xor(lt, 32, 64);
         const float inv = 1.0f / lt;
         const int qrow = q_first + 16 * qb + r16;
-        if (qrow < Q_END) {
+        if (qrow < VIT_TOKENS) {
             uint16_t* orow = out + (base + qrow) * VIT_HIDDEN + head * 64;
 #pragma unroll
             for (int db = 0; db < 4; ++db) {
@@ -331,141 +312,12 @@ __global__ __launch_bounds__(WAVES * 64, WPS) void attention8_kernel(const uint1
 }
 
 
-#ifdef PIGEON_ABLATIONS
-// ---- token 576's query of every (image, head), for the 192-query blocking (tools build: the A/B arms 22 / 23 below): one wave per pair, VALU.  s_k = q . k over the 577 keys
-// (8 lanes share a key: 16-byte chunks of its row, shuffle-reduced), softmax in base 2 over LDS-resident scores (fp32 throughout:
-// P is not rounded to 16 bits here), O = sum_k p_k v_k with the same 8-keys-per-pass walk.  ~150 KB of K/V per wave from L2:
-// the main kernel has just streamed the same rows.
-template <typename T>
-__global__ __launch_bounds__(64) void attention_last_query_kernel(const uint16_t* __restrict__ qkv, uint16_t* __restrict__ out) {
-    __shared__ float sc[VIT_TOKENS + 7];
-    const int pair = blockIdx.x, img = pair >> 4, head = pair & 15, lane = threadIdx.x;
-    const int sub = lane >> 3, ch = lane & 7;
-    const int64_t base = (int64_t)img * VIT_TOKENS;
-    const uint16_t* qrow = qkv + (base + VIT_TOKENS - 1) * QKV_LD + head * 64 + ch * 8;
-    const u32x4 qq = *(const u32x4*)qrow;
-    float q[8];
-#pragma unroll
-    for (int w = 0; w < 4; ++w) { q[2 * w] = T::val((uint16_t)(qq[w] & 0xffffu)); q[2 * w + 1] = T::val((uint16_t)(qq[w] >> 16)); }
-    const uint16_t* kbase = qkv + base * QKV_LD + 1024 + head * 64 + ch * 8;
-    // 32 keys per pass (4 independent 16-byte loads per lane in flight), 8 lanes per key
-    for (int k0 = 0; k0 < VIT_TOKENS; k0 += 32) {
-        u32x4 kk[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const int key = k0 + 8 * u + sub;
-            kk[u] = key < VIT_TOKENS ? *(const u32x4*)(kbase + (int64_t)key * QKV_LD) : u32x4{0u, 0u, 0u, 0u};
-        }
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const int key = k0 + 8 * u + sub;
-            float p = 0.f;
-#pragma unroll
-            for (int w = 0; w < 4; ++w) {
-                p = fmaf(q[2 * w], T::val((uint16_t)(kk[u][w] & 0xffffu)), p);
-                p = fmaf(q[2 * w + 1], T::val((uint16_t)(kk[u][w] >> 16)), p);
-            }
-            p += __shfl_xor(p, 1, 64); p += __shfl_xor(p, 2, 64); p += __shfl_xor(p, 4, 64);
-            if (ch == 0 && key < VIT_TOKENS) sc[key] = p;
-        }
-    }
-    __syncthreads();
-    float m = -INFINITY;
-    for (int k = lane; k < VIT_TOKENS; k += 64) m = fmaxf(m, sc[k]);
-    m = wave_max(m);
-    float l = 0.f;
-    for (int k = lane; k < VIT_TOKENS; k += 64) { const float e = __builtin_amdgcn_exp2f(sc[k] - m); sc[k] = e; l += e; }
-    l = wave_sum(l);
-    __syncthreads();
-    float o[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) o[e] = 0.f;
-    const uint16_t* vbase = kbase + 1024;
-    for (int k0 = 0; k0 < VIT_TOKENS; k0 += 32) {
-        u32x4 vv[4];
-        float pp[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const int key = k0 + 8 * u + sub;
-            const bool ok = key < VIT_TOKENS;
-            vv[u] = ok ? *(const u32x4*)(vbase + (int64_t)key * QKV_LD) : u32x4{0u, 0u, 0u, 0u};
-            pp[u] = ok ? sc[key] : 0.f;
-        }
-#pragma unroll
-        for (int u = 0; u < 4; ++u)
-#pragma unroll
-            for (int w = 0; w < 4; ++w) {
-                o[2 * w] = fmaf(pp[u], T::val((uint16_t)(vv[u][w] & 0xffffu)), o[2 * w]);
-                o[2 * w + 1] = fmaf(pp[u], T::val((uint16_t)(vv[u][w] >> 16)), o[2 * w + 1]);
-            }
-    }
-    const float inv = 1.0f / l;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-        float v = o[e];
-        v += __shfl_xor(v, 8, 64); v += __shfl_xor(v, 16, 64); v += __shfl_xor(v, 32, 64);
-        o[e] = v * inv;
-    }
-    if (sub == 0) {
-        u32x4 pk;
-#pragma unroll
-        for (int w = 0; w < 4; ++w) pk[w] = pack16x2<T>(o[2 * w], o[2 * w + 1]);
-        *(u32x4*)(out + (base + VIT_TOKENS - 1) * VIT_HIDDEN + head * 64 + ch * 8) = pk;
-    }
-}
-
-#endif
-
-#ifndef PG_DEFAULT_ATTN_VARIANT
-#define PG_DEFAULT_ATTN_VARIANT 21
-#endif
-static int attention_variant() {
-    static int v = -1;
-    if (v < 0) {
-        const char* e = getenv("PIGEON_ATTN_VARIANT");
-        v = e ? atoi(e) : PG_DEFAULT_ATTN_VARIANT;
-        if (v < 1 || v > 23) v = PG_DEFAULT_ATTN_VARIANT;
-    }
-    return v;
-}
-
-template <typename KF, typename KB>
-static int att_launch3(int dtype, KF kf, KB kb, dim3 grid, int threads, const void* qkv, void* out, hipStream_t s) {
-    if (dtype == PG_DTYPE_F16) hipLaunchKernelGGL(kf, grid, dim3(threads), 0, s, (const uint16_t*)qkv, (uint16_t*)out);
-    else hipLaunchKernelGGL(kb, grid, dim3(threads), 0, s, (const uint16_t*)qkv, (uint16_t*)out);
-    return pg_check_launch("attention");
-}
-
-// Variants (env PIGEON_ATTN_VARIANT): 21 (default, the only one in the product library) = attention8_kernel, 32 queries per wave, row
-// sums out of the matrix pipe.  Tools build only: 20 = the same with v_dot2c row sums, 19 = 64 queries per wave (A/B arms of this
-// kernel).
 int pg_attention_launch(int dtype, const void* qkv, void* out, int n_images, hipStream_t s) {
     if (n_images <= 0) return PG_OK;
     if (dtype != PG_DTYPE_F16 && dtype != PG_DTYPE_BF16) { pg_set_error("attention: dtype must be PG_DTYPE_F16 or PG_DTYPE_BF16"); return PG_EINVAL; }
     const int pairs = n_images * VIT_HEADS;                  // always a multiple of 8
-    const dim3 grid(pairs * ATT_NQB);
-    const int variant = attention_variant();
-#ifdef PIGEON_ABLATIONS
-    // Round 4 A/B arms (tools build; profiles/r04/attention_192_query_blocks_ab.txt): 192-query blocks (577 = 3 x 192 + 1) + the last
-    // query as a micro-kernel.  22 = 6 waves x 32 queries: 1.46 vs 1.04 ms -- at 156 VGPRs (3 waves per SIMD) a CU places ONE 6-wave
-    // block (2,2,1,1 waves per SIMD; a second one would need 4 on SIMD 0), where three 4-wave blocks ran.  23 = 4 waves x 48 queries
-    // (212 VGPRs, 2 waves per SIMD): main kernel 0.97 ms (-6 %), but the last query alone streams every K / V row once more --
-    // 1.2 GB through L2, 0.24 ms as a kernel of its own: 1.21 ms in total.  It would have to ride in a block that already stages K / V.
-    if (variant == 22 || variant == 23) {                    // 192-query blocks + the last query's micro-kernel
-        const int rc = variant == 22
-            ? att_launch3(dtype, attention8_kernel<T_F16, 2, 6, 3, true>, attention8_kernel<T_BF16, 2, 6, 3, true>, dim3(pairs * 3), 384, qkv, out, s)
-            : att_launch3(dtype, attention8_kernel<T_F16, 3, 4, 2, true>, attention8_kernel<T_BF16, 3, 4, 2, true>, dim3(pairs * 3), 256, qkv, out, s);
-        if (rc != PG_OK) return rc;
-        if (dtype == PG_DTYPE_F16) hipLaunchKernelGGL(attention_last_query_kernel<T_F16>, dim3(pairs), dim3(64), 0, s, (const uint16_t*)qkv, (uint16_t*)out);
-        else hipLaunchKernelGGL(attention_last_query_kernel<T_BF16>, dim3(pairs), dim3(64), 0, s, (const uint16_t*)qkv, (uint16_t*)out);
-        return pg_check_launch("attention (last query)");
-    }
-    if (variant == 19) return att_launch3(dtype, attention8_kernel<T_F16, 4, 2, 2>, attention8_kernel<T_BF16, 4, 2, 2>, grid, 128, qkv, out, s);
-    if (variant == 20) return att_launch3(dtype, attention8_kernel<T_F16, 2, 4, 3, false>, attention8_kernel<T_BF16, 2, 4, 3, false>, grid, 256, qkv, out, s);
-#endif
-    if (variant != 21) {
-        pg_set_error("attention: PIGEON_ATTN_VARIANT=%d is not part of this build (product: 21; others need -DPIGEON_ABLATIONS)", variant);
-        return PG_EINVAL;
-    }
-    return att_launch3(dtype, attention8_kernel<T_F16, 2, 4, 3, true>, attention8_kernel<T_BF16, 2, 4, 3, true>, grid, 256, qkv, out, s);
+    const dim3 grid(pairs * ATT_NQB), block(ATT8_WAVES * 64);
+    if (dtype == PG_DTYPE_F16) hipLaunchKernelGGL(attention8_kernel<T_F16>, grid, block, 0, s, (const uint16_t*)qkv, (uint16_t*)out);
+    else hipLaunchKernelGGL(attention8_kernel<T_BF16>, grid, block, 0, s, (const uint16_t*)qkv, (uint16_t*)out);
+    return pg_check_launch("attention");
 }

@@ -1,5 +1,4 @@
-// attention_common.h -- geometry constants and the two device helpers shared by the product attention kernel (attention.hip, v8)
-// and the superseded generations kept for A/B work in the tools build (tools/csrc/attention_old.hip).
+// attention_common.h -- geometry constants and the two device helpers of the attention kernel (attention.hip, v8).
 #pragma once
 #include "common.h"
 #include "pigeon_internal.h"

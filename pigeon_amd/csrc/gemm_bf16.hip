@@ -86,39 +86,11 @@ __device__ __forceinline__ void staged_epilogue(f32x16 (&acc)[TM][TN], const Gem
     }
 }
 
-// One K tile (BK = 64 = 4 k-steps of 16) of MFMAs for a wave's TM x TN tiles, fragments software-pipelined:
-// the ds_reads of k-step kk+1 are issued before the MFMAs of kk.  a_ptr / b_ptr already include the lane's row.
-template <typename T, int TM, int TN>
-__device__ __forceinline__ void mma_ktile(f32x16 (&acc)[TM][TN], const char* a_ptr, const char* b_ptr, const int (&xoff)[4]) {
-    typename T::v8 af[2][TM], bfr[2][TN];
-#pragma unroll
-    for (int i = 0; i < TM; ++i) af[0][i] = *(const typename T::v8*)(a_ptr + i * 32 * ROWB + xoff[0]);
-#pragma unroll
-    for (int j = 0; j < TN; ++j) bfr[0][j] = *(const typename T::v8*)(b_ptr + j * 32 * ROWB + xoff[0]);
-#pragma unroll
-    for (int kk = 0; kk < 4; ++kk) {
-        if (kk < 3) {
-#pragma unroll
-            for (int i = 0; i < TM; ++i)
-                af[(kk + 1) & 1][i] = *(const typename T::v8*)(a_ptr + i * 32 * ROWB + xoff[kk < 3 ? kk + 1 : 3]);
-#pragma unroll
-            for (int j = 0; j < TN; ++j)
-                bfr[(kk + 1) & 1][j] = *(const typename T::v8*)(b_ptr + j * 32 * ROWB + xoff[kk < 3 ? kk + 1 : 3]);
-        }
-        __builtin_amdgcn_s_setprio(1);
-        // swapped operands: D[n][m] -> lane owns row m = lane&31, columns n = (r&3)+8*(r>>2)+4*(lane>>5)
-#pragma unroll
-        for (int i = 0; i < TM; ++i)
-#pragma unroll
-            for (int j = 0; j < TN; ++j)
-                acc[i][j] = T::mfma(bfr[kk & 1][j], af[kk & 1][i], acc[i][j]);
-        __builtin_amdgcn_s_setprio(0);
-    }
-}
-
-// Same K tile, but the next tile's direct-to-LDS DMAs are issued in NDMA/4-sized slices between the k-steps
-// instead of all at once after the barrier: a DMA issue can stall its wave for 100+ cycles when the vector-memory
-// queue is backed up, and spreading them lets the other wave of the SIMD keep the matrix pipe busy meanwhile.
+// One K tile (BK = 64 = 4 k-steps of 16) of MFMAs for a wave's TM x TN tiles, fragments software-pipelined (the ds_reads of
+// k-step kk+1 are issued before the MFMAs of kk; a_ptr / b_ptr already include the lane's row), and the next tile's
+// direct-to-LDS DMAs issued in NDMA/4-sized slices between the k-steps instead of all at once after the barrier: a DMA issue
+// can stall its wave for 100+ cycles when the vector-memory queue is backed up, and spreading them lets the other wave of
+// the SIMD keep the matrix pipe busy meanwhile.
 template <typename T, int TM, int TN, int NDMA>
 __device__ __forceinline__ void mma_ktile_dma(f32x16 (&acc)[TM][TN], const char* a_ptr, const char* b_ptr, const int (&xoff)[4],
                                               const uint16_t* const (&src)[NDMA], const int (&ldsoff)[NDMA], char* nxt,
@@ -145,6 +117,7 @@ __device__ __forceinline__ void mma_ktile_dma(f32x16 (&acc)[TM][TN], const char*
             for (int d = 0; d < PER; ++d) glds16(src[kk * PER + d] + koff, nxt + ldsoff[kk * PER + d]);
         }
         __builtin_amdgcn_s_setprio(1);
+        // swapped operands: D[n][m] -> lane owns row m = lane&31, columns n = (r&3)+8*(r>>2)+4*(lane>>5)
 #pragma unroll
         for (int i = 0; i < TM; ++i)
 #pragma unroll
@@ -155,10 +128,14 @@ __device__ __forceinline__ void mma_ktile_dma(f32x16 (&acc)[TM][TN], const char*
 }
 
 // ================================================================================================================
-// Kernel A: BM x BN block tile, WM x WN waves, 2 LDS stages of (A|W), one __syncthreads per K tile.
+// Variant 8: 256 x 256 block tile, 2 x 4 waves, 2 LDS stages of (A|W), one __syncthreads per K tile, N-fastest raster.
+// (The other tilings -- 128 x 128, 256 x 128, a 3-stage A ring -- and their ablations were removed; see git history.)
 // ================================================================================================================
-template <typename T, int BM, int BN, int WM, int WN, int EPI, bool DIRECT, bool PIPE, int DBG = 0>
-__global__ __launch_bounds__(WM * WN * 64) void gemm_bf16_kernel(GemmArgs g) {
+constexpr int OT_BM = 256, OT_BN = 256, OT_WM = 2, OT_WN = 4;
+
+template <typename T, int EPI>
+__global__ __launch_bounds__(OT_WM * OT_WN * 64) void gemm_bf16_kernel(GemmArgs g) {
+    constexpr int BM = OT_BM, BN = OT_BN, WM = OT_WM, WN = OT_WN;
     constexpr int NW = WM * WN;
     constexpr int WTM = BM / WM, WTN = BN / WN;
     constexpr int TM = WTM / 32, TN = WTN / 32;
@@ -166,7 +143,6 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm_bf16_kernel(GemmArgs g) {
     constexpr int GROUPS = (BM + BN) / 8;        // 8-row DMA groups per stage
     constexpr int LPW = GROUPS / NW;             // DMA instructions per wave per stage
     static_assert(GROUPS % NW == 0, "stage must split evenly over waves");
-    static_assert(BM % 16 == 0 && BN % 16 == 0, "tile alignment");
 
     extern __shared__ __attribute__((aligned(16))) char smem[];
 
@@ -228,151 +204,8 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm_bf16_kernel(GemmArgs g) {
         // and every wave is done reading the buffer tile t+1 is about to overwrite.
         __syncthreads();
         const int cur = t & 1;
-        if constexpr ((DBG & 4) != 0) {                 // DMA of tile t+1 interleaved with the k-steps of tile t
-            mma_ktile_dma<T, TM, TN, LPW>(acc, smem + cur * STAGE + a_base, smem + cur * STAGE + b_base, xoff, src, ldsoff,
-                                          smem + (cur ^ 1) * STAGE, (int64_t)(t + 1) * BK, t + 1 < nt);
-            continue;
-        }
-        if (t + 1 < nt && !(DBG & 1)) {                 // DBG&1: ablation -- no DMA inside the loop (results are garbage)
-            char* nxt = smem + (cur ^ 1) * STAGE;
-#pragma unroll
-            for (int i = 0; i < LPW; ++i) glds16(src[i] + (int64_t)(t + 1) * BK, nxt + ldsoff[i]);
-        }
-        const char* sb = smem + cur * STAGE;
-        if (DBG & 2) {                                   // DBG&2: ablation -- MFMAs only, no ds_reads in the loop
-            typename T::v8 f = *(const typename T::v8*)(smem + a_base);
-            asm volatile("" : "+v"(f));
-#pragma unroll
-            for (int kk = 0; kk < 4; ++kk)
-#pragma unroll
-                for (int i = 0; i < TM; ++i)
-#pragma unroll
-                    for (int j = 0; j < TN; ++j) acc[i][j] = T::mfma(f, f, acc[i][j]);
-            continue;
-        }
-        if (PIPE) {
-            mma_ktile<T, TM, TN>(acc, sb + a_base, sb + b_base, xoff);
-            continue;
-        }
-#pragma unroll
-        for (int kk = 0; kk < 4; ++kk) {
-            typename T::v8 af[TM], bfr[TN];
-#pragma unroll
-            for (int i = 0; i < TM; ++i)
-                af[i] = *(const typename T::v8*)(sb + a_base + i * 32 * ROWB + xoff[kk]);
-#pragma unroll
-            for (int j = 0; j < TN; ++j)
-                bfr[j] = *(const typename T::v8*)(sb + b_base + j * 32 * ROWB + xoff[kk]);
-#pragma unroll
-            for (int i = 0; i < TM; ++i)
-#pragma unroll
-                for (int j = 0; j < TN; ++j)
-                    acc[i][j] = T::mfma(bfr[j], af[i], acc[i][j]);
-        }
-    }
-
-    if (DIRECT) {
-        // simple (slow) epilogue kept as a debugging fallback: scalar stores straight from the accumulators
-#pragma unroll
-        for (int i = 0; i < TM; ++i) {
-            const int row = m0 + wm * WTM + i * 32 + lrow;
-#pragma unroll
-            for (int j = 0; j < TN; ++j)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int col = n0 + wn * WTN + j * 32 + (r & 3) + 8 * (r >> 2) + 4 * lhalf;
-                    if (row < g.M) epi_store_scalar<T, EPI>(g, row, col, acc[i][j][r]);
-                }
-        }
-        return;
-    }
-    staged_epilogue<T, EPI, TM, TN, WTM, WTN>(acc, g, smem, wave, lane, m0 + wm * WTM, n0 + wn * WTN);
-}
-
-// ================================================================================================================
-// Kernel B ("a3w2"): 256 x 256 tile, 8 waves (2 x 4), the whole 160 KB of LDS:
-//     A ring  3 x 32 KB  -- activations stream from HBM/MALL (every A line is a compulsory miss for the first of
-//                           the gn blocks that share it), so A is prefetched TWO K tiles ahead;
-//     W ring  2 x 32 KB  -- weights hit the XCD's L2 (see tile_coords), one tile of lookahead is enough.
-// vmcnt retires in issue order, so each iteration issues W(t+1) BEFORE A(t+2): at the top of iteration t the
-// queue is [A(t) W(t) | A(t+1)] and `s_waitcnt vmcnt(4)` (this wave's 4 newest DMAs may stay in flight) is exactly
-// "A(t) and W(t) have landed".  Raw s_barrier + counted waits: a __syncthreads() would drain vmcnt to 0.
-// ================================================================================================================
-template <typename T, int EPI>
-__global__ __launch_bounds__(512) void gemm16_a3w2_kernel(GemmArgs g) {
-    constexpr int BM = 256, BN = 256, WN = 4, NW = 8, WTM = 128, WTN = 64, TM = 4, TN = 2;
-    constexpr int ASTG = BM * ROWB, WSTG = BN * ROWB;                 // 32 KB each
-    constexpr int W_OFF = 3 * ASTG;
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wm = wave / WN, wn = wave % WN;
-    int tm, tn;
-    tile_coords(g, tm, tn);
-    const int m0 = tm * BM, n0 = tn * BN;
-
-    const uint16_t* srcA[4];
-    const uint16_t* srcW[4];
-    int ldsoff[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int grp = wave + i * NW;                                // 8-row group 0..31 inside a 256-row stage
-        const int r = grp * 8 + (lane >> 3);
-        const int c = (lane & 7) ^ ((r >> 1) & 7);
-        int row = m0 + r;
-        row = row < g.M ? row : g.M - 1;
-        srcA[i] = g.A + (int64_t)row * g.lda + c * 8;
-        srcW[i] = g.W + (int64_t)(n0 + r) * g.ldw + c * 8;
-        ldsoff[i] = grp * 8 * ROWB;
-    }
-    const int lrow = lane & 31, lhalf = lane >> 5;
-    const int sw = (lane >> 1) & 7;
-    int xoff[4];
-#pragma unroll
-    for (int kk = 0; kk < 4; ++kk) xoff[kk] = ((kk * 2 + lhalf) ^ sw) << 4;
-    const int a_base = (wm * WTM + lrow) * ROWB;
-    const int b_base = W_OFF + (wn * WTN + lrow) * ROWB;
-
-    f32x16 acc[TM][TN];
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-
-    const int nt = g.K / BK;
-    // prologue: A(0), W(0), A(1)  (same relative order as the steady state)
-#pragma unroll
-    for (int i = 0; i < 4; ++i) glds16(srcA[i], smem + ldsoff[i]);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) glds16(srcW[i], smem + W_OFF + ldsoff[i]);
-    if (nt > 1) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) glds16(srcA[i] + BK, smem + ASTG + ldsoff[i]);
-    }
-
-    int a_slot = 0;                                                   // t % 3
-    for (int t = 0; t < nt; ++t) {
-        if (t + 1 < nt) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();                                 // tile t visible to all; slots of t-1 are free
-        __builtin_amdgcn_sched_barrier(0);
-        if (t + 1 < nt) {
-            char* wn_ = smem + W_OFF + ((t + 1) & 1) * WSTG;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) glds16(srcW[i] + (int64_t)(t + 1) * BK, wn_ + ldsoff[i]);
-        }
-        if (t + 2 < nt) {
-            const int s2 = a_slot == 0 ? 2 : a_slot - 1;              // (t + 2) % 3
-            char* an_ = smem + s2 * ASTG;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) glds16(srcA[i] + (int64_t)(t + 2) * BK, an_ + ldsoff[i]);
-        }
-        mma_ktile<T, TM, TN>(acc, smem + a_slot * ASTG + a_base, smem + (t & 1) * WSTG + b_base, xoff);
-        a_slot = a_slot == 2 ? 0 : a_slot + 1;
+        mma_ktile_dma<T, TM, TN, LPW>(acc, smem + cur * STAGE + a_base, smem + cur * STAGE + b_base, xoff, src, ldsoff,
+                                      smem + (cur ^ 1) * STAGE, (int64_t)(t + 1) * BK, t + 1 < nt);
     }
     staged_epilogue<T, EPI, TM, TN, WTM, WTN>(acc, g, smem, wave, lane, m0 + wm * WTM, n0 + wn * WTN);
 }
@@ -388,24 +221,17 @@ static int launch_kernel(KFN kfn, bool& attr_set, size_t lds, dim3 grid, dim3 bl
     return pg_check_launch("gemm16");
 }
 
-static int finish_args(GemmArgs& g, int BM, int BN) {
-    if (g.N % BN != 0 || g.K % BK != 0) { pg_set_error("gemm: N %% %d or K %% 64 != 0 (N=%d K=%d)", BN, g.N, g.K); return PG_EINVAL; }
-    g.tilesM = (g.M + BM - 1) / BM;
-    g.tilesN = g.N / BN;
+template <typename T>
+static int launch_one_tile(const GemmArgs& g0, int epi, hipStream_t s) {
+    GemmArgs g = g0;
+    if (g.N % OT_BN != 0 || g.K % BK != 0) { pg_set_error("gemm: N %% %d or K %% 64 != 0 (N=%d K=%d)", OT_BN, g.N, g.K); return PG_EINVAL; }
+    g.tilesM = (g.M + OT_BM - 1) / OT_BM;
+    g.tilesN = g.N / OT_BN;
     g.ntiles = g.tilesM * g.tilesN;
-    if (g.gn <= 0) g.gn = 4;
-    if (g.gn > g.tilesN) g.gn = g.tilesN;
-    return PG_OK;
-}
-
-template <typename T, int BM, int BN, int WM, int WN, bool DIRECT, bool PIPE, int DBG = 0>
-static int launch_cfg(const GemmArgs& g0, int epi, hipStream_t s) {
-    GemmArgs g = g0;
-    int rc = finish_args(g, BM, BN);
-    if (rc) return rc;
-    const size_t lds = 2 * (size_t)(BM + BN) * ROWB;
-    dim3 grid(g.ntiles), block(WM * WN * 64);
-#define PG_LAUNCH(E) { static bool a = false; return launch_kernel(gemm_bf16_kernel<T, BM, BN, WM, WN, E, DIRECT, PIPE, DBG>, a, lds, grid, block, g, s); }
+    g.gn = g.tilesN;                                          // N-fastest raster
+    const size_t lds = 2 * (size_t)(OT_BM + OT_BN) * ROWB;
+    dim3 grid(g.ntiles), block(OT_WM * OT_WN * 64);
+#define PG_LAUNCH(E) { static bool a = false; return launch_kernel(gemm_bf16_kernel<T, E>, a, lds, grid, block, g, s); }
     switch (epi) {
         case EPI_QKV: PG_LAUNCH(EPI_QKV)
         case EPI_GELU: PG_LAUNCH(EPI_GELU)
@@ -417,64 +243,14 @@ static int launch_cfg(const GemmArgs& g0, int epi, hipStream_t s) {
 #undef PG_LAUNCH
 }
 
-template <typename T>
-static int launch_a3w2(const GemmArgs& g0, int epi, hipStream_t s) {
-    GemmArgs g = g0;
-    int rc = finish_args(g, 256, 256);
-    if (rc) return rc;
-    const size_t lds = 5 * 256 * ROWB;                               // 160 KB: the whole LDS of a CU
-    dim3 grid(g.ntiles), block(512);
-#define PG_LAUNCH(E) { static bool a = false; return launch_kernel(gemm16_a3w2_kernel<T, E>, a, lds, grid, block, g, s); }
-    switch (epi) {
-        case EPI_QKV: PG_LAUNCH(EPI_QKV)
-        case EPI_GELU: PG_LAUNCH(EPI_GELU)
-        case EPI_RESID: PG_LAUNCH(EPI_RESID)
-        case EPI_PATCH: PG_LAUNCH(EPI_PATCH)
-        case EPI_F32: PG_LAUNCH(EPI_F32)
-        default: pg_set_error("gemm: bad epilogue %d", epi); return PG_EINVAL;
-    }
-#undef PG_LAUNCH
-}
-
-template <typename T>
-static int gemm_dispatch(GemmArgs& g, int epi, int variant, hipStream_t s) {
-    switch (variant) {
-        // the product library carries ONE one-tile-per-block kernel (variant 8: the fallback for shapes the persistent kernel
-        // does not take, and the bit-exact reference the persistent kernels are tested against); the older tilings and the
-        // timing-only ablations (21..23: wrong results by construction) exist only in the -DPIGEON_ABLATIONS tools build
-        case 8: g.gn = 1 << 20; return launch_cfg<T, 256, 256, 2, 4, false, true, 4>(g, epi, s);   // 256x256, N-fastest raster, interleaved DMA
-#ifdef PIGEON_ABLATIONS
-        case 1: return launch_cfg<T, 256, 256, 2, 4, false, false>(g, epi, s);
-        case 2: return launch_cfg<T, 128, 128, 2, 2, false, true>(g, epi, s);
-        case 3: return launch_cfg<T, 256, 128, 4, 2, false, true>(g, epi, s);
-        case 4: return launch_cfg<T, 256, 256, 2, 4, false, true>(g, epi, s);
-        case 5: return launch_a3w2<T>(g, epi, s);
-        case 6: g.gn = 1 << 20; return launch_cfg<T, 256, 256, 2, 4, false, true>(g, epi, s);   // variant 4, N-fastest raster
-        case 7: g.gn = 1 << 20; return launch_a3w2<T>(g, epi, s);                                  // variant 5, N-fastest raster
-        case 11: return launch_cfg<T, 256, 256, 2, 4, true, false>(g, epi, s);
-        case 21: g.gn = 1 << 20; return launch_cfg<T, 256, 256, 2, 4, false, true, 1>(g, epi, s);   // no in-loop DMA
-        case 22: g.gn = 1 << 20; return launch_cfg<T, 256, 256, 2, 4, false, true, 2>(g, epi, s);   // no ds_reads
-        case 23: g.gn = 1 << 20; return launch_cfg<T, 256, 256, 2, 4, false, true, 3>(g, epi, s);   // neither
-#endif
-        default: pg_set_error("gemm: variant %d is not part of this build", variant); return PG_EINVAL;
-    }
-}
-
-// the N tile of the one-tile variant (the `case`s above), 0 = not part of this build
-int pg_gemm_one_tile_bn(int variant) {
-    switch (variant) {
-        case 8: return 256;
-#ifdef PIGEON_ABLATIONS
-        case 1: case 4: case 5: case 6: case 7: case 11: case 21: case 22: case 23: return 256;
-        case 2: case 3: return 128;
-#endif
-        default: return 0;
-    }
-}
+// the N tile of the one-tile kernel for `variant`, 0 = not a one-tile variant.  The product library carries ONE one-tile-per-block
+// kernel (variant 8): the fallback for shapes the persistent kernels do not take, and the bit-exact reference they are tested against.
+int pg_gemm_one_tile_bn(int variant) { return variant == PG_GEMM_V_ONE_TILE ? OT_BN : 0; }
 
 int pg_gemm_one_tile_launch(int dtype, GemmArgs g, int epi, int variant, hipStream_t s) {
-    if (dtype == PG_DTYPE_F16) return gemm_dispatch<T_F16>(g, epi, variant, s);
-    if (dtype == PG_DTYPE_BF16) return gemm_dispatch<T_BF16>(g, epi, variant, s);
+    if (variant != PG_GEMM_V_ONE_TILE) { pg_set_error("gemm: variant %d is not a one-tile variant (8)", variant); return PG_EINVAL; }
+    if (dtype == PG_DTYPE_F16) return launch_one_tile<T_F16>(g, epi, s);
+    if (dtype == PG_DTYPE_BF16) return launch_one_tile<T_BF16>(g, epi, s);
     pg_set_error("gemm: operand dtype must be PG_DTYPE_F16 or PG_DTYPE_BF16 (got %d)", dtype);
     return PG_EINVAL;
 }

@@ -18,17 +18,17 @@ struct GemmArgs {
     int tilesM, tilesN, ntiles;
     int part_tiles;               // tiles of ONE part (tilesM x tilesN); ntiles = ex.parts x part_tiles (EPI_F32, gemm_pp.hip)
     int gn;                       // N tiles per raster group (see tile_coords)
-    int stagger;                  // gemm_pp (tools build): shader cycles of one output tile, per-CU start stagger (0 = off)
+    int stagger;                  // gemm_pp: per-CU start stagger in shader cycles (0 = off; nothing sets it now); -7 arms PG_TS
     int xcd_stagger_ticks;        // persistent kernels: XCD x starts x * ticks / 8 wall-clock ticks (100 MHz) late (0 = off)
     PgGemmExtra ex;               // LayerNorm-fold epilogues (EPI_RESID_STAT / EPI_QKV_LN / EPI_GELU_LN)
 };
 
 // The kernels' launchers (gemm_plan.hip's pg_gemm_launch calls them); tilesM/tilesN/ntiles are filled in by the callee.
-// gemm_bf16.hip: the one-tile-per-block kernel (variant 8; the older tilings in the tools build).  pg_gemm_one_tile_bn: its N tile
-// for `variant`, 0 = not part of this build.
+// gemm_bf16.hip: the one-tile-per-block kernel (variant 8).  pg_gemm_one_tile_bn: its N tile for `variant`, 0 = not a one-tile
+// variant.
 int pg_gemm_one_tile_bn(int variant);
 int pg_gemm_one_tile_launch(int dtype, GemmArgs g, int epi, int variant, hipStream_t s);
-// gemm_pp.hip: persistent ping-pong kernel (variants 30..49)
+// gemm_pp.hip: persistent ping-pong kernel (variants 33, 36)
 int pg_gemm_pp_launch(int dtype, GemmArgs g, int epi, int variant, hipStream_t s);
 // gemm_pp6.hip: the same kernel with a 384 x 256 block tile, 16-bit-output epilogues and EPI_RESID_STAT (variant 56)
 bool pg_gemm_pp6_supported(int epi, int N, int K);
@@ -58,9 +58,9 @@ int pg_gemm_tail_launch(int dtype, GemmArgs g, int epi, int m_begin, hipStream_t
 bool pg_gemm_mid_supported(int epi, int N, int K);
 int pg_gemm_mid_launch(int dtype, GemmArgs g, int epi, hipStream_t s, int m_begin = 0);
 
-// Tools build only: wall-clock stamps (100 MHz) from inside the persistent kernels, blocks 0 and 100, every wave, first 16 tiles:
+// Probe build only (-DPIGEON_PROBES): wall-clock stamps (100 MHz) from inside the persistent kernels, blocks 0 and 100, every wave, first 16 tiles:
 // buf[((blk * 16 + tile) * 8 + wave) * 12 + slot].  Armed by pg_dbg_timestamps(buf) (gemm_plan.hip), read by tools/epi_timeline.py.
-#ifdef PIGEON_ABLATIONS
+#ifdef PIGEON_PROBES
 #define PG_TS(g, iter, wave, slot)                                                                                             \
     do {                                                                                                                       \
         if ((g).stagger == -7 && (blockIdx.x == 0 || blockIdx.x == 100) && (threadIdx.x & 63) == 0 && (iter) < 16)             \
@@ -207,26 +207,3 @@ __device__ __forceinline__ void epi_store_bf16x8(const GemmArgs& g, int row, int
     pk[2] = pack16x2<T>(hi[0], hi[1]); pk[3] = pack16x2<T>(hi[2], hi[3]);
     *(u32x4*)((uint16_t*)g.out + (int64_t)row * g.ldc + col) = pk;
 }
-
-template <typename T, int EPI>
-__device__ __forceinline__ void epi_store_scalar(const GemmArgs& g, int row, int col, float v) {
-    if (EPI == EPI_QKV) {
-        if (g.bias) v += g.bias[col];
-        if (col < g.qcols) v *= g.qscale;
-        ((uint16_t*)g.out)[(int64_t)row * g.ldc + col] = T::bits(v);
-    } else if (EPI == EPI_GELU) {
-        v = quick_gelu(v + g.bias[col]);
-        ((uint16_t*)g.out)[(int64_t)row * g.ldc + col] = T::bits(v);
-    } else if (EPI == EPI_RESID) {
-        float* p = (float*)g.out + (int64_t)row * g.ldc + col;
-        *p = *p + (v + g.bias[col]);
-    } else if (EPI == EPI_PATCH) {
-        const int img = row / VIT_PATCHES, p = row - img * VIT_PATCHES;
-        float* o = (float*)g.out + ((int64_t)img * VIT_TOKENS + 1 + p) * g.ldc + col;
-        *o = v + g.aux[(int64_t)(1 + p) * g.N + col];
-    } else {
-        if (g.bias) v += g.bias[col];
-        ((float*)g.out)[(int64_t)row * g.ldc + col] = v;
-    }
-}
-

@@ -1,7 +1,7 @@
 // gemm_plan.hip -- host only, no kernels: which GEMM kernel runs which rows.  pg_gemm_launch, every GEMM of the encoder, checks its
 // arguments, asks gemm_plan for a plan and makes at most two launcher calls.  Five bit-identical kernels take a GEMM:
 //   PP6       gemm_pp6.hip   384 x 256 tiles, persistent
-//   PP        gemm_pp.hip    256 x 256 tiles, persistent (the raster / schedule variants 30..49)
+//   PP        gemm_pp.hip    256 x 256 tiles, persistent (variants 33 and 36: two rasters)
 //   MID       gemm_mid.hip   128 x 128 tiles, one per block
 //   TAIL      gemm_tail.hip  32 x 64 tiles, one per wave
 //   ONE_TILE  gemm_bf16.hip  256 x 256 tiles, one per block (variant 8: the reference of the others)
@@ -263,7 +263,7 @@ struct GemmPlan {
     int stagger_ticks;   // GemmArgs::xcd_stagger_ticks of both launches
 };
 
-static bool is_pp_variant(int v) { return v >= 30 && v < 50; }
+static bool is_pp_variant(int v) { return v == 33 || v == PG_GEMM_V_PP; }
 static bool use_pp6(int variant, int epi, int N, int K) {
     return variant == PG_GEMM_V_PP6 && pg_gemm_pp6_supported(epi, N, K) && (epi != EPI_RESID_STAT || resid6_enabled(K));
 }
@@ -358,13 +358,12 @@ static int gemm_plan(int variant, int epi, int M, int N, int K, GemmPlan& p) {
         return PG_OK;
     }
     // the one-tile-per-block kernel: variant 8 for the persistent variants on shapes they do not take, else the caller's variant
-    if (epi >= EPI_RESID_STAT) { pg_set_error("gemm: epilogue %d exists only in the persistent kernel (variants 30..49, N %% 256 == 0, K %% 128 == 0)", epi); return PG_EINVAL; }
+    if (epi >= EPI_RESID_STAT) { pg_set_error("gemm: epilogue %d exists only in the persistent kernels (variants 33, 36, 56, N %% 256 == 0, K %% 128 == 0)", epi); return PG_EINVAL; }
     p.kernel = PG_GK_ONE_TILE;
     p.variant = (variant == PG_GEMM_V_PP6 || is_pp_variant(variant)) ? PG_GEMM_V_ONE_TILE : variant;
     const int bn = pg_gemm_one_tile_bn(p.variant);
     if (bn == 0) {
-        pg_set_error("gemm: variant %d is not part of this build (product variants: 8, 33, 36, 56, 70, 71; the rest needs the "
-                     "-DPIGEON_ABLATIONS tools build, python -m pigeon_amd.build --dev)", p.variant);
+        pg_set_error("gemm: variant %d does not exist (variants: 8, 33, 36, 56, 70, 71)", p.variant);
         return PG_EINVAL;
     }
     if (N % bn != 0 || K % BK != 0) { pg_set_error("gemm: N %% %d or K %% 64 != 0 (N=%d K=%d)", bn, N, K); return PG_EINVAL; }
@@ -381,9 +380,9 @@ extern "C" int pg_gemm_plan(int variant, int epi, int M, int N, int K, int* kern
     return PG_OK;
 }
 
-#ifdef PIGEON_ABLATIONS
+#ifdef PIGEON_PROBES
 static void* g_dbg_ts = nullptr;
-// tools build: arm (buf != null) / disarm the PG_TS time stamps of the persistent kernels; buf = 2 * 16 * 8 * 12 uint64 on the device
+// probe build: arm (buf != null) / disarm the PG_TS time stamps of the persistent kernels; buf = 2 * 16 * 8 * 12 uint64 on the device
 extern "C" int pg_dbg_timestamps(void* buf) { g_dbg_ts = buf; return PG_OK; }
 #endif
 
@@ -425,9 +424,8 @@ int pg_gemm_launch(int dtype, const void* A, int64_t lda, const void* W, int64_t
     if (rc != PG_OK) return rc;
     g.xcd_stagger_ticks = p.stagger_ticks;
     if (g.ex.stat_rows <= 0) g.ex.stat_rows = M;
-#ifdef PIGEON_ABLATIONS
+#ifdef PIGEON_PROBES
     if (g_dbg_ts && epi != EPI_PATCH) { g.aux = (const float*)g_dbg_ts; g.stagger = -7; }
-    else if (epi == EPI_RESID_STAT) { static const bool abl = getenv("PIGEON_EPI_ABL") != nullptr; if (abl) g.stagger = -11; }
 #endif
     // all five kernels produce the same bits for a row: the plan changes timing only
     GemmArgs gm = g;

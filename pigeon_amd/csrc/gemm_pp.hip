@@ -45,17 +45,11 @@ constexpr int PP_SLAB_OFF = PP_STAGE;                      // epilogue slabs ove
 constexpr int PP_SLAB_ROWF = 64 + 4;                       // padded slab row, floats
 constexpr int PP_SLAB_BYTES = 32 * PP_SLAB_ROWF * 4;       // 8704 B per wave
 constexpr int PP_LDS = 160 * 1024;
-#ifndef PP_DMA_AUX
-#define PP_DMA_AUX 0                                     // cache policy of the operand DMAs (bit 0 sc0, bit 1 nt, bit 4 sc1)
-#endif
-#ifndef PP_STORE_AUX
-#define PP_STORE_AUX 0                                   // cache policy of the epilogue stores (bit 0 sc0, bit 1 nt, bit 4 sc1)
-#endif
 
 typedef __attribute__((address_space(3))) void lds_void;
 
 __device__ __forceinline__ void dma16(__amdgpu_buffer_rsrc_t rsrc, char* lds_wave_uniform, int voff, int soff) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lds_void*)lds_wave_uniform, 16, voff, soff, 0, PP_DMA_AUX);
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lds_void*)lds_wave_uniform, 16, voff, soff, 0, 0);
 }
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* base, uint32_t bytes) {
     return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), (short)0, (int)bytes, 0x00020000);
@@ -72,7 +66,7 @@ struct TileCtx {
 // is plain N-fastest order.  A persistent round gives every XCD 32 consecutive ids, i.e. one (32/gn) x gn super-tile:
 // the unique operand bytes an XCD's L2 must fetch per K step are (32/gn + gn) panels (12 for 8 x 4, against 14.7 /
 // 18 for N-fastest rows of 12 / 16 tiles).
-template <int ABL, bool PARTS = false>
+template <bool PARTS = false>
 __device__ __forceinline__ TileCtx make_tile(const GemmArgs& g, int L) {
     TileCtx c;
     c.part = 0;
@@ -93,25 +87,18 @@ __device__ __forceinline__ TileCtx make_tile(const GemmArgs& g, int L) {
     const int tm = band * gmax + im, tn = sup * g.gn + in;
     c.m0 = tm * PP_BM; c.n0 = tn * PP_BN;
     const int rows = min(PP_BM, g.M - c.m0);
-    if constexpr ((ABL & 2) != 0) {                          // ablation: every tile streams operand panel 0 (all L2 hits)
-        c.ra = make_rsrc(g.A, (uint32_t)PP_BM * (uint32_t)g.lda * 2u);
-        c.rw = make_rsrc(g.W, (uint32_t)PP_BN * (uint32_t)g.ldw * 2u);
-    } else {
-        c.ra = make_rsrc(Ab + (int64_t)c.m0 * g.lda, (uint32_t)rows * (uint32_t)g.lda * 2u);
-        c.rw = make_rsrc(Wb + (int64_t)c.n0 * g.ldw, (uint32_t)PP_BN * (uint32_t)g.ldw * 2u);
-    }
+    c.ra = make_rsrc(Ab + (int64_t)c.m0 * g.lda, (uint32_t)rows * (uint32_t)g.lda * 2u);
+    c.rw = make_rsrc(Wb + (int64_t)c.n0 * g.ldw, (uint32_t)PP_BN * (uint32_t)g.ldw * 2u);
     return c;
 }
 
 // DMA d of a K tile: d 0..3 = this wave's four 8-row groups of A, d 4..7 = of W.
-// SKIP (timing-only ablations 44 / 45): bit mask of DMAs left out -- what would 12.5 % / 25 % fewer operand bytes per tile buy?
-template <int FROM, int CNT, int SKIP = 0>
+template <int FROM, int CNT>
 __device__ __forceinline__ void issue_dma(const TileCtx& c, char* stage, int wave, const int (&voffA)[4], const int (&voffW)[4],
                                           int soff) {
 #pragma unroll
     for (int d = 0; d < 8; ++d) {
         if (d < FROM || d >= FROM + CNT) continue;
-        if ((SKIP >> d) & 1) continue;
         if (d < 4) dma16(c.ra, stage + (wave + 8 * d) * 8 * ROWB, voffA[d], soff);
         else dma16(c.rw, stage + PP_W_OFF + (wave + 8 * (d - 4)) * 8 * ROWB, voffW[d - 4], soff);
     }
@@ -147,31 +134,6 @@ __device__ __forceinline__ void mma16(AccPP& acc, const Frag<T>& f) {
         for (int j = 0; j < 4; ++j) {
             if constexpr (ZERO) T::mfma16_init(acc[HALF * 4 + i][j], f.b[j], f.a[i]);
             else T::mfma16_acc(acc[HALF * 4 + i][j], f.b[j], f.a[i]);
-        }
-}
-
-// PG_PP_PHASES = 2 (round 4 experiment, tools/gemm_ab.py): a phase covers a whole k-step of 32 over all 128 rows of the wave -- 8 A
-// + 4 W fragments (48 registers instead of 32), 32 MFMAs -- so a K tile has 2 phases and 4 CU-wide barriers per wave group instead
-// of 4 and 8.  Same MFMA chain per accumulator over k: bit-identical.
-#ifndef PG_PP_PHASES
-#define PG_PP_PHASES 4
-#endif
-template <typename T> struct Frag2 { typename T::v8 a[8], b[4]; };
-template <typename T>
-__device__ __forceinline__ void load_frag2(Frag2<T>& f, const char* sa, const char* sb, int xo) {
-#pragma unroll
-    for (int i = 0; i < 8; ++i) f.a[i] = *(const typename T::v8*)(sa + i * 16 * ROWB + xo);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) f.b[j] = *(const typename T::v8*)(sb + j * 16 * ROWB + xo);
-}
-template <typename T, bool ZERO>
-__device__ __forceinline__ void mma32(AccPP& acc, const Frag2<T>& f) {
-#pragma unroll
-    for (int i = 0; i < 8; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            if constexpr (ZERO) T::mfma16_init(acc[i][j], f.b[j], f.a[i]);
-            else T::mfma16_acc(acc[i][j], f.b[j], f.a[i]);
         }
 }
 
@@ -231,114 +193,25 @@ __device__ __forceinline__ void fetch_xrows(u32x4 (&dst)[8], const XCtx& x, int 
         dst[it] = __builtin_amdgcn_raw_buffer_load_b128(x.ro, x.voff, __builtin_amdgcn_readfirstlane(slab * x.sstep + it * x.rstep), 0);
 }
 
-// One K tile in ping-pong form.  D0..D2 = number of this wave's 8 DMAs issued in LOAD phases 0..2 (rest in phase 3).
+// One K tile in ping-pong form.  The wave's 8 DMAs of the next K tile go 4 / 4 in the first two LOAD phases (its A groups, then
+// its W groups; schedule 4/4/0/0 -- 8/0/0/0, 6/2/0/0, 5/3/0/0, 4/2/2/0 and 3/3/2/0 measured no better and were removed).
 // XF: this call may also issue the early residual fetch (phases 2 and 3, AFTER the tile's DMAs, so that the counted
 // vmcnt(16) at the end of phase 3 still means "my DMAs of the next K tile have landed").
 // XF 2: EPI_RESID_STAT fetches slab 0 only (eight loads in phase 3; its slab-ahead double buffer covers the rest).
-template <typename T, int D0, int D1, int D2, int ABL, int XF = 0, bool ZERO = false>
+template <typename T, int XF = 0, bool ZERO = false>
 __device__ __forceinline__ void ktile_pp(AccPP& acc, const char* cur, char* nxt, int a_base, int b_base,
                                          const int (&xoff)[2], const TileCtx& c, int wave, const int (&voffA)[4],
                                          const int (&voffW)[4], int soff_next, bool has_next, bool xf, const XCtx& xc,
                                          u32x4 (&xq)[4][8]) {
-    constexpr int D3 = 8 - D0 - D1 - D2;
-    static_assert(D3 >= 0, "DMA schedule");
-#if PG_PP_PHASES == 2
-    {
-        Frag2<T> f2;
-#pragma unroll
-        for (int ss = 0; ss < 2; ++ss) {
-            load_frag2<T>(f2, cur + a_base, cur + b_base, xoff[ss]);
-            if (has_next) {
-                if (ss == 0) issue_dma<0, D0 + D1, 0>(c, nxt, wave, voffA, voffW, soff_next);
-                if (ss == 1) issue_dma<D0 + D1, D2 + D3, 0>(c, nxt, wave, voffA, voffW, soff_next);
-            }
-            if constexpr (XF == 1) {
-                if (xf && ss == 1) { fetch_xrows(xq[0], xc, 0); fetch_xrows(xq[1], xc, 1); }
-            }
-            if constexpr (XF == 2) {
-                if (xf && ss == 1) fetch_xrows_wide(xq[0], xc);
-            }
-            if (ss == 1 && has_next) {
-                if (XF == 1 && xf) asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
-                else if (XF == 2 && xf) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-                else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            }
-            wait_lgkm0();
-            raw_barrier();
-            __builtin_amdgcn_s_setprio(1);
-            if (ss == 0) mma32<T, ZERO>(acc, f2);
-            else mma32<T, false>(acc, f2);
-            __builtin_amdgcn_s_setprio(0);
-            raw_barrier();
-        }
-        return;
-    }
-#endif
-#if PG_PP_PHASES == 8
-    {   // eight phases per K tile: (k-step s, quarter q of the wave's 128 rows), 2 A fragments per phase, the 4 W fragments of a k-step
-        // read in its first quarter; 8 MFMAs per phase, 16 barriers per K tile and wave group
-        typename T::v8 fa[2], fb[4];
-#pragma unroll
-        for (int ph = 0; ph < 8; ++ph) {
-            const int ss = ph >> 2, q = ph & 3;
-#pragma unroll
-            for (int i = 0; i < 2; ++i) fa[i] = *(const typename T::v8*)(cur + a_base + (q * 2 + i) * 16 * ROWB + xoff[ss]);
-            if (q == 0) {
-#pragma unroll
-                for (int j = 0; j < 4; ++j) fb[j] = *(const typename T::v8*)(cur + b_base + j * 16 * ROWB + xoff[ss]);
-            }
-            if (has_next) {
-                if (ph == 0) issue_dma<0, 2, 0>(c, nxt, wave, voffA, voffW, soff_next);
-                if (ph == 1) issue_dma<2, 2, 0>(c, nxt, wave, voffA, voffW, soff_next);
-                if (ph == 2) issue_dma<4, 2, 0>(c, nxt, wave, voffA, voffW, soff_next);
-                if (ph == 3) issue_dma<6, 2, 0>(c, nxt, wave, voffA, voffW, soff_next);
-            }
-            if constexpr (XF == 1) {
-                if (xf && ph == 5) fetch_xrows(xq[0], xc, 0);
-                if (xf && ph == 7) fetch_xrows(xq[1], xc, 1);
-            }
-            if constexpr (XF == 2) {
-                if (xf && ph == 7) fetch_xrows_wide(xq[0], xc);
-            }
-            if (ph == 7 && has_next) {
-                if (XF == 1 && xf) asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
-                else if (XF == 2 && xf) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-                else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            }
-            wait_lgkm0();
-            raw_barrier();
-            __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-            for (int i = 0; i < 2; ++i)
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    if (ZERO && ss == 0) T::mfma16_init(acc[q * 2 + i][j], fb[j], fa[i]);
-                    else T::mfma16_acc(acc[q * 2 + i][j], fb[j], fa[i]);
-                }
-            __builtin_amdgcn_s_setprio(0);
-            raw_barrier();
-        }
-        return;
-    }
-#endif
     Frag<T> f;
-    if constexpr ((ABL & 4) != 0) {                          // ablation: fragments read once per K tile (wrong results)
-        load_frag<T, true>(f, cur + a_base, cur + b_base, xoff[0]);
-        asm volatile("" : "+v"(f.a[0]), "+v"(f.a[1]), "+v"(f.a[2]), "+v"(f.a[3]), "+v"(f.b[0]), "+v"(f.b[1]), "+v"(f.b[2]), "+v"(f.b[3]));
-    }
 #pragma unroll
     for (int kk = 0; kk < 4; ++kk) {
         // phase kk = (k-step s = kk >> 1, half = kk & 1)
-        if constexpr ((ABL & 4) == 0) {
-            if ((kk & 1) == 0) load_frag<T, true>(f, cur + a_base, cur + b_base, xoff[kk >> 1]);
-            else load_frag<T, false>(f, cur + a_base + 64 * ROWB, cur + b_base, xoff[kk >> 1]);
-        }
-        if (has_next && (ABL & 1) == 0) {                    // ABL&1: ablation, no DMA inside the K loop (wrong results)
-            constexpr int SKIP = (ABL & 8) ? 0x80 : ((ABL & 16) ? 0x88 : 0);
-            if (kk == 0) issue_dma<0, D0, SKIP>(c, nxt, wave, voffA, voffW, soff_next);
-            if (kk == 1) issue_dma<D0, D1, SKIP>(c, nxt, wave, voffA, voffW, soff_next);
-            if (kk == 2) issue_dma<D0 + D1, D2, SKIP>(c, nxt, wave, voffA, voffW, soff_next);
-            if (kk == 3) issue_dma<D0 + D1 + D2, D3, SKIP>(c, nxt, wave, voffA, voffW, soff_next);
+        if ((kk & 1) == 0) load_frag<T, true>(f, cur + a_base, cur + b_base, xoff[kk >> 1]);
+        else load_frag<T, false>(f, cur + a_base + 64 * ROWB, cur + b_base, xoff[kk >> 1]);
+        if (has_next) {
+            if (kk == 0) issue_dma<0, 4>(c, nxt, wave, voffA, voffW, soff_next);
+            if (kk == 1) issue_dma<4, 4>(c, nxt, wave, voffA, voffW, soff_next);
         }
         if constexpr (XF == 1) {
             if (xf && kk == 2) fetch_xrows(xq[0], xc, 0);
@@ -361,34 +234,6 @@ __device__ __forceinline__ void ktile_pp(AccPP& acc, const char* cur, char* nxt,
         if (kk == 3) mma16<T, false, 1>(acc, f);
         __builtin_amdgcn_s_setprio(0);
         raw_barrier();
-    }
-}
-
-// Free-running form of the same K tile (MODE 0): one barrier per K tile (taken by the caller), fragments double
-// buffered in registers, the DMAs of the next tile spread 2 per k-step between the MFMA groups (= gemm_bf16 variant 8).
-template <typename T, bool ZERO = false>
-__device__ __forceinline__ void ktile_free(AccPP& acc, const char* cur, char* nxt, int a_base, int b_base,
-                                           const int (&xoff)[2], const TileCtx& c, int wave, const int (&voffA)[4],
-                                           const int (&voffW)[4], int soff_next, bool has_next) {
-    // (tools build only, variant 30; since the 16x16x32 conversion the fragments are read per phase, not double buffered)
-    Frag<T> f;
-#pragma unroll
-    for (int kk = 0; kk < 4; ++kk) {
-        if ((kk & 1) == 0) load_frag<T, true>(f, cur + a_base, cur + b_base, xoff[kk >> 1]);
-        else load_frag<T, false>(f, cur + a_base + 64 * ROWB, cur + b_base, xoff[kk >> 1]);
-        if (has_next) {
-            if (kk == 0) issue_dma<0, 2>(c, nxt, wave, voffA, voffW, soff_next);
-            if (kk == 1) issue_dma<2, 2>(c, nxt, wave, voffA, voffW, soff_next);
-            if (kk == 2) issue_dma<4, 2>(c, nxt, wave, voffA, voffW, soff_next);
-            if (kk == 3) issue_dma<6, 2>(c, nxt, wave, voffA, voffW, soff_next);
-        }
-        wait_lgkm0();
-        __builtin_amdgcn_s_setprio(1);
-        if (kk == 0) mma16<T, ZERO, 0>(acc, f);
-        if (kk == 1) mma16<T, ZERO, 1>(acc, f);
-        if (kk == 2) mma16<T, false, 0>(acc, f);
-        if (kk == 3) mma16<T, false, 1>(acc, f);
-        __builtin_amdgcn_s_setprio(0);
     }
 }
 
@@ -581,28 +426,12 @@ __device__ __forceinline__ void pp_epilogue(AccPP& acc, const GemmArgs& g, char*
                         asm("v_mov_b32 %0, %1" : "=v"(mrs) : "v"(rs[i][it][1]));
                     }
                     const u32x4 pk = epi16_finish<T, EPI>(lo, hi, bias.lo, bias.hi, bias.slo, bias.shi, rstd, mrs, col0 < g.qcols, qsc);
-                    __builtin_amdgcn_raw_buffer_store_b128(pk, ro, ooff, 0, PP_STORE_AUX);
+                    __builtin_amdgcn_raw_buffer_store_b128(pk, ro, ooff, 0, 0);
                 } else if constexpr (RESID) {
                     const f32x4 x = epi_resid4(__builtin_bit_cast(f32x4, XEARLY == 1 ? xq[i][it] : xr[i & 1][it][0]), lo, bias.lo);
-#ifdef PIGEON_ABLATIONS
-                    // timing-only ablation (env PIGEON_EPI_ABL=1, WRONG RESULTS): the fp32 rows written as 8 instead of 16 bytes per
-                    // lane -- the write traffic a residual stream stored as an fp16 value + fp16 correction pair would have
-                    // (8 instead of 10 bytes per element in all)
-                    const bool half_store = STAT && g.stagger == -11;
-                    if (half_store) {
-                        u32x2 hx2; hx2[0] = __builtin_bit_cast(u32x4, x)[0]; hx2[1] = __builtin_bit_cast(u32x4, x)[1];
-                        __builtin_amdgcn_raw_buffer_store_b64(hx2, ro, ooff, 0, 0);
-                    } else
-#endif
-                    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, x), ro, ooff, 0, PP_STORE_AUX);
+                    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, x), ro, ooff, 0, 0);
                     if constexpr (STAT) {
                         const f32x4 y = epi_resid4(__builtin_bit_cast(f32x4, xr[i & 1][it][1]), hi, bias.hi);
-#ifdef PIGEON_ABLATIONS
-                        if (half_store) {
-                            u32x2 hy2; hy2[0] = __builtin_bit_cast(u32x4, y)[0]; hy2[1] = __builtin_bit_cast(u32x4, y)[1];
-                            __builtin_amdgcn_raw_buffer_store_b64(hy2, ro, ooff + HOFF * 4, 0, 0);
-                        } else
-#endif
                         __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, y), ro, ooff + HOFF * 4, 0, 0);
                         __builtin_amdgcn_raw_buffer_store_b64(epi_copy16x4<T>(x), rx16, ooff >> 1, 0, 0);
                         __builtin_amdgcn_raw_buffer_store_b64(epi_copy16x4<T>(y), rx16, (ooff >> 1) + HOFF * 2, 0, 0);
@@ -638,16 +467,14 @@ __device__ __forceinline__ void pp_epilogue(AccPP& acc, const GemmArgs& g, char*
     }
 }
 
-// MODE 0: free-running (one barrier per K tile).  MODE 1: ping-pong.  MODE 2: ping-pong phases without the stagger
-// (both groups in lock step; A/B arm only).
-template <typename T, int EPI, int MODE, int D0, int D1, int D2, int ABL>
+template <typename T, int EPI>
 __global__ __launch_bounds__(512) void gemm_pp_kernel(GemmArgs g) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wave >> 2, wn = wave & 3;
-    const bool follower = (MODE == 1) && (wm == 1);
+    const bool follower = (wm == 1);
 
     // per-lane DMA offsets inside a tile (bytes), constant for the whole kernel
     int voffA[4], voffW[4];
@@ -674,7 +501,7 @@ __global__ __launch_bounds__(512) void gemm_pp_kernel(GemmArgs g) {
     const int nblk = gridDim.x;
     // EPI_F32 only (the exact mode's GEMMs): several independent products in one launch, see PgGemmExtra::parts.  The other
     // epilogues -- every kernel of the fast path -- compile exactly as before.
-    constexpr bool PARTS = (EPI == EPI_F32) && ABL == 0;
+    constexpr bool PARTS = (EPI == EPI_F32);
     int L = xcd_remap(blockIdx.x, nblk);
     if (L >= g.ntiles) return;
     xcd_stagger_wait(g.xcd_stagger_ticks);
@@ -686,7 +513,7 @@ __global__ __launch_bounds__(512) void gemm_pp_kernel(GemmArgs g) {
         const long long until = (long long)__builtin_readcyclecounter() + (long long)g.stagger * slot / 32;
         while ((long long)__builtin_readcyclecounter() < until) __builtin_amdgcn_s_sleep(8);
     }
-    TileCtx c = make_tile<ABL, PARTS>(g, L);
+    TileCtx c = make_tile<PARTS>(g, L);
     issue_dma<0, 8>(c, smem, wave, voffA, voffW, 0);         // K tile 0 of the first output tile -> stage 0
     EpiBias<EPI> bias;
     const int err = lane / (64 / ECPL);                      // the lane's first row inside a 32-row slab on the store side
@@ -701,7 +528,7 @@ __global__ __launch_bounds__(512) void gemm_pp_kernel(GemmArgs g) {
     // (EPI_GELU_X3 issues 96; vmcnt counts to 63)
     constexpr int NST = (EPI == EPI_PATCH) ? 0 : (EPI == EPI_F32 ? 32 : (EPI == EPI_GELU_X3 ? 63 : (epi_ln<EPI>() ? 12 : 16)));
     bool first = true;
-    int dbg_iter = 0;                                        // tile counter of the tools build's time stamps (dead code otherwise)
+    int dbg_iter = 0;                                        // tile counter of the probe build's time stamps (dead code otherwise)
 
     while (true) {
         AccPP acc;                                           // not cleared: the first k-step of the tile runs with C = 0
@@ -717,46 +544,32 @@ __global__ __launch_bounds__(512) void gemm_pp_kernel(GemmArgs g) {
         PG_TS(g, dbg_iter, wave, 0);
         u32x2 rs[4][4];
         if constexpr (epi_ln<EPI>()) load_rowstat<EPI>(rs, g, c.m0 + wm * 128, err);
-        constexpr int XEARLY = (MODE == 0 || ABL != 0) ? 0 : (EPI == EPI_RESID ? 1 : (EPI == EPI_RESID_STAT ? 2 : 0));
+        constexpr int XEARLY = EPI == EPI_RESID ? 1 : (EPI == EPI_RESID_STAT ? 2 : 0);
         XCtx xc;
         u32x4 xq[4][8];
-        if constexpr (MODE == 0) {
-            for (int t = 0; t < nt; t += 2) {
-                if (t > 0) { wait_vm0(); wait_lgkm0(); raw_barrier(); }
-                if (t == 0) ktile_free<T, true>(acc, smem, smem + PP_STAGE, a_base, b_base, xoff, c, wave, voffA, voffW, ROWB, true);
-                else ktile_free<T>(acc, smem, smem + PP_STAGE, a_base, b_base, xoff, c, wave, voffA, voffW, (t + 1) * ROWB, true);
-                wait_vm0(); wait_lgkm0(); raw_barrier();
-                ktile_free<T>(acc, smem + PP_STAGE, smem, a_base, b_base, xoff, c, wave, voffA, voffW, (t + 2) * ROWB, t + 2 < nt);
-            }
-            wait_lgkm0(); raw_barrier();
-        } else {
-            if (follower) raw_barrier();
-            int t0 = 0;
-            if (nt > 2) {                                     // first K-tile pair peeled: its first k-step runs with C = 0
-                ktile_pp<T, D0, D1, D2, ABL, 0, true>(acc, smem, smem + PP_STAGE, a_base, b_base, xoff, c, wave, voffA, voffW,
-                                                          ROWB, true, false, xc, xq);
-                ktile_pp<T, D0, D1, D2, ABL, 0>(acc, smem + PP_STAGE, smem, a_base, b_base, xoff, c, wave, voffA, voffW,
-                                                    2 * ROWB, true, false, xc, xq);
-                t0 = 2;
-            } else {                                          // K = 128: one pair, which may carry the early residual fetch
+        if (follower) raw_barrier();
+        int t0 = 0;
+        if (nt > 2) {                                         // first K-tile pair peeled: its first k-step runs with C = 0
+            ktile_pp<T, 0, true>(acc, smem, smem + PP_STAGE, a_base, b_base, xoff, c, wave, voffA, voffW, ROWB, true, false, xc, xq);
+            ktile_pp<T, 0>(acc, smem + PP_STAGE, smem, a_base, b_base, xoff, c, wave, voffA, voffW, 2 * ROWB, true, false, xc, xq);
+            t0 = 2;
+        } else {                                              // K = 128: one pair, which may carry the early residual fetch
 #pragma unroll
-                for (int i = 0; i < 8; ++i)
+            for (int i = 0; i < 8; ++i)
 #pragma unroll
-                    for (int j = 0; j < 4; ++j)
+                for (int j = 0; j < 4; ++j)
 #pragma unroll
-                        for (int r = 0; r < 4; ++r) acc[i][j][r] = 0.f;
-            }
-            for (int t = t0; t < nt; t += 2) {
-                const bool xf = XEARLY != 0 && (t + 2 == nt);
-                if (XEARLY != 0 && xf) xc = make_xctx<XEARLY == 2>(g, c.m0 + wm * 128, c.n0 + wn * 64, lane);
-                ktile_pp<T, D0, D1, D2, ABL, XEARLY>(acc, smem, smem + PP_STAGE, a_base, b_base, xoff, c, wave, voffA, voffW,
-                                                     (t + 1) * ROWB, true, xf, xc, xq);
-                ktile_pp<T, D0, D1, D2, ABL, 0>(acc, smem + PP_STAGE, smem, a_base, b_base, xoff, c, wave, voffA, voffW,
-                                                    (t + 2) * ROWB, t + 2 < nt, false, xc, xq);
-            }
-            PG_TS(g, dbg_iter, wave, 1);
-            if (MODE == 1 && !follower) raw_barrier();       // re-align: every wave has left the mainloop
+                    for (int r = 0; r < 4; ++r) acc[i][j][r] = 0.f;
         }
+        for (int t = t0; t < nt; t += 2) {
+            const bool xf = XEARLY != 0 && (t + 2 == nt);
+            if (XEARLY != 0 && xf) xc = make_xctx<XEARLY == 2>(g, c.m0 + wm * 128, c.n0 + wn * 64, lane);
+            ktile_pp<T, XEARLY>(acc, smem, smem + PP_STAGE, a_base, b_base, xoff, c, wave, voffA, voffW, (t + 1) * ROWB, true, xf, xc, xq);
+            ktile_pp<T, 0>(acc, smem + PP_STAGE, smem, a_base, b_base, xoff, c, wave, voffA, voffW, (t + 2) * ROWB, t + 2 < nt, false,
+                           xc, xq);
+        }
+        PG_TS(g, dbg_iter, wave, 1);
+        if (!follower) raw_barrier();                         // re-align: every wave has left the mainloop
 
         // the MFMAs are inline asm, so hipcc pads no "matrix-pipe write -> VALU / LDS read" hazard for the accumulators; a
         // follower wave comes here straight from its last MFMA phase (one barrier, which normally covers the 4-pass latency)
@@ -772,7 +585,7 @@ __global__ __launch_bounds__(512) void gemm_pp_kernel(GemmArgs g) {
         // count its in-order vmcnt waits along the path WITHOUT the block, i.e. on the common path it waits for ten extra
         // (younger) operations -- a full memory latency at the start of every epilogue.
         auto prefetch_next = [&]() {
-            c = make_tile<ABL, PARTS>(g, more ? L : L - nblk);
+            c = make_tile<PARTS>(g, more ? L : L - nblk);
             issue_dma<0, 8>(c, smem, wave, voffA, voffW, 0);      // next output tile's K tile 0 -> stage 0 (free since K tile nt-2)
             load_bias<EPI>(bias_next, g, c.n0 + wn * 64 + ecc);   // older than the epilogue's last stores: see NST
             if constexpr (PARTS) { if (c.part > 0) zero_bias<EPI>(bias_next); }
@@ -793,10 +606,10 @@ __global__ __launch_bounds__(512) void gemm_pp_kernel(GemmArgs g) {
     }
 }
 
-template <typename T, int EPI, int MODE, int D0, int D1, int D2, int ABL>
+template <typename T, int EPI>
 int launch_pp(const GemmArgs& g, int nblk, hipStream_t s) {
     static bool attr_set = false;
-    auto kfn = gemm_pp_kernel<T, EPI, MODE, D0, D1, D2, ABL>;
+    auto kfn = gemm_pp_kernel<T, EPI>;
     if (!attr_set) {
         hipError_t e = hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, PP_LDS);
         if (e != hipSuccess) { pg_set_error("gemm_pp: set LDS attr: %s", hipGetErrorString(e)); return PG_EHIP; }
@@ -806,37 +619,21 @@ int launch_pp(const GemmArgs& g, int nblk, hipStream_t s) {
     return pg_check_launch("gemm_pp");
 }
 
-template <typename T, int MODE, int D0, int D1, int D2, int ABL = 0>
+template <typename T>
 int launch_pp_epi(const GemmArgs& g, int epi, int nblk, hipStream_t s) {
-    if constexpr (ABL != 0) {                                // ablations: timing only, two epilogues are enough
-        switch (epi) {
-            case EPI_QKV: case EPI_GELU: return launch_pp<T, EPI_QKV, MODE, D0, D1, D2, ABL>(g, nblk, s);
-            default: return launch_pp<T, EPI_RESID, MODE, D0, D1, D2, ABL>(g, nblk, s);
-        }
-    } else {
-        switch (epi) {
-            case EPI_QKV: return launch_pp<T, EPI_QKV, MODE, D0, D1, D2, 0>(g, nblk, s);
-            case EPI_GELU: return launch_pp<T, EPI_GELU, MODE, D0, D1, D2, 0>(g, nblk, s);
-            case EPI_RESID: return launch_pp<T, EPI_RESID, MODE, D0, D1, D2, 0>(g, nblk, s);
-            case EPI_PATCH: return launch_pp<T, EPI_PATCH, MODE, D0, D1, D2, 0>(g, nblk, s);
-            case EPI_F32: return launch_pp<T, EPI_F32, MODE, D0, D1, D2, 0>(g, nblk, s);
-            case EPI_RESID_STAT: case EPI_QKV_LN: case EPI_GELU_LN: case EPI_GELU_X3:
-                // the LayerNorm-fold epilogues (and the exact mode's fused fc1 epilogue) are built only for the production schedule
-                // (ping-pong, DMA 4/4/0/0)
-                if constexpr (MODE == 1 && D0 == 4 && D1 == 4 && D2 == 0) {
-                    if (epi == EPI_GELU_X3) {
-                        if constexpr (std::is_same<T, T_F16>::value) return launch_pp<T, EPI_GELU_X3, MODE, D0, D1, D2, 0>(g, nblk, s);
-                        else { pg_set_error("gemm_pp: EPI_GELU_X3 exists for fp16 operands only (the exact mode)"); return PG_EINVAL; }
-                    }
-                    if (epi == EPI_RESID_STAT) return launch_pp<T, EPI_RESID_STAT, MODE, D0, D1, D2, 0>(g, nblk, s);
-                    if (epi == EPI_QKV_LN) return launch_pp<T, EPI_QKV_LN, MODE, D0, D1, D2, 0>(g, nblk, s);
-                    return launch_pp<T, EPI_GELU_LN, MODE, D0, D1, D2, 0>(g, nblk, s);
-                } else {
-                    pg_set_error("gemm_pp: epilogue %d exists only in variants 33 / 36 / 38 / 39", epi);
-                    return PG_EINVAL;
-                }
-            default: pg_set_error("gemm_pp: bad epilogue %d", epi); return PG_EINVAL;
-        }
+    switch (epi) {
+        case EPI_QKV: return launch_pp<T, EPI_QKV>(g, nblk, s);
+        case EPI_GELU: return launch_pp<T, EPI_GELU>(g, nblk, s);
+        case EPI_RESID: return launch_pp<T, EPI_RESID>(g, nblk, s);
+        case EPI_PATCH: return launch_pp<T, EPI_PATCH>(g, nblk, s);
+        case EPI_F32: return launch_pp<T, EPI_F32>(g, nblk, s);
+        case EPI_RESID_STAT: return launch_pp<T, EPI_RESID_STAT>(g, nblk, s);
+        case EPI_QKV_LN: return launch_pp<T, EPI_QKV_LN>(g, nblk, s);
+        case EPI_GELU_LN: return launch_pp<T, EPI_GELU_LN>(g, nblk, s);
+        case EPI_GELU_X3:                                    // the exact mode's fused fc1 epilogue
+            if constexpr (std::is_same<T, T_F16>::value) return launch_pp<T, EPI_GELU_X3>(g, nblk, s);
+            else { pg_set_error("gemm_pp: EPI_GELU_X3 exists for fp16 operands only (the exact mode)"); return PG_EINVAL; }
+        default: pg_set_error("gemm_pp: bad epilogue %d", epi); return PG_EINVAL;
     }
 }
 
@@ -844,25 +641,9 @@ template <typename T>
 int dispatch_pp(GemmArgs& g, int epi, int variant, int nblk, hipStream_t s) {
     g.gn = g.tilesN;                                         // N-fastest raster unless the variant says otherwise
     switch (variant) {
-        case 33: return launch_pp_epi<T, 1, 4, 4, 0>(g, epi, nblk, s);    // ping-pong, DMA 4/4/0/0, N-fastest raster
-        case 36: if (g.tilesN % 4 == 0) g.gn = 4; return launch_pp_epi<T, 1, 4, 4, 0>(g, epi, nblk, s);   // 33 + 8x4 super-tile raster (product)
-#ifdef PIGEON_ABLATIONS                                                     // tools build only (python -m pigeon_amd.build --dev)
-        case 30: return launch_pp_epi<T, 0, 2, 2, 2>(g, epi, nblk, s);    // persistent, free-running
-        case 31: return launch_pp_epi<T, 1, 3, 3, 2>(g, epi, nblk, s);    // ping-pong, DMA 3/3/2/0
-        case 34: return launch_pp_epi<T, 2, 4, 4, 0>(g, epi, nblk, s);    // phases without stagger
-        case 37: if (g.tilesN % 4 == 0) g.gn = 4; return launch_pp_epi<T, 1, 3, 3, 2>(g, epi, nblk, s);   // 31 + 8x4 super-tile raster
-        case 38: g.stagger = (g.K / BK) * 2600 + 6000; return launch_pp_epi<T, 1, 4, 4, 0>(g, epi, nblk, s);   // 33 + staggered start
-        case 39: g.stagger = (g.K / BK) * 1300 + 3000; return launch_pp_epi<T, 1, 4, 4, 0>(g, epi, nblk, s);   // 33 + half-period stagger
-        // (DMA schedules 8/0/0/0, 6/2/0/0, 5/3/0/0, 4/2/2/0 measured within +-3 % of 4/4/0/0 -- box-to-box noise -- and removed)
-        // ablations of 33 (timing only, WRONG RESULTS by construction)
-        case 40: return launch_pp_epi<T, 1, 4, 4, 0, 1>(g, epi, nblk, s);          // no DMA in the K loop
-        case 41: return launch_pp_epi<T, 1, 4, 4, 0, 2>(g, epi, nblk, s);          // every DMA hits panel 0 (L2 resident)
-        case 42: return launch_pp_epi<T, 1, 4, 4, 0, 4>(g, epi, nblk, s);          // no fragment ds_reads
-        case 43: return launch_pp_epi<T, 1, 4, 4, 0, 5>(g, epi, nblk, s);          // MFMA + barriers only
-        case 44: return launch_pp_epi<T, 1, 4, 4, 0, 8>(g, epi, nblk, s);          // 7 of 8 operand DMAs (-12.5 % bytes)
-        case 45: return launch_pp_epi<T, 1, 4, 4, 0, 16>(g, epi, nblk, s);         // 6 of 8 operand DMAs (-25 % bytes)
-#endif
-        default: pg_set_error("gemm_pp: variant %d is not part of this build (product: 33, 36; others need -DPIGEON_ABLATIONS)", variant); return PG_EINVAL;
+        case 33: return launch_pp_epi<T>(g, epi, nblk, s);                                  // N-fastest raster
+        case 36: if (g.tilesN % 4 == 0) g.gn = 4; return launch_pp_epi<T>(g, epi, nblk, s); // 8x4 super-tile raster (product)
+        default: pg_set_error("gemm_pp: variant %d is not a persistent schedule (33, 36)", variant); return PG_EINVAL;
     }
 }
 

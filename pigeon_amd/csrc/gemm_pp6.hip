@@ -126,25 +126,14 @@ __device__ __forceinline__ void load_frag6(Frag6<T>& f, uint32_t aA, uint32_t aB
 
 // 24 MFMAs of one phase; swapped operands (weights first): a lane owns output row lane & 15 of a 16 x 16 block and the 4
 // consecutive columns 4 (lane >> 4) ..
-// P6_EARLY (round 4): the barrier that ends an MFMA phase is ARRIVED AT before the phase's last P6_EARLY MFMAs are issued.  The
-// phase stamps of the tools build (tools/stall_probe.py, profiles/r04/gemm_pp6_phase_stamps.txt) show every wave's operands in
-// place when it asks for them (12-15 ns per K tile in vmcnt(0)) and LOAD + barrier = 145 ns against 227 ns of MFMAs -- yet a
-// phase takes ~630 ns where two alternating MFMA sections would take 454: the matrix pipe idles across each of the 8 barriers of
-// a K tile, between the last MFMA issue of one wave group and the first of the other (the s_barrier round trip).  MFMAs touch
-// registers only -- the barrier orders LDS reads against the DMAs into the other stage, and schedules the two groups -- so the
-// trailing MFMAs may follow the barrier: the partner group is released while they still feed the pipe.  Same MFMA order per
-// accumulator: bit-identical.
-#ifndef PG_P6_EARLY
-#define PG_P6_EARLY 0
-#endif
-constexpr int P6_EARLY = PG_P6_EARLY;
+// (Round 4 tried arriving at the barrier that ends an MFMA phase before the phase's last MFMAs were issued: 6-7 % slower,
+// profiles/r04/early_barrier_ab.txt.)
 template <typename T, bool ZERO, int HALF>
 __device__ __forceinline__ void mma24(Acc6& acc, const Frag6<T>& f) {
 #pragma unroll
     for (int i = 0; i < P6_TM; ++i)
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            if (P6_EARLY > 0 && i * 4 + j == 4 * P6_TM - P6_EARLY) raw_barrier();
             if constexpr (ZERO) T::mfma16_init(acc[HALF * P6_TM + i][j], f.b[j], f.a[i]);
             else T::mfma16_acc(acc[HALF * P6_TM + i][j], f.b[j], f.a[i]);
         }
@@ -154,8 +143,8 @@ __device__ __forceinline__ void mma24(Acc6& acc, const Frag6<T>& f) {
 // baseA / baseB: LDS byte addresses of this lane's fragment row (lane & 15 of block 0) in STAGE 0 at k-step 0 (chunk
 // ((lane >> 4) ^ sw) << 4); k-step s reads chunk (4 s + (lane >> 4)) ^ sw = chunk0 ^ (4 s), i.e. address ^ (s << 6) (disjoint
 // bits).  The per-phase addresses are formed by asm (one v_add / v_xor each) so that they are NOT hoisted into live registers.
-#ifdef PIGEON_ABLATIONS
-// tools build: wall-clock ticks (100 MHz) block 0's waves 0 (leader group) and 4 (follower group) spend per K tile (a) in the
+#ifdef PIGEON_PROBES
+// probe build: wall-clock ticks (100 MHz) block 0's waves 0 (leader group) and 4 (follower group) spend per K tile (a) in the
 // `s_waitcnt vmcnt(0)` that waits for the NEXT K tile's operand DMAs and (b) in the barrier right behind it; [grp][0] = (a),
 // [grp][1] = (b), [grp][2] = K tiles counted.  Read / reset with pg_dbg_stall_read (tools/stall_probe.py).
 __device__ unsigned long long pg_dbg_stall[2][4];
@@ -189,7 +178,7 @@ __device__ __forceinline__ void ktile6(Acc6& acc, char* smem, uint32_t baseA, ui
 #pragma unroll
     for (int kk = 0; kk < 4; ++kk) {
         // phase kk = (k-step s = kk >> 1, half = kk & 1)
-#ifdef PIGEON_ABLATIONS
+#ifdef PIGEON_PROBES
         const bool probe = blockIdx.x == 0 && (wave & 3) == 0;
         unsigned long long t0 = 0, t1 = 0, t2 = 0, t3 = 0;
         if (probe) t0 = __builtin_amdgcn_s_memrealtime();
@@ -203,7 +192,7 @@ __device__ __forceinline__ void ktile6(Acc6& acc, char* smem, uint32_t baseA, ui
         if (has_next) {
             if (kk == 0) issue_dma6<0, 5>(c, nxt, wave, voffA, voffW, soff_next);
             if (kk == 1) issue_dma6<5, 5>(c, nxt, wave, voffA, voffW, soff_next);
-#ifdef PIGEON_ABLATIONS
+#ifdef PIGEON_PROBES
             if (kk == 3) {                                   // every wave of block 0: how long for ITS next-tile DMAs, and how often > 200 ns
                 unsigned long long ta = 0;
                 if (blockIdx.x == 0) ta = __builtin_amdgcn_s_memrealtime();
@@ -218,11 +207,11 @@ __device__ __forceinline__ void ktile6(Acc6& acc, char* smem, uint32_t baseA, ui
 #endif
         }
         wait_lgkm0();
-#ifdef PIGEON_ABLATIONS
+#ifdef PIGEON_PROBES
         if (probe) t1 = __builtin_amdgcn_s_memrealtime();
 #endif
         raw_barrier();
-#ifdef PIGEON_ABLATIONS
+#ifdef PIGEON_PROBES
         if (probe) t2 = __builtin_amdgcn_s_memrealtime();
 #endif
         __builtin_amdgcn_s_setprio(1);
@@ -231,11 +220,11 @@ __device__ __forceinline__ void ktile6(Acc6& acc, char* smem, uint32_t baseA, ui
         if (kk == 2) mma24<T, false, 0>(acc, f);
         if (kk == 3) mma24<T, false, 1>(acc, f);
         __builtin_amdgcn_s_setprio(0);
-#ifdef PIGEON_ABLATIONS
+#ifdef PIGEON_PROBES
         if (probe) t3 = __builtin_amdgcn_s_memrealtime();
 #endif
-        if (P6_EARLY == 0) raw_barrier();
-#ifdef PIGEON_ABLATIONS
+        raw_barrier();
+#ifdef PIGEON_PROBES
         if (probe && (threadIdx.x & 63) == 0) {
             const unsigned long long t4 = __builtin_amdgcn_s_memrealtime();
             unsigned long long* d = pg_dbg_phase[wave >> 2];
@@ -262,13 +251,6 @@ __device__ __forceinline__ void pin_bias6(Bias6& b) { asm volatile("" : "+v"(b.l
 template <int EPI> constexpr bool ln6() { return EPI == EPI_QKV_LN || EPI == EPI_GELU_LN; }
 template <int EPI> constexpr bool qkv6() { return EPI == EPI_QKV || EPI == EPI_QKV_LN; }
 
-// LayerNorm-fold epilogues: (rstd, mean*rstd) of the lane's rows of one 32-row slab (rows rr + 8 it), eight registers;
-// the slab's pair is fetched while the previous slab is processed (there is no room for a whole tile's worth: 48 registers)
-struct RowStat6 { u32x2 v[4]; };
-__device__ __forceinline__ void load_rowstat6(RowStat6& rs, __amdgpu_buffer_rsrc_t rrs, int rr, int slab) {
-#pragma unroll
-    for (int it = 0; it < 4; ++it) rs.v[it] = __builtin_amdgcn_raw_buffer_load_b64(rrs, (rr + slab * 32 + it * 8) * 8, 0, 0);
-}
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t rowstat_rsrc6(const GemmArgs& g, int row0) {
     int rvs = g.M - row0; rvs = rvs < 0 ? 0 : (rvs > P6_TM * 32 ? P6_TM * 32 : rvs);
     // wave-uniform, but hipcc clamps with v_med3_i32 (there is no scalar med3): the record count, and with it the whole
@@ -277,67 +259,9 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t rowstat_rsrc6(const GemmArgs& 
     return make_rsrc((const char*)g.ex.rowstat + (int64_t)row0 * 8, (uint32_t)rvs * 8u);
 }
 
-// Round 2's epilogue of the 16-bit outputs (tools build: PIGEON_GEMM_PARK16=0; the product form is epilogue6_park16 below, same
-// bits, -1 % per launch): per wave six 32-row x 64-column fp32 slabs transposed through LDS (gemm_pp.hip
-// pp_epilogue, WIDE geometry: 8 lanes per row, 8 rows per store instruction, 4 instructions per slab).
-// LN: colsum (cs) and the row statistics of slab 0 (rs0) were fetched right after the last MFMA phase.
-template <typename T, int EPI, typename PREFETCH_DMA, typename PREFETCH_BIAS>
-__device__ __forceinline__ void epilogue6(Acc6& acc, const GemmArgs& g, char* smem, int wave, int lane, int row0,
-                                          int col0, const Bias6& bias, const Bias6& cs, const RowStat6& rs0,
-                                          __amdgpu_buffer_rsrc_t rrs, PREFETCH_DMA&& prefetch_dma, PREFETCH_BIAS&& prefetch_bias,
-                                          int dbg_iter = 0) {
-    constexpr int ROWPF = P6_SLAB_ROWF;
-    constexpr bool LN = ln6<EPI>();
-    const int l15 = lane & 15, lq = lane >> 4;               // MFMA side: row inside a 16-row block, column quad
-    float* slab = (float*)(smem + P6_SLAB_OFF + wave * P6_SLAB_BYTES);
-    const int rr = lane >> 3, cc = (lane & 7) * 8;
-    const int col = col0 + cc;
-    const float qsc = (qkv6<EPI>() && col < g.qcols) ? g.qscale : 1.f;
-    int rv = g.M - row0; rv = rv < 0 ? 0 : (rv > P6_TM * 32 ? P6_TM * 32 : rv);
-    rv = __builtin_amdgcn_readfirstlane(rv);   // descriptor stays in SGPRs (hipcc clamps with v_med3_i32, see gemm_pp6.hip rowstat_rsrc6)
-    const uint32_t nbytes = rv > 0 ? (uint32_t)(((int64_t)(rv - 1) * g.ldc + 64) * 2) : 0u;
-    __amdgpu_buffer_rsrc_t ro = make_rsrc((const char*)g.out + ((int64_t)row0 * g.ldc + col0) * 2, nbytes);
-    const int voff = (rr * (int)g.ldc + cc) * 2;
-    int rstep = 8 * (int)g.ldc * 2;                          // bytes between two store iterations
-    int sstep = 32 * (int)g.ldc * 2;                         // bytes between two slabs
-    asm volatile("" : "+s"(rstep), "+s"(sstep));             // not hoisted into 24 SGPRs across the K loop
-    prefetch_dma();
-    RowStat6 rs[2];
-    rs[0] = rs0;
-#pragma unroll
-    for (int i = 0; i < P6_TM; ++i) {
-        if constexpr (LN) { if (i + 1 < P6_TM) load_rowstat6(rs[(i + 1) & 1], rrs, rr, i + 1); }
-#pragma unroll
-        for (int ib = 0; ib < 2; ++ib)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) *(f32x4*)(slab + (ib * 16 + l15) * ROWPF + j * 16 + 4 * lq) = acc[2 * i + ib][j];
-        wave_lds_fence();
-#pragma unroll
-        for (int it = 0; it < 4; ++it) {
-            const int r = it * 8 + rr;
-            f32x4 lo = *(const f32x4*)(slab + r * ROWPF + cc);
-            f32x4 hi = *(const f32x4*)(slab + r * ROWPF + cc + 4);
-            // row offset in the VGPR offset, not the SGPR soffset (hipcc pads no wait states after a >64-bit buffer store
-            // with a register soffset: gemm_pp.hip)
-            const int ooff = voff + (i * sstep + it * rstep);
-            // LN: each scalar through an asm move of its own (hipcc SLP-packs the fmas into v_pk_fma_f32 and drops the op_sel of the
-            // high half of the loaded pair: gemm_pp.hip); the arithmetic itself is gemm_epi.h epi16_finish (packed fp32 forms)
-            float rstd = 0.f, mrs = 0.f;
-            if constexpr (LN) {
-                asm("v_mov_b32 %0, %1" : "=v"(rstd) : "v"(rs[i & 1].v[it][0]));
-                asm("v_mov_b32 %0, %1" : "=v"(mrs) : "v"(rs[i & 1].v[it][1]));
-            }
-            const u32x4 pk = epi16_finish<T, EPI>(lo, hi, bias.lo, bias.hi, cs.lo, cs.hi, rstd, mrs, col0 < g.qcols, qsc);
-            __builtin_amdgcn_raw_buffer_store_b128(pk, ro, ooff, 0, 0);
-        }
-        wave_lds_fence();                                    // slab reads retired before the next slab overwrites it
-        PG_TS(g, dbg_iter, wave, 3 + i);
-        if (i == 0) prefetch_bias();                         // next tile's bias (/ nothing else): 32 registers are free now
-    }
-}
-
 // ---- 16-bit outputs: finish in the accumulator layout, transpose the 16-bit values (product epilogue since the end of round 3) --
-// epilogue6 parks fp32 accumulators and finishes them after the read-back: 768 KB of LDS traffic per tile.  Here the arithmetic
+// Round 2's form (removed; see git history) parked the fp32 accumulators and finished them after the read-back: 768 KB of LDS
+// traffic per tile, 1 % slower per launch.  Here the arithmetic
 // (the same gemm_epi.h epi16_finish on the same values: outputs are bit-identical) runs on the accumulators where they are -- a
 // lane owns row rb * 16 + (lane & 15) and the 4 consecutive columns 16 j + 4 (lane >> 4) .. of each 16 x 16 block -- and only the
 // packed 16-bit results go through the slab: 384 KB per tile, and the read-back feeds the stores directly.  The stores keep the
@@ -380,7 +304,9 @@ __device__ __forceinline__ void epilogue6_park16(Acc6& acc, const GemmArgs& g, c
 #pragma unroll
         for (int ib = 0; ib < 2; ++ib) {
             float rstd = 0.f, mrs = 0.f;
-            if constexpr (LN) {                              // each half through a move of its own (see epilogue6)
+            // LN: each half through an asm move of its own (hipcc SLP-packs the fmas into v_pk_fma_f32 and drops the op_sel of the
+            // high half of the loaded pair: gemm_pp.hip)
+            if constexpr (LN) {
                 asm("v_mov_b32 %0, %1" : "=v"(rstd) : "v"(rs[i & 1].v[ib][0]));
                 asm("v_mov_b32 %0, %1" : "=v"(mrs) : "v"(rs[i & 1].v[ib][1]));
             }
@@ -506,7 +432,7 @@ __device__ __forceinline__ void epilogue6_resid(Acc6& acc, const GemmArgs& g, ch
     }
 }
 
-template <typename T, int EPI, bool PARK>
+template <typename T, int EPI>
 __global__ __launch_bounds__(512) void gemm_pp6_kernel(GemmArgs g) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x;
@@ -526,9 +452,8 @@ __global__ __launch_bounds__(512) void gemm_pp6_kernel(GemmArgs g) {
     const uint32_t baseA = smem0 + (wm * (P6_TM * 32) + l15) * ROWB + xo0;
     const uint32_t baseB = smem0 + P6_W_OFF + (wn * 64 + l15) * ROWB + xo0;
     constexpr bool RSTAT = (EPI == EPI_RESID_STAT);
-    constexpr bool PARK16 = PARK && !RSTAT;                  // 16-bit outputs finished in the accumulator layout (epilogue6_park16)
-    constexpr int BHOFF = RSTAT ? 32 : (PARK16 ? 16 : 4);
-    const int ecc = RSTAT ? (lane & 7) * 4 : (PARK16 ? (lane >> 4) * 4 : (lane & 7) * 8);
+    constexpr int BHOFF = RSTAT ? 32 : 16;                   // 16-bit outputs: finished in the accumulator layout (epilogue6_park16)
+    const int ecc = RSTAT ? (lane & 7) * 4 : (lane >> 4) * 4;
 
     const int nt = g.K / BK;                                 // even, >= 4 (checked on the host)
     const int nblk = gridDim.x;
@@ -544,7 +469,7 @@ __global__ __launch_bounds__(512) void gemm_pp6_kernel(GemmArgs g) {
     // operations of an epilogue, at least 5 x 4 stores (+ the bias / row-statistics loads) are younger than all of them
     constexpr int NST = (P6_TM - 1) * 4;
     bool first = true;
-    int dbg_iter = 0;                                        // tile counter of the tools build's time stamps (dead code otherwise)
+    int dbg_iter = 0;                                        // tile counter of the probe build's time stamps (dead code otherwise)
 
     while (true) {
         Acc6 acc;                                            // not cleared: the first k-step of the tile runs with C = 0
@@ -569,22 +494,17 @@ __global__ __launch_bounds__(512) void gemm_pp6_kernel(GemmArgs g) {
         // registers are dead (after the last MFMA phase); they land under the re-align barrier, the prefetch and slab 0's parking
         const int row0 = c.m0 + wm * (P6_TM * 32), col0 = c.n0 + wn * 64;
         Bias6 cs;
-        RowStat6 rs0;
         Bias6 b23, cs23;
         RowStatP rsp;
         __amdgpu_buffer_rsrc_t rrs = c.ra;                   // placeholder for the plain epilogues (never dereferenced)
-        if constexpr (PARK16) load_bias6<16>(b23, g, col0 + 32 + ecc);
+        if constexpr (!RSTAT) load_bias6<16>(b23, g, col0 + 32 + ecc);
         if constexpr (ln6<EPI>()) {
             cs.lo = *(const f32x4*)(g.ex.colsum + col0 + ecc);
             cs.hi = *(const f32x4*)(g.ex.colsum + col0 + ecc + BHOFF);
             rrs = rowstat_rsrc6(g, row0);
-            if constexpr (PARK16) {
-                cs23.lo = *(const f32x4*)(g.ex.colsum + col0 + 32 + ecc);
-                cs23.hi = *(const f32x4*)(g.ex.colsum + col0 + 48 + ecc);
-                load_rowstat_p(rsp, rrs, l15, 0);
-            } else {
-                load_rowstat6(rs0, rrs, lane >> 3, 0);
-            }
+            cs23.lo = *(const f32x4*)(g.ex.colsum + col0 + 32 + ecc);
+            cs23.hi = *(const f32x4*)(g.ex.colsum + col0 + 48 + ecc);
+            load_rowstat_p(rsp, rrs, l15, 0);
         }
         ResidCtx6 rc;
         XRows6 x0;
@@ -607,8 +527,7 @@ __global__ __launch_bounds__(512) void gemm_pp6_kernel(GemmArgs g) {
         };
         auto prefetch_bias = [&]() { load_bias6<BHOFF>(bias_next, g, c.n0 + wn * 64 + ecc); };
         if constexpr (RSTAT) epilogue6_resid<T>(acc, g, smem, wave, lane, row0, col0, bias, x0, rc, prefetch_dma, prefetch_bias, dbg_iter);
-        else if constexpr (PARK16) epilogue6_park16<T, EPI>(acc, g, smem, wave, lane, row0, col0, bias, b23, cs, cs23, rsp, rrs, prefetch_dma, prefetch_bias, dbg_iter);
-        else epilogue6<T, EPI>(acc, g, smem, wave, lane, row0, col0, bias, cs, rs0, rrs, prefetch_dma, prefetch_bias, dbg_iter);
+        else epilogue6_park16<T, EPI>(acc, g, smem, wave, lane, row0, col0, bias, b23, cs, cs23, rsp, rrs, prefetch_dma, prefetch_bias, dbg_iter);
         PG_TS(g, dbg_iter, wave, 9);
         ++dbg_iter;
         if (!more) break;
@@ -618,10 +537,10 @@ __global__ __launch_bounds__(512) void gemm_pp6_kernel(GemmArgs g) {
     }
 }
 
-template <typename T, int EPI, bool PARK = false>
+template <typename T, int EPI>
 int launch_pp6(const GemmArgs& g, int nblk, hipStream_t s) {
     static bool attr_set = false;
-    auto kfn = gemm_pp6_kernel<T, EPI, PARK>;
+    auto kfn = gemm_pp6_kernel<T, EPI>;
     if (!attr_set) {
         hipError_t e = hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, P6_LDS);
         if (e != hipSuccess) { pg_set_error("gemm_pp6: set LDS attr: %s", hipGetErrorString(e)); return PG_EHIP; }
@@ -629,18 +548,6 @@ int launch_pp6(const GemmArgs& g, int nblk, hipStream_t s) {
     }
     hipLaunchKernelGGL(kfn, dim3(nblk), dim3(512), P6_LDS, s, g);
     return pg_check_launch("gemm_pp6");
-}
-
-// 16-bit epilogues of the 384 x 256 kernel: finished in the accumulator layout, 16-bit slabs (epilogue6_park16).  Tools build:
-// PIGEON_GEMM_PARK16=0 selects round 2's fp32-slab epilogue6 (A/B arm; same bits).
-bool park16_enabled() {
-#ifdef PIGEON_ABLATIONS
-    static int v = -1;
-    if (v < 0) { const char* e = getenv("PIGEON_GEMM_PARK16"); v = e ? (atoi(e) != 0) : 1; }
-    return v != 0;
-#else
-    return true;
-#endif
 }
 
 }  // namespace
@@ -673,24 +580,17 @@ int pg_gemm_pp6_launch(int dtype, GemmArgs g, int epi, hipStream_t s) {
     const int nblk = g.ntiles < cap ? g.ntiles : cap;
     if ((epi == EPI_QKV_LN || epi == EPI_GELU_LN) && (!g.ex.colsum || !g.ex.rowstat)) { pg_set_error("gemm_pp6: LN epilogue needs colsum / rowstat"); return PG_EINVAL; }
     if (epi == EPI_RESID_STAT && (!g.ex.x16 || !g.ex.statpart || g.ex.ldx != g.ldc || !g.bias)) { pg_set_error("gemm_pp6: EPI_RESID_STAT needs bias, x16 / statpart and ldx == ldc"); return PG_EINVAL; }
-    const bool park = park16_enabled();
-#ifdef PIGEON_ABLATIONS
-#define P6_OLD16(TT, E) launch_pp6<TT, E, false>(g, nblk, s)
-#else
-#define P6_OLD16(TT, E) launch_pp6<TT, E, true>(g, nblk, s)      /* the product library carries the production epilogue only */
-#endif
 #define P6_DISPATCH(TT)                                                          \
     switch (epi) {                                                               \
-        case EPI_QKV: return park ? launch_pp6<TT, EPI_QKV, true>(g, nblk, s) : P6_OLD16(TT, EPI_QKV);                \
-        case EPI_GELU: return park ? launch_pp6<TT, EPI_GELU, true>(g, nblk, s) : P6_OLD16(TT, EPI_GELU);              \
-        case EPI_QKV_LN: return park ? launch_pp6<TT, EPI_QKV_LN, true>(g, nblk, s) : P6_OLD16(TT, EPI_QKV_LN);          \
+        case EPI_QKV: return launch_pp6<TT, EPI_QKV>(g, nblk, s);                \
+        case EPI_GELU: return launch_pp6<TT, EPI_GELU>(g, nblk, s);              \
+        case EPI_QKV_LN: return launch_pp6<TT, EPI_QKV_LN>(g, nblk, s);          \
         case EPI_RESID_STAT: return launch_pp6<TT, EPI_RESID_STAT>(g, nblk, s);  \
-        default: return park ? launch_pp6<TT, EPI_GELU_LN, true>(g, nblk, s) : P6_OLD16(TT, EPI_GELU_LN);                 \
+        default: return launch_pp6<TT, EPI_GELU_LN>(g, nblk, s);                 \
     }
     if (dtype == PG_DTYPE_F16) { P6_DISPATCH(T_F16) }
     if (dtype == PG_DTYPE_BF16) { P6_DISPATCH(T_BF16) }
 #undef P6_DISPATCH
-#undef P6_OLD16
     pg_set_error("gemm_pp6: operand dtype must be PG_DTYPE_F16 or PG_DTYPE_BF16 (got %d)", dtype);
     return PG_EINVAL;
 }

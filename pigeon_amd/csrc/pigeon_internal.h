@@ -39,8 +39,8 @@ unsigned long long pg_tune_epoch();             // bumped by every pg_tune_gemm_
 // the exact tier's form of one GEMM (vit.hip precise_gemm): 0 = gemm_mid.hip, S >= 1 = the 256 x 256 persistent kernel in S K-parts
 int pg_gemm_precise_route(int M, int N, int Ktot, bool resid, const int* cand, int ncand);
 
-// GEMM variants (env PIGEON_GEMM_VARIANT, the `variant` argument of pg_op_gemm16*): the numbers are ABI.  30..49 are the schedules
-// and rasters of the 256 x 256 persistent kernel (33 and 36 in the product library, the rest in the tools build).
+// GEMM variants (env PIGEON_GEMM_VARIANT, the `variant` argument of pg_op_gemm16*): the numbers are ABI.  33 and 36 are the two
+// rasters of the 256 x 256 persistent kernel (N-fastest / 8 x 4 super-tiles); the other numbers below 50 are retired and refused.
 enum { PG_GEMM_V_ONE_TILE = 8, PG_GEMM_V_PP = 36, PG_GEMM_V_PP6 = 56, PG_GEMM_V_TAIL = 70, PG_GEMM_V_MID = 71 };
 // the kernels of a GEMM plan (pg_gemm_plan's `kernel` / `rest` codes)
 enum PgGemmKernel { PG_GK_NONE = -1, PG_GK_PP6 = 0, PG_GK_PP = 1, PG_GK_MID = 2, PG_GK_TAIL = 3, PG_GK_ONE_TILE = 4 };

@@ -109,9 +109,6 @@ struct pg_vit {
     double prof_ms[PG_PROF_CLASSES] = {0};
 };
 
-#ifndef PG_DEFAULT_GEMM_STAGGER
-#define PG_DEFAULT_GEMM_STAGGER 0.0f
-#endif
 static const float kQScale = 0.125f * 1.4426950408889634f;    // head_dim^-0.5 * log2(e)
 
 static std::string canon(const char* name) {

@@ -526,3 +526,4 @@ def test_gemm_plan_pins_the_tail_split():
     assert L.pg_gemm_plan(64, _lib.EPI_QKV, 577, 3072, 1024, C.byref(k), C.byref(rows), C.byref(rest)) == -1     # PG_EINVAL
     assert L.pg_gemm_plan(8, _lib.EPI_RESID_STAT, 577, 1024, 1024, C.byref(k), C.byref(rows), C.byref(rest)) == -1     # PG_EINVAL
     assert L.pg_gemm_plan(70, _lib.EPI_PATCH, 577, 1024, 640, C.byref(k), C.byref(rows), C.byref(rest)) == -1     # PG_EINVAL
+    assert L.pg_gemm_plan(31, _lib.EPI_QKV, 577, 3072, 1024, C.byref(k), C.byref(rows), C.byref(rest)) == -1     # retired schedule

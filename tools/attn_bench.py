@@ -1,5 +1,5 @@
-"""Time the attention kernel (variant from env PIGEON_ATTN_VARIANT) and check it against an fp32 reference.
-   PIGEON_ATTN_VARIANT=2 python tools/attn_bench.py --images 512"""
+"""Time the attention kernel and check it against an fp32 reference.
+   python tools/attn_bench.py --images 512"""
 import argparse, os, sys
 import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -13,7 +13,6 @@ def main():
     ap.add_argument("--iters", type=int, default=5)
     ap.add_argument("--rounds", type=int, default=5)
     args = ap.parse_args()
-    var = os.environ.get("PIGEON_ATTN_VARIANT", "default")
     g = torch.Generator().manual_seed(21)
     n = 2
     qkv = torch.randn((n * 577, 3072), generator=g)
@@ -28,7 +27,7 @@ def main():
     err = ((out - ref).norm() / ref.norm()).item()
     last = torch.tensor([576, 2 * 577 - 1])
     err_last = ((out[last] - ref[last]).norm() / ref[last].norm()).item()
-    print(f"ATTN variant {var}: rel err vs fp32 {err:.2e} (token 576's rows: {err_last:.2e})", flush=True)
+    print(f"ATTN: rel err vs fp32 {err:.2e} (token 576's rows: {err_last:.2e})", flush=True)
     n = args.images
     big = torch.randn((n * 577, 3072), generator=g).to(torch.float16).cuda()
     big[:, :1024] *= 0.18
@@ -45,7 +44,7 @@ def main():
         ts.append(a.elapsed_time(b) / args.iters)
     ts.sort()
     fl = 4.0 * 577 * 577 * 64 * 16 * n
-    print(f"ATTN variant {var} n={n}: median {ts[len(ts)//2]:.3f} ms {fl/(ts[len(ts)//2]*1e-3)/1e12:6.1f} TF/s  best {ts[0]:.3f} ms", flush=True)
+    print(f"ATTN n={n}: median {ts[len(ts)//2]:.3f} ms {fl/(ts[len(ts)//2]*1e-3)/1e12:6.1f} TF/s  best {ts[0]:.3f} ms", flush=True)
 
 
 if __name__ == "__main__":

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Is a persistent GEMM's residual epilogue limited per CU or by something the CUs share (HBM, fabric)?  Cap the persistent grid
-# (PIGEON_GEMM_BLOCKS) and read a tile's epilogue time from the in-kernel stamps (tools build): with 64 of 256 CUs running, each
+# (PIGEON_GEMM_BLOCKS) and read a tile's epilogue time from the in-kernel stamps (probe build): with 64 of 256 CUs running, each
 # has 4x the HBM bandwidth to itself.  Usage (GPU box): bash tools/epi_cap_sweep.sh > gpurun_out/epi_cap_sweep.txt
 cd "$(dirname "$0")/.."
 export PIGEON_HIP_LIB=$PWD/pigeon_amd/libpigeon_hip_dev.so EPI_TIMELINE_SUMMARY_ONLY=1

@@ -1,6 +1,6 @@
 """What does each fused epilogue of the persistent 256x256 GEMM cost?  Same mainloop (variant 36), the out-projection and fc2
 shapes (295 424 rows), epilogues: 16-bit store (+bias), fp32 store, fp32 residual read-modify-write, the same + 16-bit copy +
-row statistics (LayerNorm fold).  Timing only.   python tools/epi_probe.py [variants, e.g. 36,64]"""
+row statistics (LayerNorm fold).  Timing only.   python tools/epi_probe.py [variants, e.g. 36,33]"""
 import os, sys
 import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))

@@ -1,4 +1,4 @@
-"""Where does a persistent GEMM block spend a tile period?  Tools build only (python -m pigeon_amd.build --dev):
+"""Where does a persistent GEMM block spend a tile period?  Probe build only (python -m pigeon_amd.build --dev):
 PG_TS stamps the 100 MHz wall clock inside gemm_pp.hip / gemm_pp6.hip (blocks 0 and 100, all 8 waves, first 16 tiles):
 slot 0 tile start (B_0 passed), 1 mainloop left, 2 re-aligned, 3.. slab i done, 9 epilogue done.
 

@@ -1,5 +1,5 @@
 """Run one GEMM shape repeatedly (for rocprofv3 / quick A/B timing).
-   python tools/gemm_prof.py --shape qkv --variant 1 --iters 10 [--dtype f16] [--time]"""
+   python tools/gemm_prof.py --shape qkv --variants 8 --iters 10 [--dtype f16] [--time]"""
 import argparse, os, sys
 import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -12,7 +12,7 @@ SHAPES = {"qkv": (3072, 1024, _lib.EPI_QKV), "out": (1024, 1024, _lib.EPI_RESID)
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--shape", default="qkv")
-    ap.add_argument("--variants", default="1")
+    ap.add_argument("--variants", default="8")
     ap.add_argument("--iters", type=int, default=5)
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--images", type=int, default=256)

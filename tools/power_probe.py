@@ -2,8 +2,7 @@
 
 Loops ONE kernel for ~1.5 s at a time while a thread samples `rocm-smi --showpower --showclocks`, and prints the
 median power / sclk of the samples taken inside the loop next to the kernel's time per launch.  Kernels: the four
-GEMM shapes of a layer (product variant 36), the timing-only GEMM ablations (40 no DMA, 41 every DMA hits operand
-panel 0 = L2 resident, 43 MFMA + barriers only), attention, LayerNorm.
+GEMM shapes of a layer (variant 36), attention, LayerNorm.
 
     python tools/power_probe.py [--images 512] [--seconds 1.5]
 """
@@ -88,10 +87,8 @@ def main():
         W = (torch.randn((N, K), generator=g) * 0.03).to(dt).to(dev)
         bias = torch.zeros(N, device=dev)
         out = torch.zeros((M, N), dtype=dt if epi in (L.EPI_QKV, L.EPI_GELU) else torch.float32, device=dev)
-        variants = (36, 41, 40, 43) if name in ("fc1", "fc2") else (36,)
-        for v in variants:
-            probe(f"gemm {name} variant {v}", lambda: hip_ops.gemm16(A, W, bias, out, epi, qscale=0.18, qcols=1024, variant=v),
-                  args.seconds, sm, 2.0 * M * N * K)
+        probe(f"gemm {name} variant 36", lambda: hip_ops.gemm16(A, W, bias, out, epi, qscale=0.18, qcols=1024, variant=36),
+              args.seconds, sm, 2.0 * M * N * K)
         del A, W, out
     qkv = torch.randn((M, 3072), generator=g).to(dt).to(dev)
     qkv[:, :1024] *= 0.18

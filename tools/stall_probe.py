@@ -1,4 +1,4 @@
-"""Where does a wave of the persistent 384 x 256 GEMM spend a K tile?  Tools build only (python -m pigeon_amd.build --dev):
+"""Where does a wave of the persistent 384 x 256 GEMM spend a K tile?  Probe build only (python -m pigeon_amd.build --dev):
 gemm_pp6.hip accumulates, for waves 0 (leader group) and 4 (follower group) of block 0, the wall-clock ticks (100 MHz) of the four
 sections of every ping-pong phase: LOAD (fragment ds_reads, the next K tile's DMA issue, the lgkmcnt / vmcnt waits), the barrier in
 front of the MFMAs, the 24 MFMAs, the barrier behind them.
