@@ -301,8 +301,11 @@ def test_gemm_resid_stat_on_384_row_tiles_bit_identical(env):
         for name, a, b in zip(("X", "x16", "statpart"), ref, got):
             assert torch.equal(a, b), (key, name)
     # and the values themselves: X = X0 + A W^T + b on the rounded operands
-    want = X0[:2048] + A[:2048].float() @ W.float().T + bias
-    assert torch.allclose(ref[0][:2048], want, rtol=2e-3, atol=2e-3)
+    # (every row, against fp64: the per-element bound of tests/_exactref.py AND the 2e-3 this test used to ask of its first 2048 rows)
+    import _exactref as xr
+    case = xr.GemmCase(xr.EPI_RESID_STAT, M, N, K, torch.float16, A, W, bias=bias, X0=X0[:M], exact_inputs=False)
+    found = xr.compare_gemm(case, dict(out=ref[0], x16=ref[1], part=ref[2]), guard=False, also_within=(2e-3, 2e-3))
+    assert not found, "\n".join(found)
 
 
 def test_gemm_identity_is_not_transposed(env):
