@@ -37,10 +37,11 @@ extern "C" {
 #define PG_DTYPE_F16     2
 #define PG_DTYPE_F64     3
 
-#define PG_ABI_VERSION   6   /* 2: pg_vit_cfg.precise, pg_vit_forward_precise, pg_head_margin (round 4); 3: pg_head_certainty, pg_refine_forward_ex,
+#define PG_ABI_VERSION   7   /* 2: pg_vit_cfg.precise, pg_vit_forward_precise, pg_head_margin (round 4); 3: pg_head_certainty, pg_refine_forward_ex,
                               * pg_refine_certainty, pg_tune_gemm_raster (round 5); 4: the deferred exact tier -- pg_requeue_append,
                               * pg_rows_to_slots, pg_requeue_take, pg_scatter_rows, pg_head_wstats (round 6); 5: pg_embedding_debias (round 6);
-                              * 6: pg_gemm_plan replaces pg_gemm_route */
+                              * 6: pg_gemm_plan replaces pg_gemm_route;
+                              * 7: pg_vit_precise_plan, pg_op_x3_im2col, pg_op_sum_parts, pg_op_preln, pg_op_attention_x3 */
 
 const char* pg_last_error(void);
 int pg_abi_version(void);
@@ -103,6 +104,15 @@ int pg_vit_forward_hidden(pg_vit* h, const void* pixels, int pix_dtype, int n_im
  * image.  Needs cfg.precise at creation.  Workspace from pg_vit_precise_workspace_bytes (98 KB per token row, equal chunks of at most 128 images).
  * hidden_out (DEVICE (n_images,577,1024) fp32, may be NULL) receives last_hidden_state. */
 int pg_vit_precise_workspace_bytes(const pg_vit* h, int n_images, size_t* bytes);
+/* What pg_vit_forward_precise does with a batch of n_images (>= 1) under the current knobs.  Host arithmetic only: no launch, no device
+ * work; pg_vit_forward_precise runs what this reports (one function decides both).
+ *   out[0..3]  the form of the layer's QKV / out-projection / fc1 / fc2 GEMM in the first (largest) internal pass: 0 = csrc/gemm_mid.hip,
+ *              1 = one launch of the 256 x 256 persistent kernel, S > 1 = S K-parts in one launch + the fixed-order sum of the parts
+ *   out[4]     1 = fc1's epilogue writes the QuickGELU triple (only where out[2] == 1 and pg_tune_exact_fusion is on)
+ *   out[5]     1 = the attention writes the triple the out-projection reads
+ *   out[6]     images in the largest internal pass: n_images up to 128; above, ceil(n_images / out[7])
+ *   out[7]     internal passes: ceil(n_images / 128); the first n_images - out[7] * (out[6] - 1) take out[6] images, the others one fewer */
+int pg_vit_precise_plan(int n_images, int32_t out[8]);
 int pg_vit_forward_precise(pg_vit* h, const void* pixels, int pix_dtype, int n_images, float* emb_out, float* hidden_out,
                            void* workspace, size_t workspace_bytes, void* stream);
 /* hipGraph of the encoder (round 4).  pg_vit_forward replays the ~250 launches between im2col and the token mean -- they touch only
@@ -454,7 +464,18 @@ int pg_op_cast_f32(const float* x, void* y, int out_dtype, int64_t n, void* stre
  * through pg_op_gemm16 (epi 2 / 3 / 4, K = 3 * cols) it yields the fp32-grade product.
  *   pg_op_x3_split      x fp32 (rows,cols) -> triple (rows, 3 cols); gelu != 0: through QuickGELU first (expf, IEEE division)
  *   pg_op_x3_layernorm  LayerNorm(x fp32 (rows,1024)) -> triple (rows, 3072)
- *   pg_op_attention_f32 fused QKV fp32 (n_images*577, 3072), Q NOT pre-scaled -> softmax(q k^T / 8) v, fp32 (n_images*577, 1024) */
+ *   pg_op_attention_f32 fused QKV fp32 (n_images*577, 3072), Q NOT pre-scaled -> softmax(q k^T / 8) v, fp32 (n_images*577, 1024)
+ *   pg_op_attention_x3  the same attention with the output written as the triple (n_images*577, 3072) the out-projection reads: what
+ *                       pg_op_x3_split makes of pg_op_attention_f32's rows, bit for bit.  PG_ESTATE with pg_tune_exact_attention(1).
+ *   pg_op_x3_im2col     fp32/fp16/bf16 NCHW pixels -> the triple of the patch matrix (n_images*576, 3*640): segment s holds its 588 values
+ *                       at columns [640 s, 640 s + 588), k = c*196+ky*14+kx, the 52 pad columns of every segment zero
+ *   pg_op_sum_parts     dst[i] = (resid ? dst[i] : 0) + ((p0[i] + p1[i]) + p2[i] ...), i < n, part k at parts + k*part_elems; n and
+ *                       part_elems multiples of 4, n <= part_elems, 1 <= S <= 8 */
+/* Class token + position + pre-LayerNorm in place on the fp32 residual stream x (rows,1024): a row with row % 577 == 0 becomes
+ * LN(cls + pos0) whatever x held there, every other row LN(x row); pos0 = row 0 of the position embedding.  With x16 / rowstat (both
+ * or neither): also the 16-bit copy (x16_dtype) of the NEW row and its (rstd, mean*rstd), as pg_op_rowstat_cast would give. */
+int pg_op_preln(float* x, const float* cls, const float* pos0, const float* gamma, const float* beta, int64_t rows, float eps,
+                void* x16, int x16_dtype, float* rowstat, void* stream);
 /* S independent products in ONE persistent launch (the exact mode's K-split GEMMs, csrc/vit.hip precise_gemm): part p computes
  * parts[p] (M,N) fp32 = A[:, p*Kp:(p+1)*Kp] x W[:, p*Kp:(p+1)*Kp]^T (+ bias for p = 0); A (M, >= S*Kp) and W (N, >= S*Kp) 16-bit with
  * leading dimensions lda / ldw.  N % 256 == 0, Kp % 128 == 0, 1 <= S <= 8.  Each part is bit-identical to pg_op_gemm16_ld on its slice. */
@@ -463,6 +484,9 @@ int pg_op_gemm16_parts(int dtype, const void* A, int64_t lda, const void* W, int
 int pg_op_x3_split(const float* x, void* y3, int64_t rows, int cols, int gelu, void* stream);
 int pg_op_x3_layernorm(const float* x, const float* gamma, const float* beta, void* y3, int64_t rows, float eps, void* stream);
 int pg_op_attention_f32(const float* qkv, float* out, int n_images, void* stream);
+int pg_op_attention_x3(const float* qkv, void* out3, int n_images, void* stream);
+int pg_op_x3_im2col(const void* pixels, int pix_dtype, void* out3, int n_images, void* stream);
+int pg_op_sum_parts(const float* parts, int S, int64_t part_elems, float* dst, int64_t n, int resid, void* stream);
 
 #ifdef __cplusplus
 }

@@ -59,10 +59,15 @@ def num_layers(sd) -> int:
 
 @torch.no_grad()
 def vit_last_hidden_state(sd: Dict[str, torch.Tensor], pixels: torch.Tensor,
-                          collect: Optional[dict] = None) -> torch.Tensor:
-    """(N,3,336,336) fp32 -> (N,577,1024) fp32, HF CLIPVisionModel.last_hidden_state."""
+                          collect: Optional[dict] = None, dtype: torch.dtype = torch.float32) -> torch.Tensor:
+    """(N,3,336,336) fp32 -> (N,577,1024) fp32, HF CLIPVisionModel.last_hidden_state.
+
+    dtype=torch.float64: the same network in double precision, on the device the pixels live on (the parameters are converted and
+    moved there) -- the reference of the exact tier's per-element tests.  The default is the fp32 restatement the goldens pin."""
     sd = _strip(sd)
-    x = pixels.to(torch.float32)
+    if dtype != torch.float32:
+        sd = {k: v.to(device=pixels.device, dtype=dtype) for k, v in sd.items() if torch.is_tensor(v) and v.is_floating_point()}
+    x = pixels.to(dtype)
     N = x.shape[0]
     # CLIPVisionEmbeddings.forward (modeling_clip.py:202-218)
     pe = F.conv2d(x, sd["embeddings.patch_embedding.weight"], bias=None, stride=14)
@@ -88,7 +93,7 @@ def vit_last_hidden_state(sd: Dict[str, torch.Tensor], pixels: torch.Tensor,
         k = k.view(N, TOKENS, HEADS, HEAD_DIM).transpose(1, 2)
         v = v.view(N, TOKENS, HEADS, HEAD_DIM).transpose(1, 2)
         w = torch.matmul(q, k.transpose(-1, -2)) * scale
-        w = F.softmax(w, dim=-1, dtype=torch.float32)
+        w = F.softmax(w, dim=-1, dtype=dtype)
         o = torch.matmul(w, v).transpose(1, 2).reshape(N, TOKENS, HIDDEN)
         o = F.linear(o, sd[p + "self_attn.out_proj.weight"], sd[p + "self_attn.out_proj.bias"])
         h = r + o

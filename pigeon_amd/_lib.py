@@ -107,6 +107,11 @@ SIGNATURES = {
     "pg_op_x3_split": (_I, [_P, _P, _I64, _I, _I, _P]),
     "pg_op_x3_layernorm": (_I, [_P, _P, _P, _P, _I64, _F, _P]),
     "pg_op_attention_f32": (_I, [_P, _P, _I, _P]),
+    "pg_op_attention_x3": (_I, [_P, _P, _I, _P]),
+    "pg_op_x3_im2col": (_I, [_P, _I, _P, _I, _P]),
+    "pg_op_sum_parts": (_I, [_P, _I, _I64, _P, _I64, _I, _P]),
+    "pg_op_preln": (_I, [_P, _P, _P, _P, _P, _I64, _F, _P, _I, _P, _P]),
+    "pg_vit_precise_plan": (_I, [_I, C.POINTER(C.c_int32)]),
 }
 
 _lib = None

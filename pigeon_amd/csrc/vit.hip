@@ -652,11 +652,9 @@ extern "C" int pg_vit_precise_workspace_bytes(const pg_vit* h, int n_images, siz
 // that run as ONE persistent launch (PgGemmExtra::parts: S x tilesM x tilesN tiles on the 256 CUs): part p multiplies columns
 // [p Kp, (p + 1) Kp) of the triple operands into the fp32 partial buffer p (the bias rides in part 0); then
 // dst = (resid ? dst : 0) + sum of the parts, in part order (sum_parts_kernel).
-// Which of the three forms a shape takes: pg_gemm_precise_route (gemm_plan.hip), 0 = gemm_mid.hip, S >= 1 = the persistent kernel in S parts.
-static int precise_gemm(pg_vit* h, const uint16_t* A3, int64_t lda, const uint16_t* W3, int64_t ldw, const float* bias, float* parts,
-                        float* dst, bool resid, int M, int N, int Ktot, const int* cand, int ncand, hipStream_t s) {
-    (void)h;
-    const int S = pg_gemm_precise_route(M, N, Ktot, resid, cand, ncand);
+// Which of the three forms a shape takes (S): precise_plan below, 0 = gemm_mid.hip, S >= 1 = the persistent kernel in S parts.
+static int precise_gemm(const uint16_t* A3, int64_t lda, const uint16_t* W3, int64_t ldw, const float* bias, float* parts,
+                        float* dst, bool resid, int M, int N, int Ktot, int S, hipStream_t s) {
     if (S == 0)
         return pg_gemm_launch(PG_DTYPE_F16, A3, lda, W3, ldw, bias, dst, N, M, N, Ktot, resid ? EPI_RESID : EPI_F32, 1.f, 0, nullptr, PG_GEMM_V_MID, s);
     if (S == 1)
@@ -684,6 +682,44 @@ static bool exact_fusion_on() {
     return g_exact_fusion != 0;
 }
 
+// The form of one internal pass of n images under the current knobs: the route of each of the layer's four weight GEMMs
+// (pg_gemm_precise_route: 0 = gemm_mid.hip, 1 = one persistent launch, S > 1 = S K-parts + sum_parts_kernel) and which of the two
+// activation splits ride in their producers.  Host arithmetic only.  The ONE place that decides it: vit_precise_chunk runs what this
+// returns, pg_vit_precise_plan exports it to the tests.
+struct PrecisePlan { int qkv, out, fc1, fc2; bool fuse_fc1, attn_x3; };
+static PrecisePlan precise_plan(int n) {
+    const int M = n * VIT_TOKENS, D = VIT_HIDDEN, F = VIT_MLP;
+    static const int S3[2] = {1, 3}, S6[4] = {1, 2, 3, 6};    // K-part counts precise_parts may choose from (K' = 3072 / 12288)
+    static const int S2[2] = {1, 2}, S4[3] = {1, 2, 4};       // ... with two products (K' = 2048 / 8192)
+    const int np = g_exact_products;                          // partial products per weight GEMM (3; 2: pg_tune_exact_products)
+    const int* c1 = np == 3 ? S3 : S2; const int* c2 = np == 3 ? S6 : S4; const int n2 = np == 3 ? 4 : 3;
+    const bool fuse = exact_fusion_on();
+    PrecisePlan p;
+    p.qkv = pg_gemm_precise_route(M, 3 * D, np * D, false, c1, 2);
+    p.out = pg_gemm_precise_route(M, D, np * D, true, c1, 2);
+    p.fc1 = pg_gemm_precise_route(M, F, np * D, false, c1, 2);
+    p.fc2 = pg_gemm_precise_route(M, D, np * F, true, c2, n2);
+    p.fuse_fc1 = fuse && p.fc1 == 1;                          // one persistent launch: the epilogue can finish the job
+    p.attn_x3 = fuse && pg_attention_x3out_available();
+    return p;
+}
+// A batch above PG_PRECISE_CHUNK runs as `count` internal passes of sizes equal to within one image (130 images: 65 + 65, not
+// 128 + 2 -- a two-image pass costs as much as a sixteen-image one): the first n - count (big - 1) passes take `big` images, the others big - 1.
+static void precise_chunks(int n_images, int* big, int* count) {
+    *count = (n_images + PG_PRECISE_CHUNK - 1) / PG_PRECISE_CHUNK;
+    if (*count < 1) *count = 1;
+    *big = (n_images + *count - 1) / *count;
+}
+extern "C" int pg_vit_precise_plan(int n_images, int32_t out[8]) {
+    if (n_images < 1 || n_images > (1 << 20) || !out) { pg_set_error("vit_precise_plan: bad argument"); return PG_EINVAL; }
+    int big = 0, count = 0;
+    precise_chunks(n_images, &big, &count);
+    const PrecisePlan p = precise_plan(big);
+    out[0] = p.qkv; out[1] = p.out; out[2] = p.fc1; out[3] = p.fc2;
+    out[4] = p.fuse_fc1 ? 1 : 0; out[5] = p.attn_x3 ? 1 : 0; out[6] = big; out[7] = count;
+    return PG_OK;
+}
+
 static int vit_precise_chunk(pg_vit* h, const void* pixels, int pix_dtype, int n, float* emb_out, float* hidden_out, char* ws,
                              hipStream_t s) {
     const int64_t M = (int64_t)n * VIT_TOKENS;
@@ -696,12 +732,8 @@ static int vit_precise_chunk(pg_vit* h, const void* pixels, int pix_dtype, int n
     float* PP = (float*)((char*)G3 + align_up((size_t)M * 3 * F * 2, 256));     // K-split partial products of one GEMM
     const float eps = h->cfg.ln_eps;
     const int dt = PG_DTYPE_F16, V = PG_GEMM_V_PP;            // the 256 x 256 persistent kernel takes every epilogue used here
-    static const int S3[2] = {1, 3}, S6[4] = {1, 2, 3, 6};    // K-part counts precise_parts may choose from (K' = 3072 / 12288)
-    static const int S2[2] = {1, 2}, S4[3] = {1, 2, 4};       // ... with two products (K' = 2048 / 8192)
     const int np = g_exact_products;                          // partial products per weight GEMM (3; 2: pg_tune_exact_products)
-    const int* c1 = np == 3 ? S3 : S2; const int* c2 = np == 3 ? S6 : S4; const int n2 = np == 3 ? 4 : 3;
-    const bool fuse = exact_fusion_on();
-    const bool fuse_fc1 = fuse && pg_gemm_precise_route((int)M, F, np * D, false, c1, 2) == 1;    // one persistent launch: the epilogue can finish the job
+    const PrecisePlan plan = precise_plan(n);
     RC(pg_x3_im2col_launch(pixels, pix_dtype, G3, n, s));
     RC(pg_gemm_launch(dt, G3, 3 * VIT_PATCH_KPAD, h->wpatch3, 3 * VIT_PATCH_KPAD, nullptr, X, D, n * VIT_PATCHES, D, np * VIT_PATCH_KPAD,
                       EPI_PATCH, 1.f, 0, h->pos, V, s));
@@ -709,22 +741,22 @@ static int vit_precise_chunk(pg_vit* h, const void* pixels, int pix_dtype, int n
     for (int l = 0; l < h->cfg.layers; ++l) {
         const LayerW& L = h->layers[l];
         RC(pg_x3_ln_launch(X, L.ln1g, L.ln1b, T3, M, eps, s));
-        RC(precise_gemm(h, T3, 3 * D, L.wqkv3, 3 * D, L.bqkv_raw, PP, Fb, false, (int)M, 3 * D, np * D, c1, 2, s));
-        if (fuse && pg_attention_x3out_available()) {
+        RC(precise_gemm(T3, 3 * D, L.wqkv3, 3 * D, L.bqkv_raw, PP, Fb, false, (int)M, 3 * D, np * D, plan.qkv, s));
+        if (plan.attn_x3) {
             RC(pg_attention_x3out_launch(Fb, T3, n, s));         // (T3's LayerNorm triple is dead: the QKV GEMM has consumed it)
         } else {
             RC(pg_attention_f32_launch(Fb, O, n, s));
             RC(pg_x3_split_launch(O, T3, M, D, 0, s));
         }
-        RC(precise_gemm(h, T3, 3 * D, L.wo3, 3 * D, L.bo, PP, X, true, (int)M, D, np * D, c1, 2, s));
+        RC(precise_gemm(T3, 3 * D, L.wo3, 3 * D, L.bo, PP, X, true, (int)M, D, np * D, plan.out, s));
         RC(pg_x3_ln_launch(X, L.ln2g, L.ln2b, T3, M, eps, s));
-        if (fuse_fc1) {
+        if (plan.fuse_fc1) {
             RC(pg_gemm_launch(dt, T3, 3 * D, L.w13, 3 * D, L.b1_raw, G3, 3 * F, (int)M, F, np * D, EPI_GELU_X3, 1.f, 0, nullptr, V, s));
         } else {
-            RC(precise_gemm(h, T3, 3 * D, L.w13, 3 * D, L.b1_raw, PP, Fb, false, (int)M, F, np * D, c1, 2, s));
+            RC(precise_gemm(T3, 3 * D, L.w13, 3 * D, L.b1_raw, PP, Fb, false, (int)M, F, np * D, plan.fc1, s));
             RC(pg_x3_split_launch(Fb, G3, M, F, 1, s));
         }
-        RC(precise_gemm(h, G3, 3 * F, L.w23, 3 * F, L.b2, PP, X, true, (int)M, D, np * F, c2, n2, s));
+        RC(precise_gemm(G3, 3 * F, L.w23, 3 * F, L.b2, PP, X, true, (int)M, D, np * F, plan.fc2, s));
     }
     RC(pg_token_mean_launch(X, emb_out, n, s));
     if (hidden_out) PG_HIP(hipMemcpyAsync(hidden_out, X, (size_t)M * D * 4, hipMemcpyDeviceToDevice, s));
@@ -746,13 +778,13 @@ extern "C" int pg_vit_forward_precise(pg_vit* h, const void* pixels, int pix_dty
     if (((uintptr_t)workspace & 255) != 0) { pg_set_error("vit_forward_precise: workspace must be 256-byte aligned"); return PG_EINVAL; }
     const size_t esz = pix_dtype == PG_DTYPE_F32 ? 4 : 2;
     const size_t img_elems = (size_t)3 * VIT_IMG * VIT_IMG;
-    // equal chunks (130 images: 65 + 65, not 128 + 2 -- a two-image pass costs as much as a sixteen-image one)
-    const int nchunks = (n_images + PG_PRECISE_CHUNK - 1) / PG_PRECISE_CHUNK;
-    const int per = (n_images + nchunks - 1) / nchunks;
-    for (int s0 = 0; s0 < n_images; s0 += per) {
-        const int n = (n_images - s0) < per ? (n_images - s0) : per;
+    int big = 0, nchunks = 0;
+    precise_chunks(n_images, &big, &nchunks);
+    for (int c = 0, s0 = 0; c < nchunks; ++c) {
+        const int n = big - (c < n_images - nchunks * (big - 1) ? 0 : 1);
         RC(vit_precise_chunk(h, (const char*)pixels + (size_t)s0 * img_elems * esz, pix_dtype, n, emb_out + (size_t)s0 * VIT_HIDDEN,
                              hidden_out ? hidden_out + (size_t)s0 * VIT_TOKENS * VIT_HIDDEN : nullptr, (char*)workspace, (hipStream_t)stream));
+        s0 += n;
     }
     return PG_OK;
 }
@@ -936,4 +968,23 @@ extern "C" int pg_op_x3_layernorm(const float* x, const float* gamma, const floa
 extern "C" int pg_op_attention_f32(const float* qkv, float* out, int n_images, void* stream) {
     if (!qkv || !out) { pg_set_error("op_attention_f32: null argument"); return PG_EINVAL; }
     return pg_attention_f32_launch(qkv, out, n_images, (hipStream_t)stream);
+}
+extern "C" int pg_op_x3_im2col(const void* pixels, int pix_dtype, void* out3, int n_images, void* stream) {
+    if (!pixels || !out3 || n_images < 0) { pg_set_error("op_x3_im2col: bad argument"); return PG_EINVAL; }
+    return pg_x3_im2col_launch(pixels, pix_dtype, out3, n_images, (hipStream_t)stream);
+}
+extern "C" int pg_op_sum_parts(const float* parts, int S, int64_t part_elems, float* dst, int64_t n, int resid, void* stream) {
+    if (!parts || !dst) { pg_set_error("op_sum_parts: null argument"); return PG_EINVAL; }
+    if (S < 1 || S > 8 || n < 0 || n > part_elems) { pg_set_error("op_sum_parts: 1 <= S <= 8, 0 <= n <= part_elems"); return PG_EINVAL; }
+    return pg_sum_parts_launch(parts, S, part_elems, dst, n, resid, (hipStream_t)stream);
+}
+extern "C" int pg_op_preln(float* x, const float* cls, const float* pos0, const float* gamma, const float* beta, int64_t rows, float eps,
+                           void* x16, int x16_dtype, float* rowstat, void* stream) {
+    if (!x || !cls || !pos0 || !gamma || !beta) { pg_set_error("op_preln: null argument"); return PG_EINVAL; }
+    if ((x16 == nullptr) != (rowstat == nullptr)) { pg_set_error("op_preln: x16 and rowstat go together"); return PG_EINVAL; }
+    return pg_preln_launch(x, cls, pos0, gamma, beta, rows, eps, (hipStream_t)stream, x16, x16_dtype, rowstat);
+}
+extern "C" int pg_op_attention_x3(const float* qkv, void* out3, int n_images, void* stream) {
+    if (!qkv || !out3) { pg_set_error("op_attention_x3: null argument"); return PG_EINVAL; }
+    return pg_attention_x3out_launch(qkv, out3, n_images, (hipStream_t)stream);
 }

@@ -755,3 +755,75 @@ def tune_gemm_mid(on) -> None:
     as an alternative -- the A/B arm).  Timing only: all kernels give the same bits for a row."""
     mode = 2 if (not isinstance(on, bool) and on == 2) else (1 if on else 0)
     check(load().pg_tune_gemm_mid(mode), "pg_tune_gemm_mid")
+
+
+# ----------------------------------------------------------------------------------------- exact-mode plan and the blocks it is made of
+def vit_precise_plan(n_images: int) -> dict:
+    """pg_vit_precise_plan: what forward_precise does with a batch of n_images under the current knobs (host arithmetic, no GPU)."""
+    out = (C.c_int32 * 8)()
+    check(load().pg_vit_precise_plan(int(n_images), out), "pg_vit_precise_plan")
+    return dict(qkv=out[0], out=out[1], fc1=out[2], fc2=out[3], fc1_fused=bool(out[4]), attn_x3=bool(out[5]), chunk=out[6], chunks=out[7])
+
+
+def tune_exact_products(n: int) -> None:
+    """pg_tune_exact_products: 3 (the exact tier) or 2 partial products per weight GEMM of the exact pass."""
+    check(load().pg_tune_exact_products(int(n)), "pg_tune_exact_products")
+
+
+def x3_im2col(pixels: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """pixels (n,3,336,336) fp32 / fp16 / bf16 -> the patch matrix's fp16 triple (n*576, 3*640)."""
+    _dev(pixels); _shape(pixels, "pixels", None, 3, 336, 336)
+    n = pixels.shape[0]
+    if out is None:
+        out = torch.empty((n * PATCHES, 3 * KPAD), dtype=torch.float16, device=pixels.device)
+    _dev(out, torch.float16)
+    if out.numel() < n * PATCHES * 3 * KPAD:
+        raise _lib.PigeonHipError("x3_im2col: output too small")
+    check(load().pg_op_x3_im2col(_p(pixels), _PIXDT[pixels.dtype], _p(out), n, _stream()), "pg_op_x3_im2col")
+    return out
+
+
+def sum_parts(parts: torch.Tensor, dst: torch.Tensor, resid: bool, n: Optional[int] = None) -> torch.Tensor:
+    """pg_op_sum_parts: parts (S, part_elems) fp32; dst[:n] = (resid ? dst[:n] : 0) + ((p0 + p1) + p2 ...), in place on dst."""
+    _dev(parts, torch.float32); _dev(dst, torch.float32)
+    S, pe = parts.shape[0], parts[0].numel()
+    n = pe if n is None else int(n)
+    if dst.numel() < n:
+        raise _lib.PigeonHipError("sum_parts: dst too small")
+    check(load().pg_op_sum_parts(_p(parts), S, pe, _p(dst), n, 1 if resid else 0, _stream()), "pg_op_sum_parts")
+    return dst
+
+
+def preln(x: torch.Tensor, cls: torch.Tensor, pos0: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, rows: Optional[int] = None,
+          eps: float = 1e-5, stat_dtype: Optional[torch.dtype] = None, x16: Optional[torch.Tensor] = None,
+          rowstat: Optional[torch.Tensor] = None):
+    """pg_op_preln in place on x (>= rows, 1024) fp32.  stat_dtype (or x16 / rowstat buffers): also -> (x16, rowstat)."""
+    _dev(x, torch.float32)
+    for t in (cls, pos0, gamma, beta):
+        _dev(t, torch.float32)
+        if t.numel() < HIDDEN:
+            raise _lib.PigeonHipError("preln: parameter vectors need 1024 elements")
+    rows = x.numel() // HIDDEN if rows is None else int(rows)
+    if x.numel() < rows * HIDDEN:
+        raise _lib.PigeonHipError("preln: x too small")
+    if stat_dtype is not None and x16 is None:
+        x16 = torch.empty((rows, HIDDEN), dtype=stat_dtype, device=x.device)
+        rowstat = torch.empty((rows, 2), dtype=torch.float32, device=x.device)
+    if x16 is not None and (x16.numel() < rows * HIDDEN or rowstat.numel() < rows * 2):
+        raise _lib.PigeonHipError("preln: x16 / rowstat too small")
+    check(load().pg_op_preln(_p(x), _p(cls), _p(pos0), _p(gamma), _p(beta), rows, float(eps), _p(x16),
+                             _dt16(x16) if x16 is not None else 0, _p(rowstat), _stream()), "pg_op_preln")
+    return (x16, rowstat) if x16 is not None else None
+
+
+def attention_x3(qkv: torch.Tensor, n_images: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """pg_op_attention_x3: fp32 QKV (n*577, 3072) -> the fp16 triple (n*577, 3072) of softmax(q k^T / 8) v."""
+    _dev(qkv, torch.float32)
+    _shape(qkv, "qkv", n_images * TOKENS, 3 * HIDDEN)
+    if out is None:
+        out = torch.empty((n_images * TOKENS, 3 * HIDDEN), dtype=torch.float16, device=qkv.device)
+    _dev(out, torch.float16)
+    if out.numel() < n_images * TOKENS * 3 * HIDDEN:
+        raise _lib.PigeonHipError("attention_x3: output too small")
+    check(load().pg_op_attention_x3(_p(qkv), _p(out), n_images, _stream()), "pg_op_attention_x3")
+    return out

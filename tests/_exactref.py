@@ -562,3 +562,353 @@ def compare_attention(got: torch.Tensor, want: torch.Tensor, tol=None, limit: in
     if guard is not None and not bool((guard == SENTINEL).all()):
         f.append(f"attention: guard region behind the output written at {_first(guard != SENTINEL)}")
     return f
+
+
+# ================================================================================================================ the exact tier's triple
+# csrc/x3.h: the triple of an fp32 value v is fully determined --
+#     hi = fp16_rne(clamp(v, +-65504)),   lo = fp16_rne(v - hi)  (the fp32 difference is exact),   hs = fp16_rne(hi * 2^-8)
+# -- so a kernel that writes it from a KNOWN fp32 value is compared bit for bit, fp16-subnormal halves, ties and the saturation included.
+F16_MAX = 65504.0
+SEGMENTS = ("hi", "lo", "hi*2^-8")
+
+
+def _bits(t: torch.Tensor) -> torch.Tensor:
+    return t if t.dtype == torch.int16 else t.view(torch.int16)
+
+
+def _halves(t: torch.Tensor) -> torch.Tensor:
+    return t.view(torch.float16) if t.dtype == torch.int16 else t
+
+
+def triple_ref(v: torch.Tensor):
+    """(hi, lo, hs) of the fp32 tensor v as int16 bit patterns, with torch's own conversions (round to nearest even, subnormals kept) on
+    whatever device v lives on.  |v| must stay below 1.3e5: beyond, v - hi itself overflows fp16 (outside the kernels' contract)."""
+    v = v.float()
+    hi = v.clamp(-F16_MAX, F16_MAX).half()
+    lo = (v - hi.float()).half()
+    hs = (hi.float() * 2.0 ** -8).half()
+    return _bits(hi), _bits(lo), _bits(hs)
+
+
+def compare_triple(got: torch.Tensor, v: torch.Tensor, C: int, seg: Optional[int] = None, limit: int = 4, where=None,
+                   guard: bool = True) -> List[str]:
+    """got (rows + guard rows, 3 seg) fp16 / int16 against the triple of v (rows, C) fp32, bit for bit.  Segment s occupies columns
+    [s seg, s seg + C); with seg > C (the patch matrix: C = 588, seg = 640) the columns between the segments must be zero.  Rows past
+    v's must still hold SENTINEL (guard=False: there are none).  Findings name segment, row and column (+ where(row, col))."""
+    seg = C if seg is None else seg
+    rows = v.shape[0]
+    f: List[str] = []
+    if got.dim() != 2 or got.shape[1] != 3 * seg or got.shape[0] < rows or v.shape[1] != C:
+        return [f"triple: buffer of shape {tuple(got.shape)} for values {tuple(v.shape)}, C = {C}, segment stride {seg}"]
+    g = _bits(got)
+    for s, want in enumerate(triple_ref(v)):
+        have = g[:rows, s * seg:s * seg + C]
+        bad = have != want
+        for (i, j) in _first(bad, limit):
+            f.append(f"triple {SEGMENTS[s]}: got 0x{int(have[i, j]) & 0xffff:04x} ({float(_halves(have)[i, j])!r}) want 0x{int(want[i, j]) & 0xffff:04x} "
+                     f"({float(_halves(want)[i, j])!r}) for v = {float(v[i, j])!r} at segment {s} row {i} col {j} (4-col group {j // 4})"
+                     + (" " + where(i, j) if where else ""))
+        if bad.any():
+            r = bad.any(1).nonzero().flatten()
+            f.append(f"triple {SEGMENTS[s]}: {int(bad.sum())} wrong elements in rows {int(r[0])} .. {int(r[-1])}")
+        if seg > C:
+            pad = g[:rows, s * seg + C:(s + 1) * seg]
+            if bool((pad != 0).any()):
+                f.append(f"triple {SEGMENTS[s]}: columns between the segments not zero at (row, pad col) {_first(pad != 0, limit)}")
+    if guard and got.shape[0] > rows:
+        gr = _halves(got[rows:])
+        if not bool((gr == SENTINEL).all()):
+            f.append(f"triple: guard rows past row {rows} written at (row - {rows}, col) {_first(gr != SENTINEL, limit)}")
+    return f
+
+
+def triple_consistent(got: torch.Tensor, C: int, rows: Optional[int] = None, limit: int = 4):
+    """A triple whose fp32 value the host cannot reproduce (LayerNorm, QuickGELU, attention) still has to be A triple:
+         hs == fp16(hi * 2^-8) bit for bit;   |lo| <= ulp16(hi) / 2  (hi is the NEAREST fp16);
+         fp16(hi + lo) == hi  (hi + lo is exact in fp32: at most 23 bits apart) -- except where |lo| is exactly half an ulp: lo is itself
+         rounded to 11 bits, which can carry a value just inside the half ulp onto the tie, and a tie may round to the other neighbour.
+    Returns (findings, hi + lo as fp64 (rows, C)): the reconstructed value then goes to a value comparator with triple_recon_bound."""
+    rows = got.shape[0] if rows is None else rows
+    t = _halves(got[:rows])
+    hi, lo, hs = t[:, :C], t[:, C:2 * C], t[:, 2 * C:3 * C]
+    f: List[str] = []
+    want_hs = (hi.float() * 2.0 ** -8).half()
+    hu = half_ulp16(hi.double(), torch.float16)                      # 2^-25 for a subnormal or zero hi
+    s = hi.float() + lo.float()
+    checks = (("hi*2^-8 != fp16(hi * 2^-8)", _bits(hs) != _bits(want_hs)),
+              ("|lo| > ulp16(hi) / 2", ~(lo.double().abs() <= hu)),
+              ("fp16(hi + lo) != hi", ~(s.half() == hi) & (lo.double().abs() != hu)))
+    for name, bad in checks:
+        for (i, j) in _first(bad, limit):
+            f.append(f"triple inconsistent, {name}: hi {float(hi[i, j])!r} lo {float(lo[i, j])!r} hs {float(hs[i, j])!r} at row {i} col {j} (4-col group {j // 4})")
+        if bad.any():
+            f.append(f"triple inconsistent, {name}: {int(bad.sum())} elements")
+    return f, hi.double() + lo.double()
+
+
+def triple_recon_bound(v: torch.Tensor) -> torch.Tensor:
+    """|v - (hi + lo)| for |v| <= 65504:  v - hi is exact and at most ulp16(hi) / 2 <= 2^-11 |hi|; rounding it to lo costs half an ulp of
+    lo, 2^-11 |lo| <= 2^-22 |hi| <= 2^-22 (1 + 2^-11) |v|, or half the subnormal quantum, 2^-25, where lo is subnormal:
+    max(2^-21 |v|, 2^-25) with a factor 2 to spare on the relative term."""
+    return torch.maximum(v.abs() * 2.0 ** -21, torch.full_like(v, 2.0 ** -25))
+
+
+SPECIALS = (0.0, -0.0, 2.0 ** -24, -(2.0 ** -24), 3 * 2.0 ** -25, 2.0 ** -25, 1.0e-6, 3.0e-5, 2.0 ** -14, 2.0 ** -14 - 2.0 ** -25, 6.1e-5,
+            1.0 + 2.0 ** -11, 1.0 + 3 * 2.0 ** -11, -(1.0 + 2.0 ** -11), 1.0 + 2.0 ** -11 + 2.0 ** -23, 2048.0 + 1.0, 2048.0 + 3.0,
+            65504.0, -65504.0, 65519.9, 65520.0, -65520.0, 7.0e4, -1.0e5, 65503.99, 0.1, 1.0 / 3.0)
+
+
+def triple_values(rows: int, cols: int, seed: int, device="cpu", specials: bool = True) -> torch.Tensor:
+    """fp32 (rows, cols): Gaussian times a log-uniform scale over 1e-6 .. 3e4 (every fp16 binade, the subnormal range included), and
+    SPECIALS -- +-0, the fp16 subnormal range, exact ties (1 + 2^-11 rounds down to even, 1 + 3 2^-11 up), the saturation edge (65504,
+    65519.9, 65520, 7e4, -1e5) -- planted at the start of the first row, at the end of the last row (the ragged end of a grid-stride
+    loop) and in the middle."""
+    g = torch.Generator(device=device).manual_seed(seed)
+    mag = torch.pow(10.0, torch.rand((rows, cols), generator=g, device=device) * (math.log10(3.0e4) + 6.0) - 6.0)
+    v = (torch.randn((rows, cols), generator=g, device=device) * mag).clamp(-6.0e4, 6.0e4)
+    if specials:
+        sp = torch.tensor(SPECIALS, dtype=torch.float32, device=device)
+        k = min(len(sp), cols)
+        v[0, :k] = sp[:k]
+        v[rows - 1, cols - k:] = sp[:k]
+        v[rows // 2, cols // 2 - k // 2:cols // 2 - k // 2 + k] = sp[:k].flip(0)
+    return v.contiguous()
+
+
+# ================================================================================================================ LayerNorm and row statistics
+# The row kernels (csrc/rowops.hip, csrc/precise.hip) state their arithmetic: a wave owns a 1024-float row, 16 values per lane;
+#   mean   = tree sum / 1024          in-lane (a + b) + (c + d), four of those added in sequence, then six butterfly levels: no value
+#                                     passes through more than 12 additions; the division by 1024 is exact
+#   var    = sum (x - mean)^2 / 1024  TWO passes: the deviations from the computed mean, squared, 16 in sequence per lane + 6 levels
+#   rstd   = 1 / sqrtf(var + eps)
+#   y      = (x - mean) * rstd * g + b
+# gamma_d = d u / (1 - d u) bounds the relative error of any quantity that went through d roundings (u = 2^-24).
+LN_SUM_DEPTH = 12            # additions on the longest path of the row sum
+LN_SQ_DEPTH = 25             # (x - mean) rounded (twice: it is squared) + the square + 16 + 6 additions
+
+
+def _gamma(d: int) -> float:
+    return d * U32 / (1.0 - d * U32)
+
+
+def _rstd_interval(var, dvar, eps: float):
+    """rstd = (var + eps)^-1/2 and the most the computed 1 / sqrtf(var_c + eps32) can differ from it, given |var_c - var| <= dvar and
+    var_c >= 0 (a sum of squares; rowstat_finalize clamps): eps arrives as fp32 (|eps32 - eps| <= u eps), the addition rounds once,
+    sqrtf and the division are taken at one ulp each ((1 + 2u)^2 < 1 + 5u; they are correctly rounded in this build: a factor 2 to
+    spare).  The interval is carried exactly, not to first order: with dvar close to var + eps the upper end is what it is."""
+    eps32 = float(torch.tensor(eps, dtype=torch.float32))
+    rstd = (var + eps).rsqrt()
+    t_lo = ((var - dvar).clamp_min(0.0) + eps32) * (1.0 - U32)
+    t_hi = (var + dvar + eps32) * (1.0 + U32)
+    k = 1.0 + 5.0 * U32
+    return rstd, torch.maximum(t_lo.rsqrt() * k - rstd, rstd - t_hi.rsqrt() / k)
+
+
+def _two_pass_stats(x: torch.Tensor, eps: float):
+    """fp64 (mean, deviations, rstd) of the rows of x and the bounds (dm, dr) of the kernels' computed mean and rstd:
+         |mean_c - mean| <= dm = gamma_12 mean|x|
+         var_c = (1/n) sum (x - mean_c)^2 (1 + theta), |theta| <= gamma_25, and (1/n) sum (x - mean_c)^2 = var + (mean - mean_c)^2 EXACTLY
+         (the deviations from the true mean sum to zero)  =>  |var_c - var| <= dm^2 + gamma_25 (var + dm^2): no cancellation term --
+         that is what the second pass buys."""
+    xd = x.double()
+    m = xd.mean(1, keepdim=True)
+    dev = xd - m
+    var = (dev * dev).mean(1, keepdim=True)
+    dm = _gamma(LN_SUM_DEPTH) * xd.abs().mean(1, keepdim=True)
+    rstd, dr = _rstd_interval(var, dm * dm + _gamma(LN_SQ_DEPTH) * (var + dm * dm), eps)
+    return m, dev, rstd, dm, dr
+
+
+def layernorm_bound(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps: float = 1e-5):
+    """(y, bound): LayerNorm of the fp32 rows x in fp64 and, per element, the most the kernels' fp32 result can differ from it.
+         d_c = fl(x - mean_c):                |d_c - dev| <= E_d = dm + u (|dev| + dm)
+         p_c = fl(fl(d_c rstd_c) g):          |p_c - dev rstd g| <= |g| [ E_d (rstd + dr) (1 + u)^2 + |dev| ((rstd + dr) (1 + u)^2 - rstd) ] = E_p
+         y_c = fl(p_c + b):                   |y_c - y| <= E_p + u (|y| + E_p)
+    (four roundings; with the multiply and the add contracted into an FMA there are three, which the same expression covers), plus
+    2^-124 for results below the smallest normal fp32.  A 16-bit output adds half_ulp16(|y| + bound), a triple triple_recon_bound."""
+    m, dev, rstd, dm, dr = _two_pass_stats(x, eps)
+    g, b = gamma.double()[None, :], beta.double()[None, :]
+    y = dev * rstd * g + b
+    e_d = dm + U32 * (dev.abs() + dm)
+    k = (rstd + dr) * (1.0 + U32) ** 2
+    e_p = g.abs() * (e_d * k + dev.abs() * (k - rstd))
+    return y, e_p + U32 * (y.abs() + e_p) + 2.0 ** -124
+
+
+def rowstat_bound(x: torch.Tensor, eps: float = 1e-5):
+    """((rstd, mean rstd), (bound, bound)) per row for the two-pass statistics (rowstat_cast_kernel, preln_kernel's STAT form):
+    rstd as in layernorm_bound; the product fl(mean_c rstd_c) lies within (|mean| + dm) (rstd + dr) (1 + u) - |mean| rstd of mean rstd."""
+    m, _, rstd, dm, dr = _two_pass_stats(x, eps)
+    return (rstd[:, 0], (m * rstd)[:, 0]), (dr[:, 0], ((m.abs() + dm) * (rstd + dr) * (1.0 + U32) - m.abs() * rstd)[:, 0])
+
+
+def rowstat_finalize_bound(part: torch.Tensor, eps: float = 1e-5, n: int = HIDDEN):
+    """The same pair from per-slice partials part (slots, rows, 2) = (sum, sum of squares), as rowstat_finalize_kernel computes it -- ONE
+    pass:  s1, s2 = the partials added in slot order;  mean = s1 / n;  var = max(s2 / n - mean^2, 0).  Against fp64 on the same partials:
+         |mean_c - mean| <= dm = gamma_slots sum|p1| / n,      |s2 / n - E2| <= dE = gamma_slots sum|p2| / n
+         |fl(mean_c^2) - mean^2| <= dm (2 |mean| + dm) + u (|mean| + dm)^2
+         the subtraction rounds once:  u (E2 + dE + (1 + u) (|mean| + dm)^2)
+    The last two lines are the CANCELLATION term: u (E2 + mean^2) stands against var = E2 - mean^2, so a row with |mean| >> std has a
+    bound on var (and through _rstd_interval on rstd) that is (E2 + mean^2) / var times the two-pass one -- it is carried as such, not
+    folded into a constant.  Returns ((rstd, mean rstd), (bound, bound))."""
+    p = part.double()
+    slots = part.shape[0]
+    m = (p[:, :, 0].sum(0) / n)[:, None]
+    e2 = (p[:, :, 1].sum(0) / n)[:, None]
+    var = (e2 - m * m).clamp_min(0.0)
+    dm = _gamma(slots) * (p[:, :, 0].abs().sum(0) / n)[:, None]
+    de = _gamma(slots) * (p[:, :, 1].abs().sum(0) / n)[:, None]
+    mm = (m.abs() + dm) ** 2
+    dvar = de + dm * (2.0 * m.abs() + dm) + U32 * mm + U32 * (e2 + de + (1.0 + U32) * mm)
+    rstd, dr = _rstd_interval(var, dvar, eps)
+    return (rstd[:, 0], (m * rstd)[:, 0]), (dr[:, 0], ((m.abs() + dm) * (rstd + dr) * (1.0 + U32) - m.abs() * rstd)[:, 0])
+
+
+ROW_KINDS = ("gaussian", "mean >> std", "constant", "outlier", "small")
+
+
+def ln_rows(rows: int, seed: int, device="cpu", kind0: int = 0) -> torch.Tensor:
+    """fp32 (rows, 1024); row r is of kind ROW_KINDS[(r + kind0) % 5]: Gaussian (mean 0.5, std 3); |mean| >> std (mean +-50, std 0.1 -- the
+    trained-tower regime, where a one-pass variance loses its digits); constant (variance exactly 0); Gaussian with one 3e3 outlier;
+    Gaussian of scale 1e-2."""
+    g = torch.Generator(device=device).manual_seed(seed)
+    x = torch.randn((rows, HIDDEN), generator=g, device=device)
+    r = torch.arange(rows, device=device)
+    kind = ((r + kind0) % 5)[:, None]
+    sign = (1.0 - 2.0 * ((r // 5) % 2).float())[:, None]
+    const = (torch.tensor([50.0, -3.25, 0.0, 1.0e-3, 1.0 / 3.0, -777.0], device=device)[(r // 5) % 6])[:, None]
+    col = torch.arange(HIDDEN, device=device)[None, :]
+    spike = (col == ((r * 37) % HIDDEN)[:, None]).float() * 3.0e3
+    x = torch.where(kind == 0, x * 3.0 + 0.5, torch.where(kind == 1, sign * 50.0 + 0.1 * x, torch.where(
+        kind == 2, const.expand(rows, HIDDEN), torch.where(kind == 3, x + spike, x * 1.0e-2))))
+    return x.contiguous()
+
+
+def ln_affine(seed: int, device="cpu"):
+    """Jittered LayerNorm parameters: gamma = 1 + 0.1 N(0, 1), beta = 0.05 N(0, 1) -- a parameter read from the neighbouring lane shows."""
+    g = torch.Generator(device=device).manual_seed(seed)
+    return (1.0 + 0.1 * torch.randn(HIDDEN, generator=g, device=device)).contiguous(), (0.05 * torch.randn(HIDDEN, generator=g, device=device)).contiguous()
+
+
+def _ln_where(row: int, col: int, kind0: Optional[int]) -> str:
+    k = "" if kind0 is None else f", a '{ROW_KINDS[(row + kind0) % 5]}' row"
+    return f"row {row} (token {row % TOKENS} of image {row // TOKENS}{k}) col {col} (lane {col % 256 // 4}, load {col // 256})"
+
+
+def compare_values(name: str, got: torch.Tensor, want: torch.Tensor, tol: torch.Tensor, r0: int = 0, kind0: Optional[int] = None,
+                   limit: int = 4) -> List[str]:
+    """|got - want| <= tol per element (a NaN or Inf anywhere fails); findings name the row, its kind and the column."""
+    g = got.double()
+    err = (g - want).abs()
+    bad = ~(err <= tol)
+    f = [f"{name}: got {float(g[i, j])!r} want {float(want[i, j])!r} (bound {float(tol[i, j] if tol.dim() == 2 else tol):.3e}) at " + _ln_where(r0 + i, j, kind0)
+         for (i, j) in _first(bad, limit)]
+    if f:
+        rows = bad.any(1).nonzero().flatten()
+        f.append(f"{name}: {int(bad.sum())} elements outside their bound in rows {r0 + int(rows[0])} .. {r0 + int(rows[-1])}")
+    return f
+
+
+def compare_layernorm(got: torch.Tensor, x: torch.Tensor, gamma, beta, eps: float, out, kind0: Optional[int] = None,
+                      chunk: int = 16384, limit: int = 4, name: str = "layernorm", worst: Optional[list] = None) -> List[str]:
+    """got = what a LayerNorm kernel wrote for the rows x (+ sentinel guard rows behind them), per element within layernorm_bound.
+    out: torch.float32 / float16 / bfloat16 (+ half an ulp of the type at |y| + bound) or "x3": a triple (rows, 3072), which must be
+    triple_consistent and whose hi + lo gets triple_recon_bound on top.  No element is excluded.  worst (a list): receives the largest
+    error / bound ratio."""
+    rows = x.shape[0]
+    f: List[str] = []
+    for r0 in range(0, rows, chunk):
+        r1 = min(rows, r0 + chunk)
+        y, b = layernorm_bound(x[r0:r1], gamma, beta, eps)
+        if out == "x3":
+            fc, val = triple_consistent(got[r0:r1], HIDDEN, limit=limit)
+            f += [f"{name} rows {r0}..: {m}" for m in fc]
+            b = b + triple_recon_bound(y.abs() + b)
+        else:
+            val = got[r0:r1].double()
+            if out != torch.float32:
+                b = b + half_ulp16(y.abs() + b, out)
+        f += compare_values(name, val, y, b, r0, kind0, limit)
+        if worst is not None:
+            worst.append(float(torch.nan_to_num((val - y).abs() / b, nan=float("inf")).max()))
+        if len(f) > 40:
+            return f
+    gr = got[rows:]
+    if gr.numel() and not bool((_halves(gr).double() == SENTINEL).all()):
+        f.append(f"{name}: guard rows past row {rows} written at (row - {rows}, col) {_first(_halves(gr).double() != SENTINEL, limit)}")
+    return f
+
+
+def compare_rowstat(name: str, got: torch.Tensor, ref, bound, kind0: Optional[int] = None, limit: int = 4) -> List[str]:
+    """got (rows, 2) = (rstd, mean rstd) against (ref, bound) of rowstat_bound / rowstat_finalize_bound."""
+    f = []
+    for c, what in enumerate(("rstd", "mean*rstd")):
+        err = (got[:, c].double() - ref[c]).abs()
+        bad = ~(err <= bound[c])
+        for (i,) in _first(bad, limit):
+            k = "" if kind0 is None else f" ('{ROW_KINDS[(i + kind0) % 5]}')"
+            f.append(f"{name} {what}: got {float(got[i, c])!r} want {float(ref[c][i])!r} (bound {float(bound[c][i]):.3e}) at row {i}{k}, 256-row block {i // 256} +{i % 256}")
+        if bad.any():
+            f.append(f"{name} {what}: {int(bad.sum())} rows outside their bound")
+    return f
+
+
+def statparts_of(x: torch.Tensor, slots: int = 16) -> torch.Tensor:
+    """(slots, rows, 2) fp32: per 64-column slice (sum, sum of squares) of the rows x, formed in fp64 and rounded once -- the layout the
+    RESID_STAT epilogue hands rowstat_finalize (slot-major)."""
+    xs = x.double().reshape(x.shape[0], slots, -1)
+    return torch.stack([xs.sum(2), (xs * xs).sum(2)], dim=2).permute(1, 0, 2).float().contiguous()
+
+
+# ================================================================================================================ im2col, sum of parts
+PATCH_K, PATCH_KPAD = 588, 640
+
+
+def im2col_ref(pixels: torch.Tensor) -> torch.Tensor:
+    """(n, 3, 336, 336) -> (n 576, 588) fp32: row = image 576 + py 24 + px, column k = c 196 + ky 14 + kx (Conv2d's weight flattened),
+    through torch's unfold on the pixels widened to fp32 (exact for every pixel type)."""
+    n = pixels.shape[0]
+    u = torch.nn.functional.unfold(pixels.float(), kernel_size=14, stride=14)            # (n, 588, 576)
+    return u.transpose(1, 2).reshape(n * PATCHES, PATCH_K).contiguous()
+
+
+def im2col_where(row: int, col: int) -> str:
+    p = row % PATCHES
+    return f"(image {row // PATCHES} patch row {p // 24} patch col {p % 24}; channel {col // 196} ky {col % 196 // 14} kx {col % 14})"
+
+
+def compare_im2col(got: torch.Tensor, pixels: torch.Tensor, limit: int = 4) -> List[str]:
+    """got (n 576 + guard rows, 640) 16-bit against unfold rounded to got's type: equal, pad columns 588..639 zero, guard rows untouched."""
+    want = im2col_ref(pixels)
+    if got.dtype == torch.float16:
+        want = want.clamp(-F16_MAX, F16_MAX)
+    want = want.to(got.dtype)
+    rows = want.shape[0]
+    f = []
+    bad = _bits(got[:rows, :PATCH_K]) != _bits(want)
+    for (i, j) in _first(bad, limit):
+        f.append(f"im2col: got {float(got[i, j])!r} want {float(want[i, j])!r} at row {i} col {j} " + im2col_where(i, j))
+    if bad.any():
+        f.append(f"im2col: {int(bad.sum())} wrong elements")
+    if bool((_bits(got[:rows, PATCH_K:]) != 0).any()):
+        f.append(f"im2col: pad columns not zero at (row, col - 588) {_first(_bits(got[:rows, PATCH_K:]) != 0, limit)}")
+    if got.shape[0] > rows and not bool((got[rows:].float() == SENTINEL).all()):
+        f.append(f"im2col: guard rows written at {_first(got[rows:].float() != SENTINEL, limit)}")
+    return f
+
+
+def representable_pixels(n: int, seed: int, device="cpu") -> torch.Tensor:
+    """fp32 pixels (n, 3, 336, 336) that are exact in fp16 AND bf16 (multiples of 1/16 in [-8, 8)): every (pixel type, operand type) pair
+    then has one right answer.  Neighbouring pixels, rows, channels and images differ."""
+    g = torch.Generator(device=device).manual_seed(seed)
+    return (torch.randint(-128, 128, (n, 3, 336, 336), generator=g, device=device).float() / 16.0).contiguous()
+
+
+def sum_parts_ref(parts: torch.Tensor, dst0: Optional[torch.Tensor]) -> torch.Tensor:
+    """((p0 + p1) + p2) ... in fp32, then dst0 + that: the additions of sum_parts_kernel in its order, with torch on the CPU (IEEE
+    single additions, nothing to contract)."""
+    p = parts.detach().cpu().float()
+    acc = p[0].clone()
+    for k in range(1, p.shape[0]):
+        acc = acc + p[k]
+    return acc if dst0 is None else dst0.detach().cpu().float() + acc

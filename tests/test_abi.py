@@ -25,7 +25,7 @@ def test_header_symbols_exported(hip_lib):
 def test_ctypes_signatures_and_abi_version(hip_lib):
     from pigeon_amd import _lib
     assert sorted(_lib.SIGNATURES) == declared_symbols()
-    assert hip_lib.pg_abi_version() == 6
+    assert hip_lib.pg_abi_version() == 7
 
 
 def test_no_gpu_fails_loudly(hip_lib):

@@ -289,3 +289,238 @@ def test_plan_invariants_over_every_row_count(hip_lib):
     finally:
         L.pg_tune_gemm_mid(1)
     assert {"fc1", "fc2"} <= seen_split                      # the sweep does reach the split (the invariants are not vacuous)
+
+
+# ================================================================================================================ the exact tier's streaming kernels
+# numpy stand-ins of csrc/precise.hip / csrc/rowops.hip's row kernels (numpy's own float16 / float32 conversions and another, equally
+# valid summation tree: pairwise halving, depth 10) pass the comparators of _exactref.py with NO element excluded, and each mistake such
+# a kernel can make is rejected with a message that names the place.
+F32 = np.float32
+
+
+def emulate_triple(v, C, mutant=None, seg=None, guard=3):
+    """v (rows, C) fp32 numpy -> (rows + guard, 3 seg) fp16 torch buffer as a split kernel writes it (guard rows = SENTINEL)."""
+    seg = C if seg is None else seg
+    v = np.ascontiguousarray(v, dtype=F32)
+    with np.errstate(over="ignore", invalid="ignore"):
+        vc = v if mutant == "no_saturation" else np.clip(v, -65504.0, 65504.0).astype(F32)
+        hi = vc.astype(np.float16)
+        if mutant == "truncation":                              # round toward zero instead of to nearest even
+            over = np.abs(hi.astype(F32)) > np.abs(vc)
+            hi = np.where(over, np.nextafter(hi, np.float16(0)), hi).astype(np.float16)
+        lo = (v - (vc if mutant == "lo_from_unrounded" else hi.astype(F32))).astype(np.float16)
+        if mutant == "lo_subnormal_flushed":
+            lo = np.where(np.abs(lo.astype(F32)) < 2.0 ** -14, np.float16(0), lo).astype(np.float16)
+        hs = ((v if mutant == "hs_from_v" else hi.astype(F32)) * F32(2.0 ** -8)).astype(np.float16)
+    segs = [hi, hs, lo] if mutant == "lo_hs_swapped" else [hi, lo, hs]
+    out = np.full((v.shape[0] + guard, 3 * seg), X.SENTINEL, np.float16)
+    out[:v.shape[0]] = 0 if mutant != "pad_not_zeroed" else X.SENTINEL
+    for s, a in enumerate(segs):
+        out[:v.shape[0], s * seg:s * seg + C] = a
+    if mutant == "group_at_neighbours_offset":                  # row 2, segment lo: the 4-column group 9 lands on group 10's columns
+        out[2, seg + 40:seg + 44] = lo[2, 36:40]
+    if mutant == "row_past_end":
+        out[v.shape[0], :C] = hi[-1]
+    return torch.from_numpy(out)
+
+
+TRIPLE_MUTANTS = {   # mutant -> words its finding must contain
+    "truncation": ("triple hi",), "no_saturation": ("triple hi", "65520"), "lo_from_unrounded": ("triple lo",), "hs_from_v": ("triple hi*2^-8",),
+    "lo_subnormal_flushed": ("triple lo",), "lo_hs_swapped": ("triple lo", "triple hi*2^-8"),
+    "group_at_neighbours_offset": ("segment 1 row 2 col 40 (4-col group 10)",), "row_past_end": ("guard rows",),
+}
+
+
+def test_triple_standin_accepted_and_every_mutant_rejected():
+    C = 1024
+    v = X.triple_values(7, C, 3).numpy()
+    tv = torch.from_numpy(v)
+    assert X.compare_triple(emulate_triple(v, C), tv, C) == []
+    # the planted values do what they are planted for (numpy's conversions: an implementation that is not torch's)
+    t = emulate_triple(np.array([[1 + 2.0 ** -11, 1 + 3 * 2.0 ** -11, 65519.9, 65520.0, 7.0e4, -1.0e5, 2.0 ** -24, -0.0]], F32), 8, guard=0).float()
+    assert t[0, :8].tolist() == [1.0, 1 + 2.0 ** -9, 65504.0, 65504.0, 65504.0, -65504.0, 2.0 ** -24, 0.0]
+    assert t[0, 8:16].tolist()[:6] == [2.0 ** -11, -(2.0 ** -11), 15.8984375, 16.0, 4496.0, -34496.0]
+    assert int(emulate_triple(np.array([[-0.0] * 4], F32), 4, guard=0).view(torch.int16)[0, 0]) == -32768          # -0 keeps its sign in hi
+    for m, words in TRIPLE_MUTANTS.items():
+        found = X.compare_triple(emulate_triple(v, C, m), tv, C)
+        assert found, m
+        for w in words:
+            assert any(w in line for line in found), (m, w, found[:3])
+    # the consistency check (for triples whose value the host cannot reproduce) sees the same mistakes where they break the triple's own
+    # structure, and passes the honest one on the values inside fp16's range
+    inside = np.clip(v, -6.0e4, 6.0e4)
+    f, val = X.triple_consistent(emulate_triple(inside, C, guard=0), C)
+    assert f == [] and bool(((val - torch.from_numpy(inside).double()).abs() <= X.triple_recon_bound(torch.from_numpy(inside).double())).all())
+    for m in ("truncation", "hs_from_v", "lo_hs_swapped"):
+        assert X.triple_consistent(emulate_triple(inside, C, m, guard=0), C)[0], m
+
+
+def _pairwise(a):
+    """fp32 pairwise sum over the last axis (a power of two long): another valid tree, depth log2(n)."""
+    a = a.astype(F32)
+    while a.shape[-1] > 1:
+        a = (a[..., 0::2] + a[..., 1::2]).astype(F32)
+    return a[..., 0]
+
+
+def emulate_layernorm(x, g, b, eps=1e-5, mutant=None, const_rows=None):
+    x, g, b = [np.ascontiguousarray(t, dtype=F32) for t in (x, g, b)]
+    n = F32(x.shape[1])
+    mean = (_pairwise(x) / n).astype(F32)[:, None]
+    d = (x - mean).astype(F32)
+    var = (_pairwise((d * d).astype(F32)) / (F32(1023.0) if mutant == "divisor_1023" else n)).astype(F32)[:, None]
+    if mutant == "one_pass":
+        var = np.maximum((_pairwise((x * x).astype(F32)) / n).astype(F32)[:, None] - (mean * mean).astype(F32), F32(0)).astype(F32)
+    e = np.full_like(var, F32(eps))
+    if mutant == "eps_dropped":
+        e[const_rows] = 0
+    with np.errstate(divide="ignore", invalid="ignore"):
+        rstd = (F32(1) / np.sqrt((var + e).astype(F32))).astype(F32)
+        if mutant == "gamma_of_next_lane":
+            g = np.roll(g, -4)
+        return ((((d * rstd).astype(F32) * g[None, :]).astype(F32)) + b[None, :]).astype(F32), mean[:, 0], rstd[:, 0]
+
+
+def _ln_buffer(y, out, guard=3):
+    y = torch.from_numpy(y)
+    if out == "x3":
+        return emulate_triple(y.numpy(), X.HIDDEN, guard=guard)
+    buf = torch.full((y.shape[0] + guard, X.HIDDEN), X.SENTINEL, dtype=out)
+    buf[:y.shape[0]] = y.clamp(-65504.0, 65504.0).to(out) if out == F16 else y.to(out)
+    return buf
+
+
+LN_ROWS = 45          # nine of each row kind
+LN_MUTANTS = ("one_pass", "divisor_1023", "eps_dropped", "gamma_of_next_lane")
+
+
+@pytest.mark.parametrize("out", [torch.float32, F16, BF16, "x3"], ids=["f32", "f16", "bf16", "x3"])
+def test_layernorm_standin_accepted_and_every_mutant_rejected(out):
+    x = X.ln_rows(LN_ROWS, 8)
+    g, b = X.ln_affine(9)
+    kinds = np.arange(LN_ROWS) % 5
+    y, _, _ = emulate_layernorm(x.numpy(), g.numpy(), b.numpy())
+    worst = []
+    assert X.compare_layernorm(_ln_buffer(y, out), x, g, b, 1e-5, out, kind0=0, worst=worst) == []
+    assert 0.0 < max(worst) < 1.0
+    # torch's own fp32 LayerNorm (yet another summation order) is inside the bound too
+    assert X.compare_layernorm(_ln_buffer(torch.nn.functional.layer_norm(x, (1024,), g, b, 1e-5).numpy(), out), x, g, b, 1e-5, out, kind0=0) == []
+    for m in LN_MUTANTS:
+        ym, _, _ = emulate_layernorm(x.numpy(), g.numpy(), b.numpy(), mutant=m, const_rows=kinds == 2)
+        found = X.compare_layernorm(_ln_buffer(ym, out), x, g, b, 1e-5, out, kind0=0, limit=100)
+        assert found, (m, out)
+        named = " ".join(found)
+        if m == "one_pass":
+            assert "'mean >> std' row" in named, found[:3]
+        if m == "eps_dropped":
+            assert "'constant' row" in named and all("'constant' row" in l for l in found if " at row " in l and "triple inconsistent" not in l), found[:3]
+    # a stale guard row
+    buf = _ln_buffer(y, out)
+    buf[LN_ROWS, 5] = 1.0
+    assert any("guard rows" in l for l in X.compare_layernorm(buf, x, g, b, 1e-5, out))
+
+
+def test_one_pass_variance_is_what_the_finalize_bound_allows_and_the_two_pass_bound_does_not():
+    """rowstat_finalize really is one-pass: its stand-in passes rowstat_finalize_bound (which carries the cancellation term) on every row
+    kind, and the SAME numbers fail the two-pass bound on the |mean| >> std (and constant) rows, only there -- the two bounds are not interchangeable."""
+    x = X.ln_rows(LN_ROWS, 12)
+    part = X.statparts_of(x)
+    p = part.numpy()
+    s1 = np.zeros(LN_ROWS, F32); s2 = np.zeros(LN_ROWS, F32)
+    for i in range(p.shape[0]):
+        s1 = (s1 + p[i, :, 0]).astype(F32); s2 = (s2 + p[i, :, 1]).astype(F32)
+    mean = (s1 / F32(1024)).astype(F32)
+    var = np.maximum((s2 / F32(1024)).astype(F32) - (mean * mean).astype(F32), F32(0)).astype(F32)
+    rstd = (F32(1) / np.sqrt((var + F32(1e-5)).astype(F32))).astype(F32)
+    got = torch.from_numpy(np.stack([rstd, (mean * rstd).astype(F32)], 1))
+    ref, bound = X.rowstat_finalize_bound(part)
+    assert X.compare_rowstat("finalize", got, ref, bound, kind0=0) == []
+    ref2, bound2 = X.rowstat_bound(x)
+    found = X.compare_rowstat("two-pass", got, ref2, bound2, kind0=0, limit=100)
+    # (a constant row is the limit of that regime: its variance is ALL cancellation)
+    assert any("'mean >> std'" in l for l in found) and all("'mean >> std'" in l or "'constant'" in l for l in found if " at row " in l), found[:3]
+    assert float((bound[0] / bound2[0])[1::5].min()) > 100.0          # the cancellation term, not a constant
+    # the two-pass stand-in is inside the two-pass bound; a rowstat computed from the row BEFORE it was rewritten is not
+    _, m2, r2 = emulate_layernorm(x.numpy(), np.ones(1024), np.zeros(1024))
+    assert X.compare_rowstat("cast", torch.from_numpy(np.stack([r2, (m2 * r2).astype(F32)], 1)), ref2, bound2, kind0=0) == []
+    assert X.compare_rowstat("cast", torch.from_numpy(np.stack([np.roll(r2, 1), (m2 * r2).astype(F32)], 1)), ref2, bound2, kind0=0)
+
+
+def emulate_preln(x, cls, pos0, g, b, mutant=None):
+    x = x.copy()
+    t0 = np.arange(x.shape[0]) % X.TOKENS == 0
+    if mutant != "class_row_from_stale_x":
+        x[t0] = (cls + pos0).astype(F32)[None, :]
+    return emulate_layernorm(x, g, b)[0]
+
+
+def test_preln_standin_accepted_and_stale_class_row_rejected():
+    rows = 2 * X.TOKENS + 3                                     # two images and the start of a third: class rows 0, 577, 1154
+    x = X.ln_rows(rows, 21)
+    x[::X.TOKENS] = 1234.5                                      # what the patch GEMM leaves there is NOT the class token: a sentinel
+    g, b = X.ln_affine(22)
+    gen = torch.Generator().manual_seed(23)
+    cls, pos0 = torch.randn(1024, generator=gen) * 0.03, torch.randn(1024, generator=gen) * 0.02
+    want_in = x.clone()
+    want_in[::X.TOKENS] = cls + pos0                            # one fp32 addition: the row the kernel normalises
+    y = emulate_preln(x.numpy(), cls.numpy(), pos0.numpy(), g.numpy(), b.numpy())
+    assert X.compare_layernorm(_ln_buffer(y, torch.float32), want_in, g, b, 1e-5, torch.float32, kind0=0, name="preln") == []
+    bad = emulate_preln(x.numpy(), cls.numpy(), pos0.numpy(), g.numpy(), b.numpy(), "class_row_from_stale_x")
+    found = X.compare_layernorm(_ln_buffer(bad, torch.float32), want_in, g, b, 1e-5, torch.float32, kind0=0, name="preln", limit=5000)
+    rows_named = {int(l.split(" at row ")[1].split(" ")[0]) for l in found if " at row " in l}
+    assert rows_named == {0, 577, 1154}, sorted(rows_named)[:8]
+    assert any("token 0 of image 2" in l for l in found)
+
+
+def test_sum_parts_reference_pins_the_order():
+    g = torch.Generator().manual_seed(31)
+    for S in (2, 3, 4, 6):
+        parts = torch.randn((S, 1000), generator=g) * torch.tensor([1.0, 300.0, 0.01, 7.0, 1e3, 1e-3][:S])[:, None]
+        dst0 = torch.randn(1000, generator=g)
+        p = parts.numpy()
+        acc = p[0].copy()
+        for k in range(1, S):
+            acc = (acc + p[k]).astype(F32)
+        for resid in (False, True):
+            want = X.sum_parts_ref(parts, dst0 if resid else None)
+            assert torch.equal(torch.from_numpy((dst0.numpy() + acc).astype(F32) if resid else acc), want)
+        rev = p[S - 1].copy()
+        for k in range(S - 2, -1, -1):
+            rev = (rev + p[k]).astype(F32)
+        if S > 2:                                                 # (two parts: the addition commutes; from three on the order shows)
+            assert not torch.equal(torch.from_numpy(rev), X.sum_parts_ref(parts, None)), "the inputs must tell the orders apart"
+        twice = ((dst0.numpy() + acc).astype(F32) + dst0.numpy()).astype(F32)
+        assert not torch.equal(torch.from_numpy(twice), X.sum_parts_ref(parts, dst0))
+
+
+def emulate_im2col(px, mutant=None):
+    n = px.shape[0]
+    a = px.reshape(n, 3, 24, 14, 24, 14)                        # (img, c, py, ky, px, kx)
+    order = (0, 2, 4, 1, 5, 3) if mutant == "ky_kx_transposed" else (0, 2, 4, 1, 3, 5)
+    return np.ascontiguousarray(a.transpose(order).reshape(n * 576, 588))
+
+
+@pytest.mark.parametrize("mutant", [None, "ky_kx_transposed", "pad_not_zeroed"])
+def test_im2col_standin_and_mutants(mutant):
+    px = X.representable_pixels(2, 41)
+    vals = emulate_im2col(px.numpy(), mutant)
+    for dt in (F16, BF16):                                       # the fast path's patch matrix
+        buf = torch.full((2 * 576 + 3, 640), X.SENTINEL, dtype=dt)
+        buf[:2 * 576, :588] = torch.from_numpy(vals).to(dt)
+        if mutant != "pad_not_zeroed":
+            buf[:2 * 576, 588:] = 0
+        found = X.compare_im2col(buf, px.to(dt))
+        assert bool(found) == (mutant is not None), (mutant, found[:2])
+        if mutant == "ky_kx_transposed":
+            assert any("ky 0 kx 1" in l for l in found), found[:2]     # the first element that moves
+        if mutant == "pad_not_zeroed":
+            assert any("pad columns" in l for l in found)
+    # the exact tier's: three segments of 588 at stride 640
+    ref = X.im2col_ref(px)
+    buf = emulate_triple(vals, 588, "pad_not_zeroed" if mutant == "pad_not_zeroed" else None, seg=640)
+    found = X.compare_triple(buf, ref, 588, seg=640, where=X.im2col_where)
+    assert bool(found) == (mutant is not None), (mutant, found[:2])
+    if mutant == "pad_not_zeroed":
+        assert any("columns between the segments" in l for l in found)
+    if mutant == "ky_kx_transposed":
+        assert any("ky 0 kx 1" in l for l in found), found[:2]

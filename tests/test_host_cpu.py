@@ -527,3 +527,65 @@ def test_gemm_plan_pins_the_tail_split():
     assert L.pg_gemm_plan(8, _lib.EPI_RESID_STAT, 577, 1024, 1024, C.byref(k), C.byref(rows), C.byref(rest)) == -1     # PG_EINVAL
     assert L.pg_gemm_plan(70, _lib.EPI_PATCH, 577, 1024, 640, C.byref(k), C.byref(rows), C.byref(rest)) == -1     # PG_EINVAL
     assert L.pg_gemm_plan(31, _lib.EPI_QKV, 577, 3072, 1024, C.byref(k), C.byref(rows), C.byref(rest)) == -1     # retired schedule
+
+
+def test_vit_precise_plan_host_properties():
+    """pg_vit_precise_plan (host arithmetic, no launch): what pg_vit_forward_precise does with a batch -- the form of the layer's four
+    weight GEMMs, the two fusions, the internal passes.  It is a pure function of (n, knobs); every route it reports is one the launch
+    accepts; a batch above 128 is cut into passes that differ by at most one image and never exceed 128; fc1 is fused exactly where
+    its route is 1 and fusion is on; pg_tune_gemm_mid(0) removes every gemm_mid route."""
+    import ctypes as C
+    from pigeon_amd import _lib, hip_ops
+    L = _lib.load()
+    KTOT = dict(qkv=3 * 1024, out=3 * 1024, fc1=3 * 1024, fc2=3 * 4096)
+    ALLOWED = dict(qkv=(0, 1, 3), out=(0, 1, 3), fc1=(0, 1, 3), fc2=(0, 1, 2, 3, 6))
+    ns = list(range(1, 131)) + [255, 256, 257, 258, 259, 383, 384, 385, 386, 387, 511, 512, 513, 1000, 1025]
+
+    def sweep():
+        return {n: hip_ops.vit_precise_plan(n) for n in ns}
+
+    first = sweep()
+    k, rows, rest = C.c_int(), C.c_int(), C.c_int()
+    for n in (1, 16, 64):                                          # calls of the other planner in between change nothing
+        assert L.pg_gemm_plan(0, _lib.EPI_QKV_LN, 577 * n, 3072, 1024, C.byref(k), C.byref(rows), C.byref(rest)) == 0
+    assert sweep() == first and {n: hip_ops.vit_precise_plan(n) for n in reversed(ns)} == first
+    seen = set()
+    for n, p in first.items():
+        for name in KTOT:
+            S = p[name]
+            assert S in ALLOWED[name], (n, name, S)
+            if S > 1:
+                assert KTOT[name] % S == 0 and (KTOT[name] // S) % 128 == 0, (n, name, S)
+            seen.add((name, S))
+        assert p["fc1_fused"] == (p["fc1"] == 1) and p["attn_x3"], (n, p)
+        # the internal passes: chunks * chunk >= n > chunks * (chunk - 1): sizes chunk and chunk - 1 only, none empty, none above 128
+        assert p["chunks"] == -(-n // 128) and 1 <= p["chunk"] <= 128, (n, p)
+        big = n - p["chunks"] * (p["chunk"] - 1)
+        assert 1 <= big <= p["chunks"] and big * p["chunk"] + (p["chunks"] - big) * (p["chunk"] - 1) == n, (n, p)
+        if n <= 128:
+            assert p["chunk"] == n and p["chunks"] == 1
+        else:                                                      # the routes reported are those of a pass of `chunk` images
+            q = first.get(p["chunk"]) or hip_ops.vit_precise_plan(p["chunk"])
+            assert [p[x] for x in KTOT] == [q[x] for x in KTOT], (n, p, q)
+    assert first[130]["chunk"] == 65 and first[130]["chunks"] == 2 and first[257]["chunk"] == 86 and first[259]["chunk"] == 87
+    # the default cost model reaches every form (a form that disappears from this list is a dead branch worth knowing about)
+    assert {("qkv", 0), ("qkv", 1), ("qkv", 3), ("out", 0), ("out", 1), ("out", 3), ("fc1", 0), ("fc1", 1), ("fc1", 3),
+            ("fc2", 0), ("fc2", 1), ("fc2", 2), ("fc2", 3), ("fc2", 6)} <= seen, sorted(seen)
+    out8 = (C.c_int32 * 8)()
+    assert L.pg_vit_precise_plan(0, out8) == -1 and L.pg_vit_precise_plan(-3, out8) == -1 and L.pg_vit_precise_plan(4, None) == -1
+    try:
+        assert L.pg_tune_gemm_mid(0) == 0
+        off = sweep()
+        assert all(p[name] != 0 for p in off.values() for name in KTOT)
+        assert all(p["fc1_fused"] == (p["fc1"] == 1) for p in off.values())
+        assert L.pg_tune_gemm_mid(1) == 0 and L.pg_tune_exact_fusion(0) == 0
+        unf = sweep()
+        assert all(not p["fc1_fused"] and not p["attn_x3"] for p in unf.values())
+        assert all([p[x] for x in KTOT] == [first[n][x] for x in KTOT] for n, p in unf.items())      # fusion moves no route
+        assert L.pg_tune_exact_fusion(1) == 0 and L.pg_tune_exact_products(2) == 0
+        two = sweep()
+        for n, p in two.items():                                   # two products: K' = 2048 / 8192, parts out of {1, 2} / {1, 2, 4}
+            assert p["qkv"] in (0, 1, 2) and p["out"] in (0, 1, 2) and p["fc1"] in (0, 1, 2) and p["fc2"] in (0, 1, 2, 4), (n, p)
+    finally:
+        L.pg_tune_gemm_mid(1); L.pg_tune_exact_fusion(1); L.pg_tune_exact_products(3)
+    assert sweep() == first
