@@ -41,7 +41,8 @@ extern "C" {
                               * pg_refine_certainty, pg_tune_gemm_raster (round 5); 4: the deferred exact tier -- pg_requeue_append,
                               * pg_rows_to_slots, pg_requeue_take, pg_scatter_rows, pg_head_wstats (round 6); 5: pg_embedding_debias (round 6);
                               * 6: pg_gemm_plan replaces pg_gemm_route;
-                              * 7: pg_vit_precise_plan, pg_op_x3_im2col, pg_op_sum_parts, pg_op_preln, pg_op_attention_x3 */
+                              * 7: pg_vit_precise_plan, pg_op_x3_im2col, pg_op_sum_parts, pg_op_preln, pg_op_attention_x3;
+                              * 7 (+ pg_aux_heads_forward, additive) */
 
 const char* pg_last_error(void);
 int pg_abi_version(void);
@@ -234,6 +235,26 @@ int pg_head_margin(const float* logits, int B, int C, const float* emb, int P, c
  *   Limits: 1 <= kx <= C; kx == C: nothing beyond the list. */
 int pg_head_certainty(const float* logits, int B, int C, const float* emb, int P, const float* W, const int64_t* topk_idx, int kx,
                       const float* beta, const float* wstats, float* tol, int32_t* code, float* margin, float* sens, void* stream);
+
+/* Auxiliary heads of SuperGuessr(multi_task=True) (reference models/super_guessr.py:333-338: multi_task_head 1024 -> 6, climate_layer
+ * 1024 -> 28, month_layer 1024 -> 12) in ONE launch, fp32 end to end, one block per row.
+ *   emb      DEVICE (B,P,1024) fp32, as pg_head_forward takes it (the heads read the mean over the P panels)
+ *   W, bias  DEVICE (A,1024), (A) fp32: rows [regression | climate | month], A = n_reg + n_climate + n_month <= 64;
+ *            any of the three counts may be 0 (n_month = 0: yfcc), not all of them
+ *   beta     DEVICE (1024) fp32 or NULL: the systematic part of the embedding error, as pg_head_certainty takes it
+ *   preds    DEVICE (B,A) fp32 out = mean_p(emb[b]) . W[a] + bias[a]; one fixed summation order per element: a row's bits do not
+ *            depend on B or on the other rows of the batch
+ *   cls      DEVICE (B,2) int64 out: argmax of the climate outputs, argmax of the month outputs (first maximum in torch.argmax's
+ *            order: a NaN ranks above every number, ties go to the lowest index); -1 where the classifier has no outputs
+ *   tol      DEVICE (B) fp32 out: pg_head_certainty's tolerance of the two argmaxes -- the minimum over every alternative class c of
+ *            both classifiers of (m - |e| g.beta) / (|e| |g| / 32), m = preds[c0] - preds[c], g = W[c0] - W[c]; +inf when there is
+ *            no alternative, 0 when a margin is NaN.  The regression outputs are continuous and have none.
+ *   code     DEVICE (B) int32 out: 1 + c when climate class c sets tol, 101 + c for month class c, 0 when nothing does
+ *   row_tol  DEVICE (B) fp32 in/out, may be NULL: if (tol[b] < row_tol[b]) row_tol[b] = tol[b]   (the row's tolerance over all of its
+ *            discrete outputs, e.g. pg_head_certainty's `tol`)
+ * B = 0 is a no-op (buffers may be NULL), B < 0, P < 1, a negative count, A = 0 and A > 64 are PG_EINVAL.  Asynchronous on `stream`. */
+int pg_aux_heads_forward(const float* emb, int B, int P, const float* W, const float* bias, int n_reg, int n_climate, int n_month,
+                         const float* beta, float* preds, int64_t* cls, float* tol, int32_t* code, float* row_tol, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * ProtoRefiner prototype-distance refinement over a CSR prototype bank.

@@ -9,6 +9,10 @@ CLIP_EMBED_DIM = 1024
 GEOCELL_PATH = 'data/geocells_2203.csv'       # PIGEON
 GEOCELL_PATH_YFCC = 'data/geocells_yfcc.csv'  # PIGEOTTO
 
+# Scaler of the six multi-task regression targets (config.py:39-40)
+SCALER_PATH = 'saved_models/scaler/regression.scaler'
+SCALER_PATH_YFCC = 'saved_models/scaler/regression_yfcc.scaler'
+
 # Models (config.py:58-68)
 CURRENT_SAVE_PATH = 'saved_models/WorldCLIP_head_landmarks.model'
 PRETRAINED_CLIP = 'saved_models/StreetviewCLIP.model'

@@ -10,6 +10,7 @@
 //           selection -> top-k probabilities/indices, argmax = first selection, centroid gather (float64).
 #include "common.h"
 #include "pigeon_internal.h"
+#include "certainty_common.h"   // better(): the selection order
 #include <cfloat>
 
 #define HT 64
@@ -72,12 +73,6 @@ __global__ __launch_bounds__(256) void head_logits_kernel(const float* __restric
 }
 
 struct ValIdx { float v; int i; };
-// (value desc, index asc); a NaN ranks above every number (torch.argmax / torch.topk semantics), lowest index first
-__device__ __forceinline__ bool better(float v, int i, float bv, int bi) {
-    const bool vn = v != v, bn = bv != bv;
-    if (vn || bn) return vn && (!bn || i < bi);
-    return (v > bv) || (v == bv && i < bi);
-}
 __device__ __forceinline__ ValIdx block_argbest(ValIdx x, ValIdx* red /*[4]*/) {
 #pragma unroll
     for (int o = 32; o >= 1; o >>= 1) {

@@ -41,6 +41,10 @@ import torch
 from .utils import TopK
 
 
+# what a multi-task model's state carries on top (pg_aux_heads_forward): rank-local reports like tol / margin / sens, never gathered
+AUX_KEYS = ('aux_preds', 'aux_cls', 'aux_tol', 'aux_code')
+
+
 class LocalComm:
     """world_size 1 without any process group: what `certain_forward` / `evaluate_model` (one process, as the reference's evaluate) use."""
     rank, world_size = 0, 1
@@ -100,7 +104,8 @@ class DeferredExact:
         ring['exact'] = torch.zeros((n,), dtype=torch.bool, device=dev)
         self.ring = ring
         loc = {}                                      # this rank's own reports: never gathered, patched through the remap
-        for k in ('tol', 'margin', 'sens') + (('logits',) if self.keep_logits and 'logits' in st else ()):
+        # (aux_*: the auxiliary heads of a multi-task model -- SuperGuessr._head_with_tol -- absent otherwise)
+        for k in ('tol', 'margin', 'sens') + AUX_KEYS + (('logits',) if self.keep_logits and 'logits' in st else ()):
             if k in st and st[k] is not None:
                 loc[k] = torch.zeros((R * B,) + tuple(st[k].shape[1:]), dtype=st[k].dtype, device=dev)
         if self.refiner is not None:
@@ -263,7 +268,7 @@ class DeferredExact:
         k = int(getattr(self.model, 'num_candidates', st['topk_indices'].shape[1]))
         z = lambda dt, *shape: torch.zeros((0,) + shape, dtype=dt, device=dev)     # noqa: E731
         state = {kk: st[kk] for kk in ('embedding', 'topk_values', 'topk_indices', 'preds_LLH', 'preds_geocell', 'tol', 'margin', 'sens',
-                                       'logits') if kk in st}
+                                       'logits') + AUX_KEYS if kk in st}
         state.update(certain=z(torch.bool), exact=z(torch.bool), cause=z(torch.int32), pixel_values=None)
         res = dict(embedding=st['embedding'], topk_indices=st['topk_indices'][:, :k], topk_values=st['topk_values'][:, :k],
                    preds_LLH=st['preds_LLH'], preds_geocell=st['preds_geocell'], index=z(torch.int64), certain=z(torch.bool),
@@ -433,9 +438,11 @@ def round_quantum(px_rows: torch.Tensor, tokens: int = 577, panel_rows: int = 25
     return max(1, images // views)
 
 
-def as_model_output(model, res: dict, labels=None, labels_clf=None):
+def as_model_output(model, res: dict, labels=None, labels_clf=None, labels_multi_task=None, labels_climate=None, labels_month=None):
     """One emitted result -> what `SuperGuessr.forward` returns for this rank's rows (ModelOutput or the serving tuple)."""
-    return model.package(dict(res['state']), labels, labels_clf)
+    if labels_multi_task is None and labels_climate is None and labels_month is None:
+        return model.package(dict(res['state']), labels, labels_clf)
+    return model.package(dict(res['state']), labels, labels_clf, labels_multi_task, labels_climate, labels_month)
 
 
 __all__ = ['DeferredExact', 'LocalComm', 'as_model_output', 'round_quantum', 'TopK']

@@ -42,12 +42,52 @@ def topk_geocell_accuracy(cell_labels: np.ndarray, topk_preds: np.ndarray) -> fl
     return num_correct / len(cell_labels)
 
 
-def compute_geoguessr_metrics(results) -> Dict[str, float]:
-    """reference evaluation/metrics.py:138-181 on the 11-tuple evaluate_model builds (train_eval_loop.py:138-140):
+def mae(labels: np.ndarray, preds: np.ndarray) -> float:
+    """reference evaluation/metrics.py:22-27"""
+    return np.mean(np.abs(labels - preds))
+
+
+def load_scaler(yfcc: bool = False):
+    """The fitted scaler of the six regression targets (reference evaluation/metrics.py:43-44: joblib.load of
+    config.SCALER_PATH(_YFCC)), or None when the file is not there."""
+    import os
+    from . import config as cfg
+    path = cfg.SCALER_PATH_YFCC if yfcc else cfg.SCALER_PATH
+    if not os.path.exists(path):
+        return None
+    import joblib
+    return joblib.load(path)
+
+
+def recover_regression_values(values: np.ndarray, yfcc: bool = False, scaler=None) -> np.ndarray:
+    """reference evaluation/metrics.py:29-54: undo the scaler, the log transform of every variable but the average temperature,
+    and the offsets (elevation 408, or 416 with yfcc; 1 for the other log-transformed ones).  `scaler`: anything with
+    `inverse_transform` (default: the file config.SCALER_PATH(_YFCC) names)."""
+    if scaler is None:
+        scaler = load_scaler(yfcc)
+        if scaler is None:
+            raise FileNotFoundError('recover_regression_values: no scaler given and no scaler file at config.SCALER_PATH(_YFCC)')
+    vals = np.array(scaler.inverse_transform(np.asarray(values)))
+    vals[:, :2] = np.exp(vals[:, :2])
+    vals[:, 3:] = np.exp(vals[:, 3:])
+    return vals - np.array([416 if yfcc else 408, 1, 0, 1, 1, 1]).transpose()
+
+
+def _class_labels(labels) -> np.ndarray:
+    labels = np.asarray(labels)
+    return np.argmax(labels, axis=-1) if labels.ndim > 1 else labels          # (N, classes) one-hot / probabilities, or (N,) indices
+
+
+def compute_geoguessr_metrics(results, scaler=None) -> Dict[str, float]:
+    """reference evaluation/metrics.py:138-199 on the 11-tuple evaluate_model builds (train_eval_loop.py:138-140):
     the km-error statistics, the Under_*_km fractions, the GeoGuessr score and the geocell (top-k) accuracies, under the
-    reference's keys.  Left out: `Country_accuracy` (geopandas country polygons, absent here)
-    and the multi-task regressions (training-only heads).  Host numpy on the collected predictions, as in the reference."""
-    predictions, cell_preds, _, _, _, top5_geocells, labels, cell_labels, _, _, _ = results
+    reference's keys; with multi-task labels (`labels_mt` not None, :184-199) also `Climate_accuracy`, `Month_accuracy` (when there
+    are month labels) and -- when a scaler is available: the `scaler` keyword, or the file config.SCALER_PATH(_YFCC) names -- the six
+    `Mean_*_error` entries on the recovered regression values.  Climate labels may be class indices or the (N, 28) one-hot rows
+    the model's forward takes.  Left out: `Country_accuracy` (geopandas country polygons, absent here).
+    Host numpy on the collected predictions, as in the reference."""
+    predictions, cell_preds, preds_mt, preds_climate, preds_month, top5_geocells, labels, cell_labels, labels_mt, labels_climate, \
+        labels_month = results
     cell_labels = np.asarray(cell_labels)
     if cell_labels.ndim > 1:
         cell_labels = np.argmax(cell_labels, axis=-1)
@@ -58,12 +98,26 @@ def compute_geoguessr_metrics(results) -> Dict[str, float]:
     eval_dict['Geoguessr_score'] = geoguessr_score(distances)
     eval_dict['Geocell_accuracy'] = float(np.mean(cell_labels == np.asarray(cell_preds)))      # sklearn accuracy_score
     eval_dict['Geocell_top5_accuracy'] = topk_geocell_accuracy(cell_labels, top5_geocells)
+    if labels_mt is not None:                                                  # :184-199
+        yfcc = labels_month is None                                            # :163
+        if scaler is None:
+            scaler = load_scaler(yfcc)
+        if scaler is None:
+            print('compute_geoguessr_metrics: no regression scaler (config.SCALER_PATH) -- the six Mean_*_error entries are left out')
+        else:
+            p_mt = recover_regression_values(np.asarray(preds_mt), yfcc, scaler)
+            l_mt = recover_regression_values(np.asarray(labels_mt), False, scaler)     # :186 as the reference: the labels without `yfcc`
+            for i, name in enumerate(('elevation', 'population', 'temperature', 'temp_diff', 'precipitation', 'prec_diff')):
+                eval_dict[f'Mean_{name}_error'] = mae(l_mt[:, i], p_mt[:, i])
+        eval_dict['Climate_accuracy'] = float(np.mean(_class_labels(labels_climate) == np.argmax(np.asarray(preds_climate), axis=-1)))
+        if not yfcc:
+            eval_dict['Month_accuracy'] = float(np.mean(_class_labels(labels_month) == np.argmax(np.asarray(preds_month), axis=-1)))
     return eval_dict
 
 
 @torch.no_grad()
 def certain_forward(model: SuperGuessr, refiner: Optional[ProtoRefiner], pixel_values=None, embedding=None, labels=None,
-                    labels_clf=None, **_unused):
+                    labels_clf=None, labels_multi_task=None, labels_climate=None, labels_month=None, **_unused):
     """`model(**data)` followed by `refiner(...)` with the reference's discrete outputs (a z ~ 4 statistical statement for the samples called certain, pigeon_amd/certainty.py): one fast pass, the tolerance of every
     discrete decision downstream of the embedding -- the top-1 cell (pg_head_certainty) and, with a refiner, the winning candidate,
     the candidate-set boundary, the nearest prototype and the farthest member (pg_refine_certainty) -- and ONE exact pass
@@ -74,14 +128,20 @@ def certain_forward(model: SuperGuessr, refiner: Optional[ProtoRefiner], pixel_v
     Returns (outputs as `model.forward` returns them, info) with info = dict(certain (B,) bool: every output of the sample is the
     reference's; cause (B,) int32: why a sample was not certain after the fast pass; reencoded (n,) int64; head_tol, refine_tol,
     refine_code (B,) or None; boundary_checked; refined_LLH (B,2) f32 / refined_geocell (B,) i64: the refinement's result -- the
-    caller need not run the refiner again)."""
+    caller need not run the refiner again; multi-task models: aux_tol (B,) f32 the tolerance of the climate and month argmaxes,
+    aux_code (B,) i32 which class sets it -- `head_tol` is already the minimum over the geocell, climate and month decisions)."""
     res = model.engine(refiner).submit(pixel_values, embedding)[0]
     st = dict(res['state'])
-    out = model.package(st, labels, labels_clf)
+    if getattr(model, 'multi_task', False):
+        out = model.package(st, labels, labels_clf, labels_multi_task, labels_climate, labels_month)
+    else:
+        out = model.package(st, labels, labels_clf)
     info = dict(certain=st['certain'], cause=st['cause'], head_tol=st['tol'], refine_tol=st.get('refine_tol'),
                 refine_code=st.get('refine_code'), boundary_checked=model.engine(refiner).boundary_checked if refiner is not None else None,
                 reencoded=torch.nonzero(st['exact']).flatten(), refined_LLH=st.get('refined_LLH'),
                 refined_geocell=st.get('refined_geocell'))
+    if 'aux_tol' in st:
+        info['aux_tol'], info['aux_code'] = st['aux_tol'], st['aux_code']
     model.last_certain = info['certain']
     return out, info
 
@@ -105,6 +165,9 @@ def evaluate_model(model: SuperGuessr, dataset, metrics: Optional[Callable] = No
         refiner.eval()
     combined_preds, combined_geocell_preds, combined_top5_cells, combined_top5_probs = [], [], [], []
     combined_loss = 0.0
+    combined_preds_mt, combined_preds_climate, combined_preds_month = [], [], []
+    combined_loss_mt = [0.0, 0.0, 0.0]                     # reg, climate, month
+    multi_task = bool(getattr(model, 'multi_task', False))
     combined_certain = []
     n_seen = 0
     # The reference's loop (:77-112) computes a batch and appends its predictions; the predictions are only read after the loop
@@ -119,9 +182,23 @@ def evaluate_model(model: SuperGuessr, dataset, metrics: Optional[Callable] = No
         nonlocal combined_loss, n_seen
         for res in done:
             meta = res['meta']
-            outputs = model.package(dict(res['state']), meta.get('labels'), meta.get('labels_clf'))
+            if multi_task:
+                outputs = model.package(dict(res['state']), meta.get('labels'), meta.get('labels_clf'), meta.get('labels_multi_task'),
+                                        meta.get('labels_climate'), meta.get('labels_month'))
+            else:
+                outputs = model.package(dict(res['state']), meta.get('labels'), meta.get('labels_clf'))
             if outputs.loss_clf is not None:
                 combined_loss = combined_loss + outputs.loss_clf.detach() * meta['n_keys']   # :81-82 (`len(data)` as the reference)
+            # :84-95.  The reference decides with `outputs.loss_reg > 0` -- a comparison of a device value on the host, i.e. a
+            # synchronisation per step, which this loop does not do: decided from what the host knows (a multi-task model, and the
+            # batch came with regression labels)
+            if multi_task and meta.get('labels_multi_task') is not None:
+                for i, l in enumerate((outputs.loss_reg, outputs.loss_climate, outputs.loss_month)):
+                    combined_loss_mt[i] = combined_loss_mt[i] + (l.detach() if torch.is_tensor(l) else l) * meta['n_keys']
+                combined_preds_mt.append(outputs.preds_mt)
+                combined_preds_climate.append(outputs.preds_climate)
+                if outputs.preds_month is not None:
+                    combined_preds_month.append(outputs.preds_month)
             # :98-103: the refinement is the one the engine already ran (and re-ran for the rows the exact tier re-encoded)
             combined_preds.append(res['refined_LLH'] if refiner is not None else outputs.preds_LLH)
             combined_geocell_preds.append(outputs.preds_geocell)                 # :106-112
@@ -134,7 +211,9 @@ def evaluate_model(model: SuperGuessr, dataset, metrics: Optional[Callable] = No
     with torch.no_grad():
         for data in eval_data:
             # :80 `model(**data)` and :98 `refiner(...)`, with what the refiner will consume checked as well
-            keep = {'labels': data.get('labels'), 'labels_clf': data.get('labels_clf'), 'n_keys': len(data)}
+            keep = {'labels': data.get('labels'), 'labels_clf': data.get('labels_clf'), 'n_keys': len(data),
+                    'labels_multi_task': data.get('labels_multi_task'), 'labels_climate': data.get('labels_climate'),
+                    'labels_month': data.get('labels_month')}
             collect(engine.submit(data.get('pixel_values'), data.get('embedding'), meta=keep))
         collect(engine.flush())
     dropped = engine.check_nothing_dropped()
@@ -152,12 +231,23 @@ def evaluate_model(model: SuperGuessr, dataset, metrics: Optional[Callable] = No
         # how many samples are STILL not certain after the exact tier (judged at its floor): their outputs are returned as computed
         results['uncertain_after_exact'] = int((~results['geocell_certain']).sum())
         results['exact_passes'] = [dict(f) for f in engine.flush_log]
+    preds_mt = preds_climate = preds_month = None
+    if combined_preds_mt:                                                         # :126-135
+        preds_mt, preds_climate = to_np(combined_preds_mt), to_np(combined_preds_climate)
+        preds_month = to_np(combined_preds_month) if combined_preds_month else None
+        results.update(preds_mt=preds_mt, preds_climate=preds_climate, preds_month=preds_month,
+                       loss_reg=float(combined_loss_mt[0]) / max(n_seen, 1), loss_climate=float(combined_loss_mt[1]) / max(n_seen, 1),
+                       loss_month=float(combined_loss_mt[2]) / max(n_seen, 1))
     if metrics is not None:                                                       # :122-140
         labels_lla, labels_cell = dataset['labels'], dataset['labels_clf']
         if isinstance(labels_lla, np.ndarray) == False:
             labels_lla, labels_cell = np.asarray(labels_lla), np.asarray(labels_cell)
-        results.update(metrics((preds, preds_geocells, None, None, None, top5_geocells,
-                                labels_lla, labels_cell, None, None, None)))
+        labels_mt = labels_climate = labels_month = None
+        if preds_mt is not None:
+            labels_mt, labels_climate = np.asarray(dataset['labels_multi_task']), np.asarray(dataset['labels_climate'])
+            labels_month = np.asarray(dataset['labels_month']) if preds_month is not None else None
+        results.update(metrics((preds, preds_geocells, preds_mt, preds_climate, preds_month, top5_geocells,
+                                labels_lla, labels_cell, labels_mt, labels_climate, labels_month)))
     model.train()
     logger.warning('Back to training ...')
     return results
@@ -165,7 +255,7 @@ def evaluate_model(model: SuperGuessr, dataset, metrics: Optional[Callable] = No
 
 def evaluate(model: str, dataset, yfcc: bool, landmarks: bool, base_model=None, heading: bool = False,
              refine: bool = True, geocell_path: Optional[str] = None, proto_path: Optional[str] = None,
-             dataset_path=None, bank=None, head_state: Optional[str] = None):
+             dataset_path=None, bank=None, head_state: Optional[str] = None, multi_task: bool = False):
     """reference evaluation/evaluate.py:10-85.
 
     `base_model`: as in the reference a STRING -- config.CLIP_MODEL for the pretrained tower, or the path of a checkpoint whose
@@ -178,6 +268,9 @@ def evaluate(model: str, dataset, yfcc: bool, landmarks: bool, base_model=None, 
     file `<proto_model_path>.npz` this package writes at its first build, or the reference's own pickle at
     `proto_model_path` (`torch.save(refiner, ...)`, read with `load_refiner_cache` -- an existing
     saved_models/refiner/proto.refiner keeps working).
+    `multi_task` (the reference's evaluate hard-wires False, :43; its `run.py -m` trains such models): build the model with the
+    regression, climate and month heads, so that a multi-task checkpoint loads completely and the multi-task metrics are reported
+    when the dataset carries `labels_multi_task` / `labels_climate` / `labels_month`.
     """
     import os
     from . import config as cfg
@@ -203,7 +296,7 @@ def evaluate(model: str, dataset, yfcc: bool, landmarks: bool, base_model=None, 
                                    f'({why})') from why
             base_model = HipCLIPVisionModel(state_dict)
             print(f'Initialized base model with weights from: {path} (pretrained tower unavailable: checkpoint only)')
-    full_model = SuperGuessr(base_model, panorama=True, hierarchical=False, multi_task=False, heading=heading,
+    full_model = SuperGuessr(base_model, panorama=True, hierarchical=False, multi_task=multi_task, heading=heading,
                              freeze_base=True, yfcc=yfcc, num_candidates=50, geocell_path=geocell_path)
     # the reference's torch.load raises on a missing checkpoint (:46); only the explicit random-init names skip loading
     for ckpt in (head_state, model):

@@ -497,6 +497,38 @@ def head_certainty(logits: torch.Tensor, emb: torch.Tensor, W: torch.Tensor, top
     return tol, code, margin, sens
 
 
+def aux_heads_forward(emb: torch.Tensor, W: torch.Tensor, bias: torch.Tensor, n_reg: int, n_climate: int, n_month: int,
+                      drift: Optional[torch.Tensor] = None, row_tol: Optional[torch.Tensor] = None):
+    """pg_aux_heads_forward: the auxiliary heads of SuperGuessr(multi_task=True) in one launch.  emb (B,P,1024) or (B,1024) fp32,
+    W (A,1024) / bias (A,) fp32 with rows [regression | climate | month], A = n_reg + n_climate + n_month <= 64, drift (1024,) fp32 or
+    None, row_tol (B,) fp32 or None: lowered IN PLACE to the minimum of itself and the returned tolerance.  Returns dict(preds (B,A)
+    f32, cls (B,2) i64 = [argmax climate, argmax month] (-1: no such classifier), tol (B,) f32, code (B,) i32 = 1 + climate class /
+    101 + month class that sets tol, 0 = none)."""
+    _dev(emb, torch.float32); _dev(W, torch.float32); _dev(bias, torch.float32)
+    if emb.dim() not in (2, 3):
+        raise _lib.PigeonHipError(f"emb must be (B,{HIDDEN}) or (B,P,{HIDDEN}), got {tuple(emb.shape)}")
+    B = emb.shape[0]
+    P = emb.shape[1] if emb.dim() == 3 else 1
+    _shape(emb, "emb", *((B, P, HIDDEN) if emb.dim() == 3 else (B, HIDDEN)))
+    n_reg, n_climate, n_month = int(n_reg), int(n_climate), int(n_month)
+    if min(n_reg, n_climate, n_month) < 0:
+        raise _lib.PigeonHipError(f"aux_heads: negative output count (n_reg={n_reg} n_climate={n_climate} n_month={n_month})")
+    A = n_reg + n_climate + n_month
+    _shape(W, "W", A, HIDDEN); _shape(bias, "bias", A)
+    if drift is not None:
+        _dev(drift, torch.float32); _shape(drift, "drift", HIDDEN)
+    if row_tol is not None:
+        _dev(row_tol, torch.float32); _shape(row_tol, "row_tol", B)
+    dev = emb.device
+    preds = torch.empty((B, A), dtype=torch.float32, device=dev)
+    cls = torch.empty((B, 2), dtype=torch.int64, device=dev)
+    tol = torch.empty((B,), dtype=torch.float32, device=dev)
+    code = torch.empty((B,), dtype=torch.int32, device=dev)
+    check(load().pg_aux_heads_forward(_p(emb), B, P, _p(W), _p(bias), n_reg, n_climate, n_month, _p(drift), _p(preds), _p(cls),
+                                      _p(tol), _p(code), _p(row_tol), _stream()), "pg_aux_heads_forward")
+    return dict(preds=preds, cls=cls, tol=tol, code=code)
+
+
 def embedding_debias(emb: torch.Tensor, bias: torch.Tensor) -> torch.Tensor:
     """pg_embedding_debias, in place: emb[r] -= |emb[r]| * bias for every row of the (n,1024) fp32 matrix `emb` (contiguous; any
     leading shape).  bias (1024,) fp32: the calibrated systematic part of the 16-bit encoder's error (pigeon_amd/certainty.py)."""

@@ -71,11 +71,13 @@ def predict_panorama(views: Sequence, model, refiner=None, preprocess: Optional[
             # pigeon_amd.SuperGuessr: the same call with the certainty of every discrete output (top-1 cell AND what the refiner below
             # will pick) checked, and the panorama re-encoded in the exact mode if it is not certain (exact_top1, the default)
             from .evaluate import certain_forward
-            (pred_llh, topk, embedding), info = certain_forward(model, refiner, pixel_values=px)
+            out, info = certain_forward(model, refiner, pixel_values=px)
+            pred_llh, topk, embedding = out[0], out[1], out[-1]    # multi-task models put preds_mt in between (:463-464)
             if refiner is not None:
                 pred_llh = info["refined_LLH"]                     # the refinement certain_forward ran (once; re-run for re-encoded rows)
         else:
-            pred_llh, topk, embedding = model(pixel_values=px)     # serving tuple, [lng, lat] order (:455, :462-466)
+            out = model(pixel_values=px)                           # serving tuple, [lng, lat] order (:455, :462-466)
+            pred_llh, topk, embedding = out[0], out[1], out[-1]    # 3 elements, or 4 with preds_mt third (multi-task, :463-464)
             if refiner is not None:
                 _, pred_llh, _ = refiner(embedding=embedding, initial_preds=pred_llh, candidate_cells=topk.indices,
                                          candidate_probs=topk.values)

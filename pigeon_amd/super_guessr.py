@@ -2,13 +2,17 @@
 
 Mirrors reference models/super_guessr.py (same constructor signature, `load_geocells`, `load_state`,
 `forward(pixel_values | embedding, ..., labels_clf, ...)` returning `ModelOutput` or the serving tuple).
-Only the inference branch that evaluation/evaluate.py:42-44 constructs is accelerated and supported:
-`hierarchical=False, multi_task=False, heading=False`.  The training-only options raise NotImplementedError
-(SURVEY.md section 2 row 4 lists them as out of scope).
+The inference branch is accelerated and supported: the configuration evaluation/evaluate.py:42-44 constructs
+(`hierarchical=False`, `heading` as the caller passes it: a no-op with `panorama=True`, :273-274) and `multi_task=True`
+(:316-348: the regression, climate and month heads of a multi-task checkpoint -- pg_aux_heads_forward, one launch, with the
+tolerance of the climate and month argmaxes taking part in the decision which rows go to the exact tier).  `hierarchical=True`
+and the 1026-wide heading head (`heading=True` without `panorama`) raise NotImplementedError: the reference's final model uses
+neither (models/README.md).  Training is out of scope: the losses are computed for logging only.
 """
 from __future__ import annotations
 
 import os
+from collections import namedtuple
 
 import numpy as np
 import pandas as pd
@@ -22,6 +26,15 @@ from .geo_utils import haversine_matrix, smooth_labels
 from .clip_embedder import HipCLIPVisionModel
 from .config import CLIP_EMBED_DIM, GEOCELL_PATH, GEOCELL_PATH_YFCC
 from .utils import ModelOutput, TopK, resolve_name
+
+# reference models/super_guessr.py:12-23
+MultiTaskPredictions = namedtuple('MultiTaskPredictions', 'loss_reg preds_mt loss_climate preds_climate loss_month preds_month')
+NUM_MULTI_TASK_VARIABLES = 6
+REGRESSION_LOSS_SCALING = 8
+NUM_CLIMATES = 28
+CLIMATE_LOSS_SCALING = 2
+NUM_MONTHS = 12
+MONTHS_LOSS_SCALING = 1
 
 
 # candidates the head computes beyond `num_candidates`: never exposed, they tell the certainty pass how far the next cells are
@@ -76,9 +89,14 @@ class SuperGuessr(nn.Module):
         self.last_state = None
         if len(kwargs) > 0:
             print(f'Not using keyword arguments: {list(kwargs.keys())}')
-        if hierarchical or multi_task or heading:
-            raise NotImplementedError('pigeon_amd.SuperGuessr implements the inference configuration of '
-                                      'evaluation/evaluate.py:42-44 (hierarchical=False, multi_task=False, heading=False)')
+        if hierarchical:
+            raise NotImplementedError('pigeon_amd.SuperGuessr: hierarchical=True (the self-attention combiner of the four panels, '
+                                      'models/super_guessr.py:95-103,417-433) is not implemented; the reference\'s final model '
+                                      'averages the panels (hierarchical=False)')
+        if heading and not panorama:
+            raise NotImplementedError('pigeon_amd.SuperGuessr: heading=True without panorama=True (the 1026-wide cell_layer fed with '
+                                      'the compass heading, models/super_guessr.py:90-92,276-297) is not implemented; with '
+                                      'panorama=True the heading is ignored, as in the reference (:273-274)')
 
         self.base_model = base_model
         self.panorama = panorama
@@ -101,6 +119,16 @@ class SuperGuessr(nn.Module):
 
         self.cell_layer = nn.Linear(self.input_dim, self.num_cells)
         self.softmax = nn.Softmax(dim=-1)
+        if self.multi_task:                                  # :110-124, under the reference's attribute names (= state dict keys)
+            print('Model is multi-task.')
+            self.multi_task_head = nn.Linear(self.hidden_size, NUM_MULTI_TASK_VARIABLES)
+            self.loss_fnc_mt = nn.MSELoss(reduction='mean')
+            self.climate_layer = nn.Linear(self.input_dim, NUM_CLIMATES)
+            self.loss_fnc_climate = nn.CrossEntropyLoss()
+            if not self.yfcc:
+                self.month_layer = nn.Linear(self.input_dim, NUM_MONTHS)
+                self.loss_fnc_month = nn.CrossEntropyLoss()
+        self._aux_pack = None                                # (key, W (A,1024), bias (A,)): see _aux_weights()
         self._freeze_params()
         self.loss_fnc = nn.CrossEntropyLoss()
         self._hip_base = None
@@ -173,6 +201,7 @@ class SuperGuessr(nn.Module):
         self.certainty = Certainty(self.certainty.kappa, self._rel_tol0, self.certainty.rel_tol_exact, debias=self.certainty.debias)
         self._cal_buffer = []
         self._engines = {}
+        self._aux_pack = None
 
     def state_dict(self, *args, **kwargs):
         sd = super().state_dict(*args, **kwargs)
@@ -221,6 +250,22 @@ class SuperGuessr(nn.Module):
             self._wnorm[exact] = (key, hip_ops.head_wstats(Wd.contiguous(), drift))
         return self._wnorm[exact][1]
 
+    def _aux_layers(self):
+        return [self.multi_task_head, self.climate_layer] + ([] if self.yfcc else [self.month_layer])
+
+    def _aux_weights(self):
+        """(W (A,1024), bias (A,)) fp32 on the head's device: the rows of multi_task_head, climate_layer and month_layer one after the
+        other, as pg_aux_heads_forward takes them.  Packed once; packed again when any of the layers' tensors is replaced, edited in
+        place (its version) or moved."""
+        ts = [t for l in self._aux_layers() for t in (l.weight, l.bias)]
+        key = tuple((t.data_ptr(), t._version, str(t.device), t.dtype) for t in ts)
+        if self._aux_pack is None or self._aux_pack[0] != key:
+            dev = self.cell_layer.weight.device
+            W = torch.cat([l.weight.data.to(dev, torch.float32) for l in self._aux_layers()]).contiguous()
+            b = torch.cat([l.bias.data.to(dev, torch.float32) for l in self._aux_layers()]).contiguous()
+            self._aux_pack = (key, W, b)
+        return self._aux_pack[1], self._aux_pack[2]
+
     def _panels(self) -> int:
         return 4 if self.panorama else 1
 
@@ -241,6 +286,14 @@ class SuperGuessr(nn.Module):
         drift = None if exact else self.certainty.drift_on(W.device)
         o['tol'], o['code'], o['margin'], o['sens'] = hip_ops.head_certainty(o['logits'], head_in, W, o['topk_indices'], drift,
                                                                              self.wstats(exact))
+        if self.multi_task:
+            # :333-338 the regression, climate and month layers on the same rows, one launch.  The climate and month argmaxes
+            # (evaluation/metrics.py:187,198) are discrete outputs like the top-1 cell: their tolerance lowers the row's (`row_tol`,
+            # in place), so a row that only they cannot settle goes to the exact tier too
+            Wa, ba = self._aux_weights()
+            a = hip_ops.aux_heads_forward(head_in, Wa, ba, NUM_MULTI_TASK_VARIABLES, NUM_CLIMATES, 0 if self.yfcc else NUM_MONTHS,
+                                          drift=drift, row_tol=o['tol'])
+            o['aux_preds'], o['aux_cls'], o['aux_tol'], o['aux_code'] = a['preds'], a['cls'], a['tol'], a['code']
         return o
 
     @torch.no_grad()
@@ -331,14 +384,24 @@ class SuperGuessr(nn.Module):
         thr = torch.where(st['exact'], self.certainty.threshold(True), self.certainty.threshold(False))
         return st['sens'] * thr
 
-    def package(self, st: dict, labels: Tensor = None, labels_clf: Tensor = None):
+    def package(self, st: dict, labels: Tensor = None, labels_clf: Tensor = None, labels_multi_task: Tensor = None,
+                labels_climate: Tensor = None, labels_month: Tensor = None):
         """State -> the reference's outputs (:459-483).  The state's reference to the input pixels is dropped here (it was only
-        needed for a possible re-encode): `last_state` must not keep a whole batch of pixels alive."""
+        needed for a possible re-encode): `last_state` must not keep a whole batch of pixels alive.
+
+        Multi-task (:316-348, :463-464, :477): `preds_mt / preds_climate / preds_month` are the columns of the state's `aux_preds`
+        (contiguous copies; `preds_month` None with yfcc), the three losses the reference's expressions through torch's loss modules
+        -- logged values like `loss_clf`, no gradients.  `labels_climate` is what torch's CrossEntropyLoss accepts after the
+        reference's float cast (:342): (B, 28) class probabilities / one-hot rows.  A loss whose labels were not given is 0 (the
+        reference would raise on None there)."""
         self._publish(st)
         st['pixel_values'] = None
         k = self.num_candidates
         geocell_topk = TopK(st['topk_values'][:, :k], st['topk_indices'][:, :k])
+        mt = self._multi_task_predictions(st, labels_multi_task, labels_climate, labels_month)
         if not self.training and self.serving:                              # :462-466
+            if self.multi_task:
+                return st['preds_LLH'], geocell_topk, mt.preds_mt, st['embedding']
             return st['preds_LLH'], geocell_topk, st['embedding']
         dev = st['logits'].device
         loss_clf = None
@@ -348,8 +411,31 @@ class SuperGuessr(nn.Module):
                 distances = haversine_matrix(labels.to(dev), self.lla_geocells.data.t())
                 label_probs = smooth_labels(distances)
             loss_clf = self.loss_fnc(st['logits'], label_probs)
-        return ModelOutput(loss_clf, loss_clf, 0, 0, 0, st['preds_LLH'], st['preds_geocell'], None, None, None,
-                           geocell_topk, st['embedding'])
+        loss = loss_clf
+        if self.multi_task and loss_clf is not None:                        # :477
+            loss = loss_clf + mt.loss_reg + mt.loss_climate + mt.loss_month
+        return ModelOutput(loss, loss_clf, mt.loss_reg, mt.loss_climate, mt.loss_month, st['preds_LLH'], st['preds_geocell'],
+                           mt.preds_mt, mt.preds_climate, mt.preds_month, geocell_topk, st['embedding'])
+
+    def _multi_task_predictions(self, st: dict, labels_multi_task: Tensor = None, labels_climate: Tensor = None,
+                                labels_month: Tensor = None) -> MultiTaskPredictions:
+        """:316-348 on what pg_aux_heads_forward left in the state."""
+        if not self.multi_task:
+            return MultiTaskPredictions(0, None, 0, None, 0, None)
+        ap = st['aux_preds']
+        dev = ap.device
+        r, c = NUM_MULTI_TASK_VARIABLES, NUM_MULTI_TASK_VARIABLES + NUM_CLIMATES
+        preds_mt, preds_climate = ap[:, :r].contiguous(), ap[:, r:c].contiguous()
+        preds_month = None if self.yfcc else ap[:, c:].contiguous()
+        loss_reg = loss_climate = loss_month = 0
+        if not self.serving:                                                # :340-345
+            if labels_multi_task is not None:
+                loss_reg = self.loss_fnc_mt(preds_mt, labels_multi_task.to(dev)) * REGRESSION_LOSS_SCALING
+            if labels_climate is not None:
+                loss_climate = self.loss_fnc_climate(preds_climate, labels_climate.to(dev, dtype=torch.float32)) * CLIMATE_LOSS_SCALING
+            if preds_month is not None and labels_month is not None:
+                loss_month = self.loss_fnc_month(preds_month, labels_month.to(dev)) * MONTHS_LOSS_SCALING
+        return MultiTaskPredictions(loss_reg, preds_mt, loss_climate, preds_climate, loss_month, preds_month)
 
     def forward(self, pixel_values: Tensor = None, embedding: Tensor = None, heading: Tensor = None,
                 labels: Tensor = None, labels_clf: Tensor = None, labels_multi_task: Tensor = None,
@@ -357,7 +443,9 @@ class SuperGuessr(nn.Module):
         """Inference branch of reference models/super_guessr.py:350-483.
 
         pixel_values (B,12,336,336) [panorama] or (B,3,336,336); or embedding (B,4,1024)/(B,1024).
-        Returns ModelOutput (or, with serving=True in eval mode, the (pred_LLH, topk, embedding) tuple, :462-466).
+        Returns ModelOutput (or, with serving=True in eval mode, the (pred_LLH, topk, embedding) tuple -- multi-task:
+        (pred_LLH, topk, preds_mt, embedding) --, :462-466).  `heading` is ignored: the only configuration that accepts
+        heading=True is the one in which the reference ignores it too (:273-274).
         """
         self._assert_requirements(pixel_values, embedding, heading)
         if not self.cell_layer.weight.is_cuda:
@@ -366,7 +454,7 @@ class SuperGuessr(nn.Module):
             # fast pass, tolerance of the top-1 against every cell, exact re-encode of the samples that are not certain
             # (pigeon_amd.deferred, settled before this call returns: one host synchronisation)
             res = self.engine(None).submit(pixel_values, embedding)[0]
-            return self.package(dict(res['state']), labels, labels_clf)
+            return self.package(dict(res['state']), labels, labels_clf, labels_multi_task, labels_climate, labels_month)
 
     def engine(self, refiner=None, **kw):
         """The settle-before-return form of pigeon_amd.deferred.DeferredExact for (this model, `refiner`), built once."""

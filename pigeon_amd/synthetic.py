@@ -189,6 +189,15 @@ def make_head_weights(num_cells: int, seed: int = 0, embed_dim: int = HIDDEN):
     return W, b
 
 
+def make_aux_head_weights(seed: int = 0, yfcc: bool = False, embed_dim: int = HIDDEN):
+    """The auxiliary layers of SuperGuessr(multi_task=True) at nn.Linear's default init (`make_head_weights`), as a state dict under
+    the reference's names: multi_task_head (6), climate_layer (28) and -- unless yfcc -- month_layer (12)."""
+    sd = {}
+    for i, (name, n) in enumerate((('multi_task_head', 6), ('climate_layer', 28)) + ((() if yfcc else (('month_layer', 12),)))):
+        sd[f'{name}.weight'], sd[f'{name}.bias'] = make_head_weights(n, seed=seed + 101 * (i + 1), embed_dim=embed_dim)
+    return sd
+
+
 class SyntheticBank:
     """A CSR prototype bank + its training-embedding bank, in the arrays the kernels consume.
 

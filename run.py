@@ -11,6 +11,7 @@ replaced by seeded synthetic fixtures:  `--synthetic N` embeds / evaluates N syn
   python run.py embed saved_models/StreetviewCLIP.model -l data/hf_dataset          # weights from a checkpoint
   python run.py embed random --synthetic 64                                        # plumbing check, random ViT
   python run.py evaluate saved_models/head.model -l data/hf_eval -b saved_models/StreetviewCLIP.model
+  python run.py evaluate saved_models/head_mt.model -m -l data/hf_eval -b saved_models/StreetviewCLIP.model   (a multi-task checkpoint)
   torchrun --nproc-per-node 8 --master-addr 127.0.0.1 run.py embed random --synthetic 4096
 """
 import argparse
@@ -143,7 +144,8 @@ def _dispatch(args, comm):
             if not args.yfcc:
                 dataset = dataset['test'] if args.test else dataset['val']
         results = evaluate(args.name, dataset, yfcc=args.yfcc, base_model=_vision_model(args), refine=True,
-                           landmarks=args.landmarks, geocell_path=geocell_path, bank=bank)
+                           landmarks=args.landmarks, geocell_path=geocell_path, bank=bank, heading=args.heading,
+                           multi_task=args.multitask)
         if comm.is_main_process:
             print({k: (v if not hasattr(v, 'shape') or v.shape == () else tuple(v.shape)) for k, v in results.items() if k != 'exact_passes'})
             if 'geocell_certain' in results:
