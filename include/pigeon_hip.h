@@ -42,7 +42,7 @@ extern "C" {
                               * pg_rows_to_slots, pg_requeue_take, pg_scatter_rows, pg_head_wstats (round 6); 5: pg_embedding_debias (round 6);
                               * 6: pg_gemm_plan replaces pg_gemm_route;
                               * 7: pg_vit_precise_plan, pg_op_x3_im2col, pg_op_sum_parts, pg_op_preln, pg_op_attention_x3;
-                              * 7 (+ pg_aux_heads_forward, additive) */
+                              * 7 (+ pg_aux_heads_forward, additive; + pg_fingerprint, pg_vit_fingerprint, additive) */
 
 const char* pg_last_error(void);
 int pg_abi_version(void);
@@ -125,6 +125,24 @@ int pg_vit_graph(pg_vit* h, int on, int64_t* replays, int64_t* captures);
 int pg_vit_destroy(pg_vit* h);
 /* The operand format the handle resolved to (PG_DTYPE_F16 or PG_DTYPE_BF16). */
 int pg_vit_mma_dtype(const pg_vit* h);
+
+/* WEIGHT FINGERPRINT: the key of a stored calibration.  The reference maps (weights, image) to an embedding deterministically
+ * (models/clip_embedder.py:63-65); this path's fast embeddings additionally depend on a measurement taken once per set of weights
+ * (the bias pg_embedding_debias subtracts, the certainty tolerance).  A stored measurement is only safe with the weights it was
+ * taken on, and those exist only on the device (16-bit, LayerNorm-folded, packed by pg_vit_finalize) -- so the key is computed there.
+ *
+ * pg_fingerprint: a 128-bit digest of `bytes` bytes at DEVICE pointer `data` (16-byte aligned, else PG_EINVAL with a message and `out`
+ * untouched; on the current device), written to HOST out[2].  Position-sensitive, seed- and length-dependent, independent of grid and
+ * reduction order (wrap-around integer sums); defined completely in csrc/fingerprint.hip's header, restated in tests/_fpref.py.
+ * bytes = 0 is legal (the digest of the empty buffer, no launch).  Runs on `stream` and SYNCHRONISES it before returning (the result
+ * is a host value); allocates and frees a small scratch buffer.  Not for the hot path.
+ * pg_vit_fingerprint: the digests of every parameter buffer pg_vit_forward reads (packed 16-bit weights, folded column sums and
+ * biases, LayerNorm parameters, class and position embeddings), each with its byte size and a per-buffer seed, folded in a fixed
+ * order (csrc/vit.hip) with the layer count, the MFMA operand dtype and whether LayerNorm is folded.  The exact tier's split-weight
+ * copy (cfg.precise) is not included: handles with and without it give the same value.  Two launches on the null stream, one
+ * synchronous copy back (~0.6 GB read for ViT-L).  Any change of a weight that changes a stored bit changes the result. */
+int pg_fingerprint(const void* data, size_t bytes, uint64_t seed, uint64_t out[2], void* stream);
+int pg_vit_fingerprint(const pg_vit* h, uint64_t out[2]);
 
 /* Per-kernel-class timing (HIP events on `stream`), for bench.py's roofline object.
  * pg_vit_profile_enable(h,1) makes subsequent forwards bracket every launch with events; a value >= 2 is a class mask

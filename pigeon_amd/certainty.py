@@ -45,10 +45,36 @@ their discrete outputs do not.
 """
 from __future__ import annotations
 
+import json
 import os
-from typing import Optional
+from typing import Optional, Tuple
 
+import numpy as np
 import torch
+
+# The calibration FILE (round 7).  Everything `calibrate` decides -- the bias vector every fast embedding loses, `rel_tol` (which rows
+# go to the exact tier), the `force_exact` verdict -- is a measurement on a handful of samples; two objects that measure for themselves
+# (two runs, two ranks, `CLIPEmbedding` writing a prototype bank and `SuperGuessr` querying it) return embeddings that differ at the
+# 1e-5 level for the same image under the same weights.  `Certainty.save` / `Certainty.load` make the measurement STATE: one .npz that
+# travels with the checkpoint, keyed by the fingerprint of the weights it was measured on (pg_vit_fingerprint: taken on the device over
+# the packed buffers the fast encoder reads).  Given the same file, (weights, image) -> embedding is a function again, as it is in the
+# reference (models/clip_embedder.py:63-65).  Format: INTEGRATION.md.
+FORMAT_VERSION = 1
+_HEADER_KEYS = ('format_version', 'fingerprint', 'layers', 'mma_dtype', 'ln_fold', 'panels', 'samples', 'source')
+_STATE_SCALARS = (('rel_tol', float), ('rel_tol_exact', float), ('kappa', float), ('debias', bool), ('force_exact', bool),
+                  ('calibrated', bool))
+
+
+class CalibrationError(ValueError):
+    """A calibration file that cannot be used: unreadable, of an unknown format version, or measured on other weights / another
+    panel count than the object it is loaded into.  Raised BEFORE anything on the object changes."""
+
+
+def require_fingerprint(path: str, header: dict, ours: str) -> None:
+    """Refuse a calibration file measured on other weights than the encoder whose fingerprint is `ours`; the message names both."""
+    if header['fingerprint'] != ours:
+        raise CalibrationError(f'{path!r} was measured on other weights: file fingerprint {header["fingerprint"]}, this encoder\'s {ours} '
+                               f'(file: layers {header["layers"]}, {header["mma_dtype"]}, ln_fold {header["ln_fold"]}; source: {header["source"]!r})')
 
 
 class Certainty:
@@ -112,6 +138,7 @@ class Certainty:
         total = float(rel.norm(dim=1).pow(2).mean().sqrt())
         st = {'samples': n, 'fast_vs_exact_rms': total, 'drift_norm': 0.0, 'residual_rms': total, 'drift_used': False}
         drift = bias = None
+        held_image_resid = None
         st['debias'] = False
         P = 0
         if fast_images is not None and exact_images is not None and n and fast_images.shape[0] % n == 0:
@@ -128,6 +155,10 @@ class Certainty:
             resid = float(((corr - ref).norm(dim=1) / ref.norm(dim=1).clamp_min(1e-30)).pow(2).mean().sqrt())
             st['residual_rms'] = resid
             st['drift_norm'] = float(rel_img.reshape((-1, rel_img.shape[-1])).mean(dim=0).norm())
+            # the same held-out residual per IMAGE (not per panel mean): what an embedding this path writes out still carries
+            corr_i = self.apply_bias(held_f.reshape((-1, held_f.shape[-1])), b_half)
+            held_ei = held_e.reshape((-1, held_e.shape[-1]))
+            held_image_resid = float(((corr_i - held_ei).norm(dim=1) / held_ei.norm(dim=1).clamp_min(1e-30)).pow(2).mean().sqrt())
             if resid < 0.9 * total:
                 bias = rel_img.reshape((-1, rel_img.shape[-1])).mean(dim=0).contiguous()
                 st['drift_used'] = st['debias'] = True
@@ -152,6 +183,16 @@ class Certainty:
                 ci = self.apply_bias(fi, bias)              # (in sample: the bias was fitted on these images)
                 st['image_rel_err_debiased'] = float((ci - ei).norm() / ei.norm().clamp_min(1e-30))
                 st['worst_image_rel_err_debiased'] = float(((ci - ei).norm(dim=1) / ei.norm(dim=1).clamp_min(1e-30)).max())
+        # `image_residual_rms`: the per-image error of what this path RETURNS -- with a bias kept, the held-out residual after it; without
+        # one, the raw per-image RMS error (no images given: the per-sample figure).  A consumer of precomputed embeddings judges them
+        # at 1.1 x this (`SuperGuessr.load_calibration` with base_model=None).
+        if bias is not None and held_image_resid is not None:
+            st['image_residual_rms'] = held_image_resid
+        elif fast_images is not None and exact_images is not None and fast_images.numel():
+            fi, ei = fast_images.float(), exact_images.float()
+            st['image_residual_rms'] = float(((fi - ei).norm(dim=1) / ei.norm(dim=1).clamp_min(1e-30)).pow(2).mean().sqrt())
+        else:
+            st['image_residual_rms'] = total
         st['force_exact'] = self.force_exact
         eps = st['residual_rms'] if (drift is not None or bias is not None) else total
         self.rel_tol = max(safety * eps, 2.0 * self.rel_tol_exact)
@@ -162,6 +203,106 @@ class Certainty:
         st['kappa'] = self.kappa
         self.stats = st
         return st
+
+    # ------------------------------------------------------------------------------------------ calibration as state
+    def state_dict(self) -> dict:
+        """Everything a calibration decides, as plain values: `bias` / `drift` ((1024,) fp32 CPU tensors or None), `rel_tol`,
+        `rel_tol_exact`, `kappa`, `debias`, `force_exact`, `calibrated`, `stats` (a copy)."""
+        sd = {'bias': None if self.bias is None else self.bias.detach().to('cpu', torch.float32).clone(),
+              'drift': None if self.drift is None else self.drift.detach().to('cpu', torch.float32).clone()}
+        for k, _ in _STATE_SCALARS:
+            sd[k] = getattr(self, k)
+        sd['stats'] = dict(self.stats)
+        return sd
+
+    def load_state_dict(self, sd: dict) -> None:
+        """Set all of the above at once from `state_dict()`'s form (checked first: nothing changes when a key is missing or a vector
+        has the wrong shape)."""
+        missing = [k for k in ('bias', 'drift', 'stats') + tuple(k for k, _ in _STATE_SCALARS) if k not in sd]
+        if missing:
+            raise CalibrationError(f'calibration state lacks {missing}')
+        vecs = {}
+        for k in ('bias', 'drift'):
+            v = sd[k]
+            if v is not None:
+                v = torch.as_tensor(v).detach().to(torch.float32).reshape(-1).clone().contiguous()
+                if v.numel() != 1024 or not bool(torch.isfinite(v).all()):
+                    raise CalibrationError(f'calibration state: {k} must be 1024 finite values, got {tuple(v.shape)}')
+            vecs[k] = v
+        scal = {k: typ(sd[k]) for k, typ in _STATE_SCALARS}
+        for k in ('rel_tol', 'rel_tol_exact', 'kappa'):
+            if not (scal[k] > 0.0 and scal[k] < float('inf')):
+                raise CalibrationError(f'calibration state: {k} = {scal[k]!r} is not a positive finite number')
+        stats = dict(sd['stats'])
+        self.bias, self.drift = vecs['bias'], vecs['drift']
+        for k, v in scal.items():
+            setattr(self, k, v)
+        self.stats = stats
+
+    def save(self, path: str, fingerprint: str, panels: int, meta: Optional[dict] = None) -> str:
+        """Write the calibration to `path` (one .npz, no pickled member), keyed by `fingerprint` (32 hex digits:
+        HipCLIPVisionModel.fingerprint()).  `panels`: images per sample `rel_tol` was measured on (4 for panoramas, 1 for single
+        images).  `meta`: `layers`, `mma_dtype`, `ln_fold` (HipCLIPVisionModel.encoder_config()) and a free-text `source`.  The file
+        is written under a temporary name and moved into place (os.replace): a reader never sees half a file."""
+        if not self.calibrated:
+            raise CalibrationError('Certainty.save: nothing to save -- not calibrated')
+        meta = dict(meta or {})
+        sd = self.state_dict()
+        empty = np.zeros((0,), dtype=np.float32)
+        arrays = {
+            'format_version': np.int64(FORMAT_VERSION), 'fingerprint': np.str_(str(fingerprint)),
+            'layers': np.int64(meta.get('layers', 0)), 'mma_dtype': np.str_(str(meta.get('mma_dtype', ''))),
+            'ln_fold': np.bool_(meta.get('ln_fold', True)), 'panels': np.int64(panels),
+            'samples': np.int64(sd['stats'].get('samples', 0)), 'source': np.str_(str(meta.get('source', ''))),
+            'bias': empty if sd['bias'] is None else sd['bias'].numpy(), 'drift': empty if sd['drift'] is None else sd['drift'].numpy(),
+            'rel_tol': np.float64(sd['rel_tol']), 'rel_tol_exact': np.float64(sd['rel_tol_exact']), 'kappa': np.float64(sd['kappa']),
+            'debias': np.bool_(sd['debias']), 'force_exact': np.bool_(sd['force_exact']), 'calibrated': np.bool_(sd['calibrated']),
+            'stats_json': np.str_(json.dumps(sd['stats'], sort_keys=True)),
+        }
+        path = str(path)
+        os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+        tmp = f'{path}.tmp.{os.getpid()}'
+        try:
+            with open(tmp, 'wb') as f:
+                np.savez(f, **arrays)
+            os.replace(tmp, path)
+        finally:
+            if os.path.exists(tmp):
+                os.remove(tmp)
+        return path
+
+    @staticmethod
+    def load(path: str) -> Tuple[dict, dict]:
+        """Read a calibration file -> (state dict for `load_state_dict`, header dict: `format_version`, `fingerprint`, `layers`,
+        `mma_dtype`, `ln_fold`, `panels`, `samples`, `source`).  Read with allow_pickle=False; a file that is truncated, lacks a
+        member, holds a pickled member or has an unknown `format_version` raises CalibrationError naming the reason.  Whether the
+        fingerprint is the RIGHT one is the caller's check (it knows the encoder)."""
+        path = str(path)
+        if not os.path.exists(path):
+            raise FileNotFoundError(f'calibration file {path!r} does not exist')
+        try:
+            with np.load(path, allow_pickle=False) as z:
+                if 'format_version' not in z.files:
+                    raise CalibrationError(f'{path!r} is not a calibration file: no format_version')
+                version = int(z['format_version'])
+                if version != FORMAT_VERSION:
+                    raise CalibrationError(f'{path!r}: unknown format_version {version} (this build reads format_version {FORMAT_VERSION})')
+                raw = {k: z[k] for k in _HEADER_KEYS + ('bias', 'drift', 'stats_json') + tuple(k for k, _ in _STATE_SCALARS)}
+        except CalibrationError:
+            raise
+        except Exception as e:      # noqa  zipfile.BadZipFile / EOFError / OSError (truncated), KeyError (member missing), ValueError (pickled member)
+            raise CalibrationError(f'{path!r} cannot be read as a calibration file: {type(e).__name__}: {e}') from e
+        header = {'format_version': version, 'fingerprint': str(raw['fingerprint']), 'layers': int(raw['layers']),
+                  'mma_dtype': str(raw['mma_dtype']), 'ln_fold': bool(raw['ln_fold']), 'panels': int(raw['panels']),
+                  'samples': int(raw['samples']), 'source': str(raw['source'])}
+        sd = {k: (torch.from_numpy(np.array(raw[k], dtype=np.float32)) if raw[k].size else None) for k in ('bias', 'drift')}
+        for k, typ in _STATE_SCALARS:
+            sd[k] = typ(raw[k])
+        try:
+            sd['stats'] = dict(json.loads(str(raw['stats_json'])))
+        except Exception as e:  # noqa
+            raise CalibrationError(f'{path!r}: stats cannot be decoded: {e}') from e
+        return sd, header
 
     def describe(self) -> str:
         s = self.stats

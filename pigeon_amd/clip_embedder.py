@@ -101,6 +101,21 @@ class HipCLIPVisionModel(torch.nn.Module):
         pixel_values = _to_device_pixels(pixel_values, self._dummy.device)
         return self._encoder(pixel_values.device).forward(pixel_values)
 
+    def fingerprint(self) -> str:
+        """32 hex digits identifying the weights the fast encoder computes with (pg_vit_fingerprint over the packed device buffers;
+        builds the packed encoder if needed, on the module's device).  What a calibration file is keyed by."""
+        dev = self._dummy.device if self._dummy.is_cuda else torch.device("cuda", torch.cuda.current_device())
+        return "%016x%016x" % self._encoder(dev).fingerprint()
+
+    def encoder_config(self) -> dict:
+        """What, besides the weights, changes the fast path's bits (part of the fingerprint; written into a calibration file's header)."""
+        fold = os.environ.get("PIGEON_LN_FOLD", "1")[:1] != "0"
+        mma = self._enc.mma_dtype if self._enc is not None else ("bf16" if os.environ.get("PIGEON_MMA_DTYPE", "").lower() == "bf16" else "f16")
+        layers = 0
+        while f"encoder.layers.{layers}.layer_norm1.weight" in self._sd:
+            layers += 1
+        return {"layers": layers, "mma_dtype": mma, "ln_fold": bool(fold)}
+
     def forward(self, pixel_values: Tensor = None, **kwargs):
         pixel_values = _to_device_pixels(pixel_values, self._dummy.device)
         emb, hid = self._encoder(pixel_values.device).forward(pixel_values, return_hidden=True)
@@ -274,7 +289,8 @@ def gpu_preprocess(images, device="cuda", out_dtype: torch.dtype = torch.float32
 class CLIPEmbedding(torch.nn.Module):
     def __init__(self, model_name: str, device: str = 'cuda', load_checkpoint: bool = False,
                  panorama: bool = False, state_dict: Optional[Dict[str, Tensor]] = None,
-                 clip_model: Optional[HipCLIPVisionModel] = None, contract_guard: Optional[str] = None):
+                 clip_model: Optional[HipCLIPVisionModel] = None, contract_guard: Optional[str] = None,
+                 calibration: Optional[str] = None):
         """CLIP embedding model (not trainable) -- reference models/clip_embedder.py:11-40.
 
         Args follow the reference.  The reference pulls the base weights from the HuggingFace hub
@@ -291,6 +307,9 @@ class CLIPEmbedding(torch.nn.Module):
         in the exact mode from then on (~3x the time per image), 'raise': raises, 'off': no check.  The embeddings `run.py embed`
         writes are what prototype banks are built from: a tower with large attention logits must not write them out of tolerance
         silently.
+
+        `calibration` (a path): `load_calibration(path)` at the end of construction -- bias and verdict come from the file, and the
+        first forward runs neither the guard's measurement nor its collectives.  Without it nothing changes.
         """
         super().__init__()
         self.device = device
@@ -332,6 +351,60 @@ class CLIPEmbedding(torch.nn.Module):
         else:
             self.clip_model = self.clip_model.cuda(self.device)
         self.eval()
+        self.calibration_header = None           # header of the calibration file in force (None: none loaded)
+        if calibration is not None:
+            self.load_calibration(calibration)
+
+    # ---- calibration as a file (pigeon_amd/certainty.py) ----
+    def save_calibration(self, path: str, source: str = '') -> str:
+        """Write what the first forward's guard measured -- the bias this module subtracts (in a data-parallel job: the one vector
+        all ranks share) and the verdict -- as a calibration file keyed by the encoder's weight fingerprint.  `panels` is 1: the
+        tolerance in the file is a per-image one.  A `SuperGuessr` on precomputed embeddings (base_model=None) or another
+        `CLIPEmbedding` loads it; a panorama `SuperGuessr` with an encoder wants a file measured on panoramas."""
+        from .certainty import CalibrationError, Certainty
+        st = self.guard_stats
+        if st is None:
+            raise CalibrationError('CLIPEmbedding.save_calibration: nothing measured yet (the guard runs in the first forward; '
+                                   "contract_guard='off' never measures)")
+        c = Certainty(debias=self.debias)
+        # the per-image error of what this module returns: what is left after the bias (held out), or the raw error without one
+        resid = st.get('residual_rms') if (self.bias is not None or st.get('image_rel_err') is None) else st.get('image_rel_err')
+        if resid is None:
+            raise CalibrationError('CLIPEmbedding.save_calibration: the guard statistics hold no per-image error')
+        resid = float(resid)
+        c.bias = None if self.bias is None else self.bias.detach().to('cpu', torch.float32).clone()
+        c.force_exact = bool(self.force_exact)
+        c.rel_tol = max(1.1 * resid, 2.0 * c.rel_tol_exact)
+        c.calibrated = True
+        c.stats = dict(st.get('file_stats') or {})
+        c.stats.update({k: v for k, v in st.items() if isinstance(v, (bool, int, float, str))})
+        c.stats.update(samples=int(st['images']), image_residual_rms=resid, rel_tol=c.rel_tol, kappa=c.kappa,
+                       force_exact=c.force_exact, debias=self.bias is not None)
+        base = self.clip_model.base_model
+        meta = base.encoder_config()
+        meta['source'] = source or f"CLIPEmbedding, {st['images']} images"
+        return c.save(path, base.fingerprint(), 1, meta)
+
+    def load_calibration(self, path: str) -> dict:
+        """Take `bias` and `force_exact` from a calibration file and fill `guard_stats`: the first forward then measures nothing and
+        joins no collective (every rank of a job loads the same file instead).  The file is checked before anything changes: an
+        unreadable file, an unknown format_version and a fingerprint that is not this encoder's are refused (CalibrationError, both
+        fingerprints named).  Any `panels` is accepted: the bias is per image.  Returns the header."""
+        from .certainty import Certainty, require_fingerprint
+        sd, header = Certainty.load(path)
+        c = Certainty()
+        c.load_state_dict(sd)
+        require_fingerprint(path, header, self.clip_model.base_model.fingerprint())
+        if c.force_exact and self.contract_guard == 'raise':
+            raise RuntimeError(f'CLIPEmbedding: {path!r} records the 16-bit encoder outside the 1e-3 embedding contract on these weights; '
+                               "construct with contract_guard='exact' to encode in the exact mode")
+        st = {'images': int(c.stats.get('samples', header['samples'])), 'image_rel_err': c.stats.get('image_rel_err'),
+              'worst_image_rel_err': c.stats.get('worst_image_rel_err'), 'contract': 1e-3, 'debias': c.bias is not None,
+              'outside': bool(c.force_exact), 'from_file': str(path), 'fingerprint': header['fingerprint'], 'file_stats': dict(c.stats)}
+        if 'image_residual_rms' in c.stats:
+            st['residual_rms'] = c.stats['image_residual_rms']
+        self.bias, self.force_exact, self.guard_stats, self.calibration_header = c.bias, bool(c.force_exact), st, header
+        return header
 
     def _get_embedding(self, image) -> Tensor:
         """reference models/clip_embedder.py:42-66"""

@@ -54,6 +54,13 @@ enum PgGemmKernel { PG_GK_NONE = -1, PG_GK_PP6 = 0, PG_GK_PP = 1, PG_GK_MID = 2,
         }                                                                                     \
     } while (0)
 
+// fingerprint.hip: the digests (definition: that file's header) of n device buffers on the current device -- 16-byte aligned, or
+// PG_EINVAL before any launch -- in two launches and one copy back for all of them; out[2 i], out[2 i + 1] (HOST) = buffer i's.
+// Synchronises `stream`.  pg_fingerprint_host: the same function of a HOST buffer (pg_vit_fingerprint folds its table with it).
+struct PgFpBuf { const void* data; size_t bytes; uint64_t seed; };
+int pg_fingerprint_many(const PgFpBuf* bufs, int n, uint64_t* out, hipStream_t stream);
+void pg_fingerprint_host(const void* data, size_t bytes, uint64_t seed, uint64_t out[2]);
+
 // gemm_plan.hip: every GEMM; argument checks, the plan, at most two kernel launches
 int pg_gemm_launch(int dtype, const void* A, int64_t lda, const void* W, int64_t ldw, const float* bias, void* out, int64_t ldc,
                    int M, int N, int K, int epi, float qscale, int qcols, const float* aux, int variant,

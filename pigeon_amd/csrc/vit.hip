@@ -74,6 +74,7 @@ struct pg_vit {
     bool ln_fold = true;                                   // LayerNorm folded into the GEMMs (env PIGEON_LN_FOLD=0: separate kernels)
     std::map<std::string, std::vector<float>> host;      // staged fp32 parameters until finalize
     std::vector<void*> allocs;
+    std::map<const void*, size_t> alloc_bytes;             // byte size of every uploaded parameter buffer (pg_vit_fingerprint reads them whole)
     uint16_t* wpatch = nullptr;                           // [1024][640] bf16 (K zero padded)
     uint16_t* wpatch3 = nullptr;                          // exact mode: [1024][3 * 640] split-fp16 triple
     float *cls = nullptr, *pos = nullptr, *preg = nullptr, *preb = nullptr;
@@ -251,12 +252,14 @@ static int need(pg_vit* h, const std::string& k, size_t n, const std::vector<flo
 static int upload_f32(pg_vit* h, const float* src, size_t n, float** dst) {
     PG_HIP(hipMalloc((void**)dst, n * sizeof(float)));
     h->allocs.push_back(*dst);
+    h->alloc_bytes[*dst] = n * sizeof(float);
     PG_HIP(hipMemcpy(*dst, src, n * sizeof(float), hipMemcpyHostToDevice));
     return PG_OK;
 }
 static int upload_bf16(pg_vit* h, const std::vector<uint16_t>& src, uint16_t** dst) {
     PG_HIP(hipMalloc((void**)dst, src.size() * 2));
     h->allocs.push_back(*dst);
+    h->alloc_bytes[*dst] = src.size() * 2;
     PG_HIP(hipMemcpy(*dst, src.data(), src.size() * 2, hipMemcpyHostToDevice));
     return PG_OK;
 }
@@ -882,6 +885,54 @@ extern "C" int pg_vit_profile_reset(pg_vit* h) {
     if (!h) { pg_set_error("profile_reset: null handle"); return PG_EINVAL; }
     RC(prof_drain(h));
     for (int i = 0; i < PG_PROF_CLASSES; ++i) { h->prof_launches[i] = 0; h->prof_ms[i] = 0; }
+    return PG_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ weight fingerprint
+// pg_vit_fingerprint: 128 bits that identify what the FAST encoder computes with -- the key of a stored calibration
+// (pigeon_amd/certainty.py).  The order is fixed and part of the definition:
+//   buffers (each: pg_fingerprint of the whole device buffer, seed = (group << 8) | slot, group 0 = the embeddings, group l + 1 =
+//   encoder layer l):
+//     group 0:      0 patch weight (16-bit, [1024][640])  1 class embedding  2 position embedding  3 pre_layrnorm weight  4 its bias
+//     group l + 1:  0 QKV weight (16-bit; gamma-folded with ln_fold)  1 QKV bias (with ln_fold: beta.W^T + b)  2 QKV column sums
+//                   (ln_fold only)  3 out_proj weight  4 its bias  5 fc1 weight (as QKV)  6 fc1 bias  7 fc1 column sums (ln_fold
+//                   only)  8 fc2 weight  9 its bias  10..13 layer_norm1 weight, bias, layer_norm2 weight, bias
+//   table of 64-bit words: ['PGVITFP1', layers, mma_dtype, ln_fold, buffers, then per buffer: seed, bytes, digest[0], digest[1]]
+//   result: the digest (same function, seed 0) of that table's bytes.
+// The exact tier's split-weight copies and raw biases (cfg.precise) are NOT in it: they are a function of the same fp32 weights, and
+// a handle built without `precise` gives the same value.
+extern "C" int pg_vit_fingerprint(const pg_vit* h, uint64_t out[2]) {
+    if (!h || !out) { pg_set_error("vit_fingerprint: null argument"); return PG_EINVAL; }
+    if (!h->finalized) { pg_set_error("vit_fingerprint: handle not finalized"); return PG_ESTATE; }
+    std::vector<PgFpBuf> bufs;
+    int missing = 0;
+    auto add = [&](const void* p, int group, int slot) {
+        if (!p) return;                                        // (the column sums without ln_fold)
+        auto it = h->alloc_bytes.find(p);
+        if (it == h->alloc_bytes.end()) { ++missing; return; }
+        bufs.push_back({p, it->second, ((uint64_t)group << 8) | (uint64_t)slot});
+    };
+    add(h->wpatch, 0, 0); add(h->cls, 0, 1); add(h->pos, 0, 2); add(h->preg, 0, 3); add(h->preb, 0, 4);
+    for (int l = 0; l < h->cfg.layers; ++l) {
+        const LayerW& L = h->layers[l];
+        const void* p[14] = {L.wqkv, L.bqkv, L.sqkv, L.wo, L.bo, L.w1, L.b1, L.s1, L.w2, L.b2, L.ln1g, L.ln1b, L.ln2g, L.ln2b};
+        for (int s = 0; s < 14; ++s) add(p[s], l + 1, s);
+    }
+    if (missing) { pg_set_error("vit_fingerprint: %d parameter buffers without a recorded size", missing); return PG_ESTATE; }
+    int cur = 0;
+    PG_HIP(hipGetDevice(&cur));
+    PG_HIP(hipSetDevice(h->device));                         // the weights live on the handle's device, whatever is current
+    std::vector<uint64_t> dig(bufs.size() * 2);
+    const int rc = pg_fingerprint_many(bufs.data(), (int)bufs.size(), dig.data(), nullptr);
+    (void)hipSetDevice(cur);
+    if (rc != PG_OK) return rc;
+    std::vector<uint64_t> table = {0x3150465449564750ull /* 'PGVITFP1' */, (uint64_t)h->cfg.layers, (uint64_t)h->cfg.mma_dtype,
+                                   (uint64_t)(h->ln_fold ? 1 : 0), (uint64_t)bufs.size()};
+    for (size_t i = 0; i < bufs.size(); ++i) {
+        table.push_back(bufs[i].seed); table.push_back((uint64_t)bufs[i].bytes);
+        table.push_back(dig[2 * i]); table.push_back(dig[2 * i + 1]);
+    }
+    pg_fingerprint_host(table.data(), table.size() * sizeof(uint64_t), 0, out);
     return PG_OK;
 }
 

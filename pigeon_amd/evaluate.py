@@ -255,7 +255,8 @@ def evaluate_model(model: SuperGuessr, dataset, metrics: Optional[Callable] = No
 
 def evaluate(model: str, dataset, yfcc: bool, landmarks: bool, base_model=None, heading: bool = False,
              refine: bool = True, geocell_path: Optional[str] = None, proto_path: Optional[str] = None,
-             dataset_path=None, bank=None, head_state: Optional[str] = None, multi_task: bool = False):
+             dataset_path=None, bank=None, head_state: Optional[str] = None, multi_task: bool = False,
+             calibration: Optional[str] = None):
     """reference evaluation/evaluate.py:10-85.
 
     `base_model`: as in the reference a STRING -- config.CLIP_MODEL for the pretrained tower, or the path of a checkpoint whose
@@ -271,6 +272,9 @@ def evaluate(model: str, dataset, yfcc: bool, landmarks: bool, base_model=None, 
     `multi_task` (the reference's evaluate hard-wires False, :43; its `run.py -m` trains such models): build the model with the
     regression, climate and month heads, so that a multi-task checkpoint loads completely and the multi-task metrics are reported
     when the dataset carries `labels_multi_task` / `labels_climate` / `labels_month`.
+    `calibration` (a path; pigeon_amd/certainty.py): if the file exists it is loaded AFTER the weights and before the first batch
+    (`SuperGuessr.load_calibration`: a file measured on other weights raises); if not, the run calibrates on its first batch as
+    without the argument and rank 0 writes the file at the end (in a multi-rank job: rank 0's own measurement).
     """
     import os
     from . import config as cfg
@@ -308,6 +312,13 @@ def evaluate(model: str, dataset, yfcc: bool, landmarks: bool, base_model=None, 
         full_model.load_state(ckpt)
     full_model.to('cuda')
     print(full_model)
+    write_calibration = False
+    if calibration:
+        if os.path.exists(calibration):                                           # weights first, then the calibration
+            header = full_model.load_calibration(calibration)
+            print(f'Loaded calibration {calibration} (fingerprint {header["fingerprint"]}, {header["samples"]} samples; {header["source"]})')
+        else:
+            write_calibration = int(os.environ.get('RANK', '0')) == 0
     refiner = None
     if refine:
         proto_model_path = cfg.PROTO_MODEL_YFCC_PATH if yfcc else cfg.PROTO_MODEL_PATH
@@ -335,7 +346,15 @@ def evaluate(model: str, dataset, yfcc: bool, landmarks: bool, base_model=None, 
             os.makedirs(os.path.dirname(packed) or '.', exist_ok=True)
             refiner.host_bank.save(packed)
         print(refiner)
-    return evaluate_model(full_model, dataset, compute_geoguessr_metrics, None, refiner)
+    results = evaluate_model(full_model, dataset, compute_geoguessr_metrics, None, refiner)
+    if write_calibration:
+        if full_model.base_model is not None and full_model.certainty.calibrated:
+            full_model.save_calibration(calibration, source=f'evaluate, first batch, {full_model.certainty.stats.get("samples")} samples')
+            print(f'Calibration written to {calibration}')
+        else:
+            print(f'No calibration written to {calibration}: nothing was measured in this run (no encoder, the exact tier off, '
+                  'or fewer than 8 samples)')
+    return results
 
 
 class PanoramaPipeline:

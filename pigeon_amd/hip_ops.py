@@ -378,6 +378,14 @@ class VitEncoder:
                                             C.c_void_p(ws.data_ptr() + off), ws.numel() - off, _stream()), "pg_vit_forward_precise")
         return (emb, hid) if return_hidden else emb
 
+    def fingerprint(self):
+        """pg_vit_fingerprint -> (int, int): 128 bits over every device buffer the FAST encoder reads (packed 16-bit weights, folded
+        column sums and biases, LayerNorm parameters, class and position embeddings) plus layer count, operand dtype and LayerNorm
+        fold.  The same with and without `precise`.  The key of a stored calibration (pigeon_amd/certainty.py).  Synchronises."""
+        out = (C.c_uint64 * 2)()
+        check(load().pg_vit_fingerprint(self._h, out), "pg_vit_fingerprint")
+        return int(out[0]), int(out[1])
+
     def graph(self, on: Optional[bool] = None):
         """Switch the encoder's hipGraph replay on / off (None: query only) -> (replays, captures) since creation."""
         r, c = C.c_int64(), C.c_int64()
@@ -538,6 +546,17 @@ def embedding_debias(emb: torch.Tensor, bias: torch.Tensor) -> torch.Tensor:
     n = emb.numel() // HIDDEN
     check(load().pg_embedding_debias(_p(emb), n, HIDDEN, _p(bias), _stream()), "pg_embedding_debias")
     return emb
+
+
+def fingerprint(t: torch.Tensor, seed: int = 0):
+    """pg_fingerprint -> (int, int): the 128-bit digest (csrc/fingerprint.hip) of the bytes of the contiguous device tensor `t`, which
+    must start on a 16-byte boundary (PigeonHipError otherwise).  Synchronises the current stream: the result is a host value."""
+    _dev(t)
+    out = (C.c_uint64 * 2)()
+    with torch.cuda.device(t.device):
+        check(load().pg_fingerprint(_p(t), t.numel() * t.element_size(), C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), out, _stream()),
+              "pg_fingerprint")
+    return int(out[0]), int(out[1])
 
 
 # ----------------------------------------------------------------------------------------- deferred exact tier (csrc/requeue.hip)

@@ -122,13 +122,39 @@ def make_app(model, refiner=None, preprocess: Optional[Callable] = None, game_lo
 
 
 def main(argv=None):
-    """python -m pigeon_amd.serve --head <head.model> [--geocells <csv>] [--protos <csv> --dataset <dir>] [--port 5000]"""
-    import argparse
+    """python -m pigeon_amd.serve --head <head.model> [--geocells <csv>] [--protos <csv> --dataset <dir>] [--calibration <file>] [--port 5000]"""
+    import os
+    ap = _arg_parser()
+    args = ap.parse_args(argv)
+    if args.calibration and not os.path.exists(args.calibration):
+        ap.error(f"--calibration {args.calibration}: no such file (the server only loads a calibration; write one with "
+                 "`python -m pigeon_amd.calibrate` or `run.py evaluate --calibration`)")
     import torch
     import uvicorn
     from .clip_embedder import HipCLIPVisionModel
     from .proto_refiner import ProtoRefiner
     from .super_guessr import SuperGuessr
+    kw = {"geocell_path": args.geocells} if args.geocells else {}
+    from .clip_embedder import load_pretrained_clip
+    try:
+        base = load_pretrained_clip()                                  # CLIP_MODEL from local files (env PIGEON_CLIP_MODEL / HF cache)
+    except RuntimeError as why:
+        print(f"[serve] no pretrained tower ({why}); using a seeded random-init ViT-L/14-336 with {args.layers} layers")
+        base = HipCLIPVisionModel(seed=0, layers=args.layers)
+    model = SuperGuessr(base, panorama=True, serving=True, freeze_base=True, exact_top1=args.exact_top1, **kw).to("cuda").eval()
+    if args.head:
+        model.load_state(args.head)
+    if args.calibration:                                               # after the weights: the first request is answered calibrated
+        header = model.load_calibration(args.calibration)
+        print(f"[serve] calibration {args.calibration}: fingerprint {header['fingerprint']}, {header['samples']} samples; "
+              f"{model.certainty.describe()}")
+    refiner = ProtoRefiner(proto_path=args.protos, dataset_path=args.dataset) if args.protos else None
+    torch.cuda.synchronize()
+    uvicorn.run(make_app(model, refiner), host=args.host, port=args.port)
+
+
+def _arg_parser():
+    import argparse
     ap = argparse.ArgumentParser(description=main.__doc__)
     ap.add_argument("--head", default=None, help="SuperGuessr checkpoint (torch.save state dict); random init if omitted")
     ap.add_argument("--geocells", default=None)
@@ -140,20 +166,11 @@ def main(argv=None):
                          "are re-encoded in the encoder's exact mode, so that the answer is the reference's fp32 one)")
     ap.add_argument("--host", default="127.0.0.1")
     ap.add_argument("--port", type=int, default=5000)
-    args = ap.parse_args(argv)
-    kw = {"geocell_path": args.geocells} if args.geocells else {}
-    from .clip_embedder import load_pretrained_clip
-    try:
-        base = load_pretrained_clip()                                  # CLIP_MODEL from local files (env PIGEON_CLIP_MODEL / HF cache)
-    except RuntimeError as why:
-        print(f"[serve] no pretrained tower ({why}); using a seeded random-init ViT-L/14-336 with {args.layers} layers")
-        base = HipCLIPVisionModel(seed=0, layers=args.layers)
-    model = SuperGuessr(base, panorama=True, serving=True, freeze_base=True, exact_top1=args.exact_top1, **kw).to("cuda").eval()
-    if args.head:
-        model.load_state(args.head)
-    refiner = ProtoRefiner(proto_path=args.protos, dataset_path=args.dataset) if args.protos else None
-    torch.cuda.synchronize()
-    uvicorn.run(make_app(model, refiner), host=args.host, port=args.port)
+    ap.add_argument("--calibration", default=None, metavar="FILE",
+                    help="encoder calibration file (pigeon_amd/certainty.py), LOAD ONLY: it must exist and match the weights.  The first "
+                         "request is then answered with the measured tolerance and de-biased embeddings, instead of the uncalibrated "
+                         "tolerance until 16 panoramas have come in")
+    return ap
 
 
 if __name__ == "__main__":

@@ -21,7 +21,7 @@ from torch import nn, Tensor
 from torch.nn.parameter import Parameter
 
 from . import hip_ops
-from .certainty import Certainty
+from .certainty import CalibrationError, Certainty, require_fingerprint
 from .geo_utils import haversine_matrix, smooth_labels
 from .clip_embedder import HipCLIPVisionModel
 from .config import CLIP_EMBED_DIM, GEOCELL_PATH, GEOCELL_PATH_YFCC
@@ -75,9 +75,12 @@ class SuperGuessr(nn.Module):
         `exact_top1`, `margin_kappa` (z-score, default 3.6), `margin_rel_tol` (default 1e-3 = the contract's embedding
         tolerance until `calibrate_certainty` -- called explicitly, or by the first forward that sees >= 8 samples with pixels, or
         once 16 samples have come in through smaller batches -- replaces it by the measured error of THIS set of weights), `margin_rel_tol_exact` (5e-6).
+        `calibration` (a path): `load_calibration(path)` at the end of construction -- the stored measurement instead of one taken
+        inside the first forward(s); without it nothing changes.
         """
         super(SuperGuessr, self).__init__()
         geocell_path = kwargs.pop('geocell_path', None)
+        calibration = kwargs.pop('calibration', None)
         exact_top1 = kwargs.pop('exact_top1', None)
         self.exact_top1 = (os.environ.get('PIGEON_EXACT_TOP1', '1') not in ('', '0')) if exact_top1 is None else bool(exact_top1)
         self.certainty = Certainty(kappa=float(kwargs.pop('margin_kappa', os.environ.get('PIGEON_MARGIN_KAPPA', 3.6))),
@@ -139,7 +142,11 @@ class SuperGuessr(nn.Module):
         self._rel_tol0 = self.certainty.rel_tol              # the constructor's uncalibrated tolerance: what a weight load goes back to
         if self.exact_top1 and isinstance(self.base_model, HipCLIPVisionModel):
             self.base_model.enable_precise(True)             # pack the split-weight copy with the first build, not inside a request
+        self._embedding_rel_tol0 = None                      # `embedding_rel_tol` as it was before a calibration file set it (load_state gives it back)
+        self.calibration_header = None                       # header of the calibration file in force (None: none loaded)
         print(f'Initialized SuperGuessr classification model with {self.num_cells} geocells.')
+        if calibration is not None:
+            self.load_calibration(calibration)
 
     # legacy names of the certainty parameters (round 4)
     @property
@@ -198,7 +205,12 @@ class SuperGuessr(nn.Module):
         if isinstance(self.base_model, HipCLIPVisionModel):
             self.base_model._weights_changed()
         # other weights: the measured error is void -- back to the constructor's tolerance (not a hard-coded one), nothing half-collected
+        # (a calibration LOADED from a file goes the same way: it is keyed to the weights that have just been replaced -- load it again
+        # after the weights, `evaluate()` does it in that order)
         self.certainty = Certainty(self.certainty.kappa, self._rel_tol0, self.certainty.rel_tol_exact, debias=self.certainty.debias)
+        if self._embedding_rel_tol0 is not None:
+            self.embedding_rel_tol, self._embedding_rel_tol0 = self._embedding_rel_tol0, None
+        self.calibration_header = None
         self._cal_buffer = []
         self._engines = {}
         self._aux_pack = None
@@ -506,6 +518,56 @@ class SuperGuessr(nn.Module):
         dev = self.cell_layer.weight.device
         px = pixel_values.reshape((-1, 3, 336, 336)).to(dev)
         return self._calibrate(px, max_samples)['fast_vs_exact_rms']
+
+    # ------------------------------------------------------------------------------------------ calibration as a file
+    def _calibration_meta(self, source: str = '') -> dict:
+        meta = self._encoder().encoder_config()
+        meta['source'] = source
+        return meta
+
+    def save_calibration(self, path: str, source: str = '') -> str:
+        """Write what `calibrate_certainty` (or the first forwards) measured to `path`, keyed by the encoder's weight fingerprint
+        (pg_vit_fingerprint) -- `Certainty.save`.  Needs a base model and a finished calibration."""
+        if self.base_model is None:
+            raise CalibrationError('save_calibration: no base model -- nothing was measured here')
+        if not self.certainty.calibrated:
+            raise CalibrationError('save_calibration: not calibrated yet (call calibrate_certainty, or run the first forwards)')
+        return self.certainty.save(path, self._encoder().fingerprint(), self._panels(),
+                                   self._calibration_meta(source or f'SuperGuessr, {self.certainty.stats.get("samples")} samples'))
+
+    def load_calibration(self, path: str) -> dict:
+        """Take bias, tolerance and the `force_exact` verdict from a calibration file instead of measuring them inside a forward.
+        The file is checked BEFORE anything on this object changes, and all state is set at once.  Refused (CalibrationError): an
+        unreadable file, an unknown `format_version`, a fingerprint that is not this encoder's (both are named), `panels` different
+        from this model's.  Order: weights first (`load_state` drops a calibration, loaded or measured), then the calibration.
+        With base_model=None (precomputed embeddings) there is no encoder to fingerprint: the file is accepted and sets
+        `embedding_rel_tol` -- what caller-supplied embeddings are judged against -- to 1.1 x the file's `image_residual_rms` (the
+        per-image error of the 16-bit path that wrote them, after its bias), or to the exact tier's floor when the file says
+        `force_exact` (those embeddings were written by the exact encoder).  Returns the file's header."""
+        sd, header = Certainty.load(path)
+        new = Certainty(self.certainty.kappa, self._rel_tol0, self.certainty.rel_tol_exact, debias=self.certainty.debias)
+        new.load_state_dict(sd)
+        if self.base_model is None:
+            if new.force_exact:
+                tol = new.rel_tol_exact
+            else:
+                resid = new.stats.get('image_residual_rms')
+                if resid is None or not (float(resid) > 0.0):
+                    raise CalibrationError(f'{path!r}: no image_residual_rms in the file\'s statistics -- cannot set embedding_rel_tol')
+                tol = 1.1 * float(resid)                   # the safety factor `Certainty.calibrate` puts on rel_tol
+            if self._embedding_rel_tol0 is None:
+                self._embedding_rel_tol0 = self.embedding_rel_tol
+            self.embedding_rel_tol = float(tol)
+            self.calibration_header = header
+            return header
+        require_fingerprint(path, header, self._encoder().fingerprint())
+        if header['panels'] != self._panels():
+            raise CalibrationError(f'{path!r}: rel_tol was measured on samples of {header["panels"]} images (panels), this model uses {self._panels()}')
+        self.certainty = new
+        self.calibration_header = header
+        self._cal_buffer = []
+        self._wnorm = {}
+        return header
 
     def __str__(self):
         shown = (('base_model', self.base_model is not None), ('panorama', self.panorama), ('hierarchical', self.hierarchical),

@@ -13,6 +13,7 @@ replaced by seeded synthetic fixtures:  `--synthetic N` embeds / evaluates N syn
   python run.py evaluate saved_models/head.model -l data/hf_eval -b saved_models/StreetviewCLIP.model
   python run.py evaluate saved_models/head_mt.model -m -l data/hf_eval -b saved_models/StreetviewCLIP.model   (a multi-task checkpoint)
   torchrun --nproc-per-node 8 --master-addr 127.0.0.1 run.py embed random --synthetic 4096
+  python run.py embed random --synthetic 64 --calibration cal.npz                  # first run writes cal.npz, later runs load it
 """
 import argparse
 import logging
@@ -52,6 +53,12 @@ argp.add_argument('--exact-top1', dest='exact_top1', action='store_true', defaul
                        "encoder's exact mode, so that geocell argmax and refined point are the reference's fp32 ones (PIGEON_EXACT_TOP1=1)")
 argp.add_argument('--no-exact-top1', dest='exact_top1', action='store_false',
                   help="the 16-bit path alone (PIGEON_EXACT_TOP1=0): embeddings within 1e-3, discrete outputs not guaranteed")
+argp.add_argument('--calibration', default=None, metavar='FILE',
+                  help="encoder calibration file (bias vector, certainty tolerance, exact-encoder verdict; keyed by the weight "
+                       "fingerprint).  If FILE exists it is loaded before the first batch -- every rank loads the same one, nothing is "
+                       "measured inside a forward, and a file measured on other weights ends the run with an error.  If not, the run "
+                       "calibrates on its first batch as without this option and rank 0 writes FILE at the end: `embed` writes the "
+                       "vector all ranks already share, `evaluate` rank 0's own.  An explicit calibration run: python -m pigeon_amd.calibrate")
 
 
 class _SyntheticImages(torch.utils.data.Dataset):
@@ -116,13 +123,23 @@ def _dispatch(args, comm):
             raise NotImplementedError('Resuming from checkpoint not supported.')
         from pigeon_amd.clip_embedder import CLIPEmbedding
         from pigeon_amd.embed import embed_images
-        embedder = CLIPEmbedding(args.name, device=dev, panorama=(not args.yfcc), clip_model=_vision_model(args))
+        have_cal = bool(args.calibration) and os.path.exists(args.calibration)
+        embedder = CLIPEmbedding(args.name, device=dev, panorama=(not args.yfcc), clip_model=_vision_model(args),
+                                 calibration=args.calibration if have_cal else None)
+        if have_cal and comm.is_main_process:
+            print(f'Loaded calibration {args.calibration} (fingerprint {embedder.calibration_header["fingerprint"]})')
         if args.synthetic:
             dataset = {'train': _SyntheticImages(args.synthetic, panorama=False)}
         else:
             from datasets import DatasetDict
             dataset = DatasetDict.load_from_disk(args.load[0])
         embed_images(embedder, dataset, comm, out_dir=args.out_dir, num_workers=0 if args.synthetic else 8)
+        if args.calibration and not have_cal and comm.is_main_process:
+            if embedder.guard_stats is not None:
+                embedder.save_calibration(args.calibration, source=f'run.py embed, first batch, {embedder.guard_stats["images"]} images')
+                print(f'Calibration written to {args.calibration}')
+            else:
+                print(f'No calibration written to {args.calibration}: nothing was measured in this run')
         if comm.is_main_process:
             print(f'Embeddings written to {args.out_dir}/')
         return args.out_dir
@@ -145,7 +162,7 @@ def _dispatch(args, comm):
                 dataset = dataset['test'] if args.test else dataset['val']
         results = evaluate(args.name, dataset, yfcc=args.yfcc, base_model=_vision_model(args), refine=True,
                            landmarks=args.landmarks, geocell_path=geocell_path, bank=bank, heading=args.heading,
-                           multi_task=args.multitask)
+                           multi_task=args.multitask, calibration=args.calibration)
         if comm.is_main_process:
             print({k: (v if not hasattr(v, 'shape') or v.shape == () else tuple(v.shape)) for k, v in results.items() if k != 'exact_passes'})
             if 'geocell_certain' in results:
