@@ -42,7 +42,8 @@ extern "C" {
                               * pg_rows_to_slots, pg_requeue_take, pg_scatter_rows, pg_head_wstats (round 6); 5: pg_embedding_debias (round 6);
                               * 6: pg_gemm_plan replaces pg_gemm_route;
                               * 7: pg_vit_precise_plan, pg_op_x3_im2col, pg_op_sum_parts, pg_op_preln, pg_op_attention_x3;
-                              * 7 (+ pg_aux_heads_forward, additive; + pg_fingerprint, pg_vit_fingerprint, additive) */
+                              * 7 (+ pg_aux_heads_forward, additive; + pg_fingerprint, pg_vit_fingerprint, additive;
+                              *    + pg_prep_ragged_plan / _create / _destroy / _forward and pg_prep_item, additive) */
 
 const char* pg_last_error(void);
 int pg_abi_version(void);
@@ -403,6 +404,47 @@ int pg_prep_workspace_bytes(const pg_prep* h, int n_images, size_t* bytes);
  * Asynchronous on `stream`. */
 int pg_prep_forward(pg_prep* h, const void* images_u8, int n_images, void* out, int out_dtype, void* workspace,
                     size_t workspace_bytes, void* stream);
+
+/* Ragged batches: n images of n different sizes in ONE packed buffer, one host-to-device copy and three launches, the same bits
+ * as pg_prep_forward on each image alone.  One descriptor per image (plain data, PG_PREP_ITEM_BYTES bytes):
+ *
+ *   packed buffer  [ n descriptors | image 0 | image 1 | ... ]   every image (in_h, in_w, 3) uint8 RGB, starting at a multiple of
+ *                  16 bytes, back to back in index order behind the n * PG_PREP_ITEM_BYTES bytes of the descriptors; the total is
+ *                  rounded up to 16.  The descriptors travel in the buffer's head, so one copy carries both.
+ *   workspace      [ tables of image 0 | tables of image 1 | ... | temp image ]   per image and axis the bounds (336 x 2 int32:
+ *                  first source pixel, tap count -- Pillow's, i.e. in source coordinates) and the weights (336 x ksize int32, 22-bit
+ *                  fixed point, zero behind the tap count), written by the first kernel; the temp image (the horizontally resized
+ *                  rows the crop's vertical taps read: sum of nrows rows of 336 x 3 bytes, image after image) begins at the
+ *                  first multiple of 256 behind the last table. */
+#define PG_PREP_ITEM_BYTES 80
+#define PG_PREP_RAGGED_MAX_IMAGES 65535
+typedef struct pg_prep_item {
+    uint64_t src_off;                 /* byte offset of the image in the packed buffer (multiple of 16) */
+    int32_t in_h, in_w;               /* source size */
+    int32_t new_h, new_w, top, left;  /* size after the resize, corner of the 336 x 336 crop in it (as pg_prep_geometry) */
+    int32_t ksize_h, ksize_v;         /* taps per output of the horizontal / vertical pass (1 where the axis keeps its size) */
+    int32_t row0, nrows;              /* source rows [row0, row0 + nrows) are the ones the crop's vertical taps read */
+    int32_t tmp_row;                  /* the image's first row in the shared temp image: exclusive prefix sum of nrows */
+    uint32_t bounds_h_off, kk_h_off, bounds_v_off, kk_v_off;   /* byte offsets of the four tables in the workspace (multiples of 16) */
+    int32_t reserved[3];              /* zero */
+} pg_prep_item;
+/* HOST ONLY (no HIP call; works in a process that never opens a GPU): hw = n pairs (height, width); fills items_out[n] and the sizes
+ * of the two buffers.  PG_EINVAL with a message for n < 0, n > PG_PREP_RAGGED_MAX_IMAGES, a null pointer, a size outside 1..16384
+ * and tables that outgrow the descriptor's 32-bit offsets (the image is named).  n = 0: both sizes 0, pointers may be NULL. */
+int pg_prep_ragged_plan(int n, const int32_t* hw, pg_prep_item* items_out, size_t* packed_bytes, size_t* workspace_bytes);
+/* The handle owns the 3 x 256 normalisation table only; it serves every geometry. */
+typedef struct pg_prep_ragged pg_prep_ragged;
+int pg_prep_ragged_create(pg_prep_ragged** out, int device);
+int pg_prep_ragged_destroy(pg_prep_ragged* h);
+/* packed_dev: DEVICE, packed_bytes bytes, 16-byte aligned, laid out as above -- its first n * PG_PREP_ITEM_BYTES bytes MUST be a copy
+ * of items_host (the kernels read the descriptors there; the host copy is what this call checks).  out: DEVICE (n,3,336,336) fp32 or
+ * fp16 as pg_prep_forward.  workspace: DEVICE, 16-byte aligned.  Before anything is launched every descriptor is checked against
+ * its own (in_h, in_w) and against packed_bytes / workspace_bytes -- geometry, range, alignment, ascending overlap-free offsets:
+ * PG_EINVAL (PG_ENOMEM for a workspace too small for the temp image) with a message that names the image.  n = 0 is a no-op (buffers
+ * may be NULL).  Asynchronous on `stream`: three launches whatever the sizes; the horizontal pass stages one source row in dynamic
+ * LDS, widest in_w x 3 + 32 bytes (48 KiB + 32 at in_w = 16384). */
+int pg_prep_ragged_forward(pg_prep_ragged* h, const void* packed_dev, size_t packed_bytes, const pg_prep_item* items_host, int n,
+                           void* out, int out_dtype, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * The one collective of the path: all-gather over RCCL (xGMI inside a node).

@@ -32,6 +32,18 @@ class Bank(C.Structure):
                 ("num_cells", C.c_int64), ("num_protos", C.c_int64), ("num_train", C.c_int64)]
 
 
+class PrepItem(C.Structure):
+    """pg_prep_item (include/pigeon_hip.h): one image of a ragged preprocessing batch, PREP_ITEM_BYTES bytes."""
+    _fields_ = [("src_off", C.c_uint64), ("in_h", C.c_int32), ("in_w", C.c_int32), ("new_h", C.c_int32), ("new_w", C.c_int32),
+                ("top", C.c_int32), ("left", C.c_int32), ("ksize_h", C.c_int32), ("ksize_v", C.c_int32), ("row0", C.c_int32),
+                ("nrows", C.c_int32), ("tmp_row", C.c_int32), ("bounds_h_off", C.c_uint32), ("kk_h_off", C.c_uint32),
+                ("bounds_v_off", C.c_uint32), ("kk_v_off", C.c_uint32), ("reserved", C.c_int32 * 3)]
+
+
+PREP_ITEM_BYTES = 80
+assert C.sizeof(PrepItem) == PREP_ITEM_BYTES
+
+
 # name -> (restype, argtypes); must list EVERY symbol declared in include/pigeon_hip.h (tests check this)
 _P, _I, _I64, _F, _D, _SZ = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_double, C.c_size_t
 SIGNATURES = {
@@ -78,6 +90,10 @@ SIGNATURES = {
     "pg_prep_geometry": (_I, [_P, C.POINTER(C.c_int32)]),
     "pg_prep_workspace_bytes": (_I, [_P, _I, C.POINTER(_SZ)]),
     "pg_prep_forward": (_I, [_P, _P, _I, _P, _I, _P, _SZ, _P]),
+    "pg_prep_ragged_plan": (_I, [_I, C.POINTER(C.c_int32), C.POINTER(PrepItem), C.POINTER(_SZ), C.POINTER(_SZ)]),
+    "pg_prep_ragged_create": (_I, [C.POINTER(_P), _I]),
+    "pg_prep_ragged_destroy": (_I, [_P]),
+    "pg_prep_ragged_forward": (_I, [_P, _P, _SZ, C.POINTER(PrepItem), _I, _P, _I, _P, _SZ, _P]),
     "pg_proto_build": (_I, [_P, _I, _I64, _P, _P, _I64, _P, _P]),
     "pg_haversine_matrix": (_I, [_P, _I, _P, _I, _I, _P, _P]),
     "pg_haversine_pairs": (_I, [_P, _P, _I, _I64, _P, _P]),

@@ -8,6 +8,7 @@ runs entirely inside libpigeon_hip.so.
 from __future__ import annotations
 
 import os
+import threading
 from types import SimpleNamespace
 from typing import Callable, Dict, Optional
 
@@ -17,6 +18,7 @@ from torch import Tensor
 
 from . import hip_ops, synthetic
 from .config import CLIP_MODEL, OPENAI_CLIP_MEAN, OPENAI_CLIP_STD
+from .packing import PackedImages, as_rgb_array, check_rgb_u8, chunk_by_bytes, pack_images, pack_into, packed_layout  # noqa: F401  (re-exported)
 from .utils import load_state_dict
 
 
@@ -236,13 +238,85 @@ def _staging_done(t: Tensor) -> None:
             return
 
 
+# The ragged path (pg_prep_ragged_forward): one RaggedPreprocessor per device -- it owns the normalisation table and a workspace,
+# nothing per geometry -- and ONE pinned staging buffer per device, grown when a batch needs more: [tensor, event of the last copy].
+_RAGGED: Dict = {}
+_RAGGED_STAGING: Dict = {}
+# Lists of more than one shape take the ragged path: 512 images in 128 sizes measured 17.7 ms against 45.0 ms grouped by size
+# (tools/prep_ragged_ab.py, profiles/r07/prep_ragged_ab.txt); PIGEON_PREP_RAGGED=0 keeps them on the grouped path.
+RAGGED_LISTS = os.environ.get("PIGEON_PREP_RAGGED", "1") not in ("", "0")
+RAGGED_MAX_BYTES = 256 << 20                                       # packed bytes per ragged call of the list path
+# gpu_preprocess fills shared pinned staging buffers (_STAGING, _RAGGED_STAGING) before it queues their copies: one caller at a time
+_PREP_LOCK = threading.RLock()
+
+
+def _ragged_preprocessor(device_index: int) -> "hip_ops.RaggedPreprocessor":
+    p = _RAGGED.get(int(device_index))
+    if p is None:
+        p = _RAGGED[int(device_index)] = hip_ops.RaggedPreprocessor(int(device_index))
+    return p
+
+
+def _ragged_staging(nbytes: int, dev) -> Tensor:
+    ent = _RAGGED_STAGING.get(int(dev.index))
+    if ent is None or ent[0].numel() < nbytes:
+        grown = nbytes if ent is None else max(nbytes, ent[0].numel() * 3 // 2)
+        ent = _RAGGED_STAGING[int(dev.index)] = [torch.empty(grown, dtype=torch.uint8).pin_memory(), None]
+    elif ent[1] is not None:
+        ent[1].synchronize()                                       # rewritten only after the last copy out of it has run
+    return ent[0][:nbytes]
+
+
+def _ragged_forward(host: Tensor, plan, dev, out_dtype, staged: bool) -> Tensor:
+    """`host`: plan.packed_bytes bytes with the pixels in place.  The descriptors go into its head, one copy, one forward."""
+    host.numpy()[:plan.header_bytes] = plan.header()
+    with torch.cuda.device(dev):
+        on_dev = host.to(dev, non_blocking=True)
+        if staged:
+            ent = _RAGGED_STAGING[int(dev.index)]
+            ent[1] = torch.cuda.Event()
+            ent[1].record()
+        return _ragged_preprocessor(dev.index).forward(on_dev, plan, out_dtype, header_written=True)
+
+
+def _gpu_preprocess_packed(packed: PackedImages, dev, out_dtype) -> Tensor:
+    data = packed.data
+    if not torch.is_tensor(data) or data.dtype != torch.uint8 or data.dim() != 1 or data.is_cuda or not data.is_contiguous():
+        raise ValueError("gpu_preprocess: PackedImages.data must be a contiguous 1-D uint8 host tensor")
+    plan = hip_ops.ragged_plan(packed.size_list())
+    if data.numel() != plan.packed_bytes:
+        raise ValueError(f"gpu_preprocess: PackedImages holds {data.numel()} bytes, its {plan.n} sizes need {plan.packed_bytes}")
+    if plan.n == 0:
+        return torch.empty((0, 3, 336, 336), dtype=out_dtype, device=dev)
+    if data.is_pinned():
+        out = _ragged_forward(data, plan, dev, out_dtype, staged=False)        # its head was left blank for exactly this
+        with torch.cuda.device(dev):
+            packed.copy_event = torch.cuda.Event()                 # the caller may rewrite the pinned buffer once this has passed
+            packed.copy_event.record()
+        return out
+    stage = _ragged_staging(plan.packed_bytes, dev)
+    stage.copy_(data)
+    return _ragged_forward(stage, plan, dev, out_dtype, staged=True)
+
+
 def gpu_preprocess(images, device="cuda", out_dtype: torch.dtype = torch.float32) -> Tensor:
-    """CLIP preprocessing on the GPU (pg_prep_forward): `images` is a uint8 RGB tensor / ndarray (N,H,W,3) or (H,W,3),
-    or a list of PIL images / arrays (grouped by size; every size gets its own coefficient tables).  Returns the
+    """See `_gpu_preprocess`.  Callers from several threads are served one after the other: the pinned staging buffers are shared."""
+    with _PREP_LOCK:
+        return _gpu_preprocess(images, device, out_dtype)
+
+
+def _gpu_preprocess(images, device="cuda", out_dtype: torch.dtype = torch.float32) -> Tensor:
+    """CLIP preprocessing on the GPU: `images` is a uint8 RGB tensor / ndarray (N,H,W,3) or (H,W,3), a list of PIL images / arrays,
+    or a `PackedImages`.  Tensors and lists of ONE shape run pg_prep_forward (a handle per geometry); a `PackedImages` and a list of
+    several shapes run pg_prep_ragged_forward: one packed staging buffer and, per chunk of at most RAGGED_MAX_BYTES (256 MiB) of packed
+    bytes, one copy and three launches whatever the sizes.  A PINNED `PackedImages` is copied from in place: its head is overwritten
+    with the descriptors and the buffer belongs to the call until `copy_event` (set on the object) has passed.  Returns the
     (N,3,336,336) pixel_values on `device`, bit-identical to `clip_preprocess` / the reference's CLIPProcessor."""
     dev = torch.device(device)
     if dev.index is None:
         dev = torch.device("cuda", torch.cuda.current_device())
+    if isinstance(images, PackedImages):
+        return _gpu_preprocess_packed(images, dev, out_dtype)
     if hasattr(images, "convert"):                                 # one PIL image, as `processor(images=img)` accepts it
         images = [images]
     if torch.is_tensor(images) or isinstance(images, np.ndarray):
@@ -252,11 +326,22 @@ def gpu_preprocess(images, device="cuda", out_dtype: torch.dtype = torch.float32
         groups = [(None, t)]
     else:
         # (a PIL image that is RGB already is not copied by `convert`: a serving request's four views are; round 6)
-        arrs = [np.asarray(im if getattr(im, "mode", None) == "RGB" else im.convert("RGB")) if hasattr(im, "convert") else np.asarray(im)
-                for im in images]
+        arrs = [as_rgb_array(im) for im in images]
         by_size: Dict = {}
         for i, a in enumerate(arrs):
             by_size.setdefault(a.shape, []).append(i)
+        if RAGGED_LISTS and len(by_size) > 1:
+            for a in arrs:
+                check_rgb_u8(a)
+            # (a list beyond the byte budget or the 65535 images of one call goes in consecutive chunks: the staging buffer and the
+            # workspace stay bounded, and no list the grouped path took is refused)
+            outs = []
+            for lo, hi in chunk_by_bytes([a.shape[:2] for a in arrs], RAGGED_MAX_BYTES):
+                plan = hip_ops.ragged_plan([a.shape[:2] for a in arrs[lo:hi]])
+                stage = _ragged_staging(plan.packed_bytes, dev)    # the images go straight to their places in the pinned buffer
+                pack_into(arrs[lo:hi], [int(it.src_off) for it in plan.items], stage.numpy())
+                outs.append(_ragged_forward(stage, plan, dev, out_dtype, staged=True))
+            return outs[0] if len(outs) == 1 else torch.cat(outs, dim=0)
         groups = []
         for idx in by_size.values():
             a0 = arrs[idx[0]]
@@ -410,7 +495,7 @@ class CLIPEmbedding(torch.nn.Module):
         """reference models/clip_embedder.py:42-66"""
         with torch.no_grad():
             if isinstance(image, Tensor) == False or image.dtype == torch.uint8:
-                # PIL image(s) / uint8 HWC arrays: resize + crop + normalise on the GPU (bit-identical to the
+                # PIL image(s) / uint8 HWC arrays / a PackedImages: resize + crop + normalise on the GPU (bit-identical to the
                 # reference's host-side CLIPProcessor); 16-bit pixels when the encoder's MFMA operands are fp16
                 dev = self.device if type(self.device) == str else f'cuda:{self.device}'
                 pixel_values = gpu_preprocess(image, dev, self._pixel_dtype())

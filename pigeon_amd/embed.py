@@ -42,6 +42,47 @@ class EmbedDataset:
         return len(self.dataset)
 
 
+class RawImageDataset:
+    """The raw flavour of EmbedDataset: yields (uint8 (H,W,3) RGB array, index).  Decoding and `convert('RGB')` run here, in the
+    DataLoader worker; nothing is resized -- that happens on the GPU (pg_prep_ragged_forward), for the whole batch at once."""
+
+    def __init__(self, dataset):
+        self.dataset = dataset
+
+    def __getitem__(self, idx):
+        from .packing import as_rgb_array, check_rgb_u8
+        data = self.dataset[idx]
+        a = as_rgb_array(data['image'])
+        check_rgb_u8(a)
+        return a, data['index']
+
+    def __len__(self):
+        return len(self.dataset)
+
+
+MAX_PACKED_BYTES = 256 << 20
+
+
+def collate_packed(batch, max_packed_bytes: int = MAX_PACKED_BYTES):
+    """collate_fn for RawImageDataset: [(array, index), ...] -> ([PackedImages, ...], index tensor).  The batch is cut, in order,
+    into chunks of at most `max_packed_bytes` packed bytes each (an image above the budget travels alone), which bounds the
+    staging buffer and the GPU workspace whatever the photo sizes; the chunks' images, concatenated, are the batch's."""
+    from .packing import chunk_by_bytes, pack_images
+    arrs = [a for a, _ in batch]
+    chunks = [pack_images(arrs[lo:hi]) for lo, hi in chunk_by_bytes([a.shape[:2] for a in arrs], max_packed_bytes)]
+    return chunks, torch.as_tensor([int(i) for _, i in batch], dtype=torch.int64)
+
+
+class _ChunkedModel:
+    """model([PackedImages, ...]) -> the chunks' embeddings, concatenated: one step's output for compute_embeddings."""
+
+    def __init__(self, model):
+        self.model = model
+
+    def __call__(self, chunks):
+        return torch.cat([self.model(c) for c in chunks], dim=0)
+
+
 def _stack_padded(batches, fill):
     """np.stack of per-step arrays; a shorter last step is padded to the common length (fill None: indices -> int max so
     they sort last)."""
@@ -85,9 +126,15 @@ def compute_embeddings(name: str, model: Any, data: Iterable, accelerator: Commu
 
 def embed_images(loaded_model: Any, dataset, accelerator: Optional[Communicator] = None,
                  batch_size: int = EMBED_BATCH_SIZE_PER_GPU, num_workers: int = 8,
-                 out_dir: str = 'data/landmark_embeddings'):
+                 out_dir: str = 'data/landmark_embeddings', raw_images: bool = False,
+                 max_packed_bytes: int = MAX_PACKED_BYTES):
     """reference preprocessing/embed.py:45-83: wrap every split in EmbedDataset, one DataLoader per split
-    (bs 512 per GPU, shuffle False), shard batches over ranks, embed train/val/test with a barrier between."""
+    (bs 512 per GPU, shuffle False), shard batches over ranks, embed train/val/test with a barrier between.
+
+    raw_images=True (one image of any size per item): the workers decode and PACK (RawImageDataset, collate_packed) and the model
+    resizes on the GPU -- uint8 pixels of the source size cross the bus instead of 1.35 MB of fp32 per image, and no worker runs
+    Pillow's resize.  The batches are dealt to the ranks by the same rule, applied to the sample indices before anything is
+    loaded, so every rank decodes its own batches only.  What is written is the same."""
     from torch.utils.data import DataLoader
     accelerator = accelerator or Communicator()
     results = {}
@@ -95,8 +142,18 @@ def embed_images(loaded_model: Any, dataset, accelerator: Optional[Communicator]
     for split_name in ('train', 'val', 'test'):
         if split_name not in dataset:
             continue
-        loader = DataLoader(EmbedDataset(dataset[split_name]), batch_size, shuffle=False, num_workers=num_workers)
-        sharded = shard_batches(loader, accelerator.rank, accelerator.world_size)
-        results[split_name] = compute_embeddings(split_name, loaded_model, sharded, accelerator, out_dir)
+        if raw_images:
+            from functools import partial
+            n = len(dataset[split_name])
+            mine = list(shard_batches([list(range(i, min(i + batch_size, n))) for i in range(0, n, batch_size)],
+                                      accelerator.rank, accelerator.world_size))
+            sharded = DataLoader(RawImageDataset(dataset[split_name]), batch_sampler=mine, num_workers=num_workers,
+                                 collate_fn=partial(collate_packed, max_packed_bytes=max_packed_bytes))
+            model = _ChunkedModel(loaded_model)
+        else:
+            loader = DataLoader(EmbedDataset(dataset[split_name]), batch_size, shuffle=False, num_workers=num_workers)
+            sharded = shard_batches(loader, accelerator.rank, accelerator.world_size)
+            model = loaded_model
+        results[split_name] = compute_embeddings(split_name, model, sharded, accelerator, out_dir)
         accelerator.wait_for_everyone()
     return results

@@ -281,6 +281,84 @@ class Preprocessor:
             pass
 
 
+class RaggedPlan:
+    """What pg_prep_ragged_plan makes of a list of (height, width): one descriptor per image (`items`, a ctypes array of
+    _lib.PrepItem; `header()` = the same bytes as a uint8 array, what the head of the packed buffer must hold) and the sizes of the
+    packed buffer and of the workspace.  Host data only."""
+
+    def __init__(self, sizes, items, packed_bytes: int, workspace_bytes: int):
+        self.sizes, self.items = sizes, items
+        self.n = len(sizes)
+        self.packed_bytes, self.workspace_bytes = int(packed_bytes), int(workspace_bytes)
+        self.header_bytes = self.n * _lib.PREP_ITEM_BYTES
+
+    def header(self):
+        import numpy as np
+        return np.frombuffer(self.items, dtype=np.uint8, count=self.header_bytes) if self.n else np.zeros(0, dtype=np.uint8)
+
+
+def ragged_plan(sizes) -> RaggedPlan:
+    """pg_prep_ragged_plan: the layout of a batch of images of the given (height, width) pairs.  No HIP call: needs the library,
+    not a GPU."""
+    sizes = [(int(h), int(w)) for h, w in sizes]
+    n = len(sizes)
+    hw = (C.c_int32 * (2 * n))(*[v for s in sizes for v in s])
+    items = (_lib.PrepItem * n)()
+    packed, ws = C.c_size_t(), C.c_size_t()
+    check(load().pg_prep_ragged_plan(n, hw, items, C.byref(packed), C.byref(ws)), "pg_prep_ragged_plan")
+    return RaggedPlan(sizes, items, packed.value, ws.value)
+
+
+class RaggedPreprocessor:
+    """CLIP preprocessing on the GPU for a batch of images of DIFFERENT sizes in one packed buffer (layout: pigeon_hip.h,
+    pg_prep_ragged_forward): the same bits per image as `Preprocessor(h, w)` on it alone, in three launches per call."""
+
+    def __init__(self, device: int = 0):
+        _lib.require_gpu()
+        self._h = C.c_void_p()
+        check(load().pg_prep_ragged_create(C.byref(self._h), int(device)), "pg_prep_ragged_create")
+        self.device = int(device)
+        self._ws = None
+
+    plan = staticmethod(ragged_plan)
+
+    def forward(self, packed_u8: torch.Tensor, plan: RaggedPlan, out_dtype: torch.dtype = torch.float32,
+                header_written: bool = False) -> torch.Tensor:
+        """packed_u8: DEVICE 1-D uint8 of plan.packed_bytes bytes.  The kernels read the descriptors from its head: they are copied
+        there from the plan unless the caller says it has written them already (`header_written`, what gpu_preprocess does on the
+        host side of its one copy)."""
+        _dev(packed_u8, torch.uint8)
+        if packed_u8.dim() != 1 or packed_u8.numel() != plan.packed_bytes:
+            raise _lib.PigeonHipError(f"packed buffer must be 1-D uint8 of {plan.packed_bytes} bytes, got {tuple(packed_u8.shape)}")
+        if packed_u8.device.index != self.device:
+            raise _lib.PigeonHipError(f"packed buffer is on {packed_u8.device}, the preprocessor on cuda:{self.device}")
+        if out_dtype not in (torch.float32, torch.float16):
+            raise _lib.PigeonHipError("preprocess output dtype must be float32 or float16")
+        out = torch.empty((plan.n, 3, 336, 336), dtype=out_dtype, device=packed_u8.device)
+        if plan.n == 0:
+            return out
+        if self._ws is None or self._ws.numel() < plan.workspace_bytes:
+            self._ws = torch.empty(plan.workspace_bytes, dtype=torch.uint8, device=packed_u8.device)
+        if not header_written:
+            packed_u8[:plan.header_bytes].copy_(torch.from_numpy(plan.header().copy()))
+        check(load().pg_prep_ragged_forward(self._h, _p(packed_u8), plan.packed_bytes, plan.items, plan.n, _p(out), _PIXDT[out_dtype],
+                                            _p(self._ws), self._ws.numel(), _stream()), "pg_prep_ragged_forward")
+        return out
+
+    __call__ = forward
+
+    def close(self):
+        if self._h:
+            load().pg_prep_ragged_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 # ----------------------------------------------------------------------------------------- ViT encoder handle
 class VitEncoder:
     """Owns a pg_vit handle: bf16-packed weights resident in HBM, forward = ViT-L/14-336 + token mean.

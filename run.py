@@ -53,6 +53,9 @@ argp.add_argument('--exact-top1', dest='exact_top1', action='store_true', defaul
                        "encoder's exact mode, so that geocell argmax and refined point are the reference's fp32 ones (PIGEON_EXACT_TOP1=1)")
 argp.add_argument('--no-exact-top1', dest='exact_top1', action='store_false',
                   help="the 16-bit path alone (PIGEON_EXACT_TOP1=0): embeddings within 1e-3, discrete outputs not guaranteed")
+argp.add_argument('--raw-images', dest='raw_images', action='store_true', default=False,
+                  help="embed: items hold one image of any size each (PIL / uint8 array); the DataLoader workers decode and pack, "
+                       "the resize + crop + normalise runs on the GPU for the whole mixed-size batch at once (pg_prep_ragged_forward)")
 argp.add_argument('--calibration', default=None, metavar='FILE',
                   help="encoder calibration file (bias vector, certainty tolerance, exact-encoder verdict; keyed by the weight "
                        "fingerprint).  If FILE exists it is loaded before the first batch -- every rank loads the same one, nothing is "
@@ -133,7 +136,8 @@ def _dispatch(args, comm):
         else:
             from datasets import DatasetDict
             dataset = DatasetDict.load_from_disk(args.load[0])
-        embed_images(embedder, dataset, comm, out_dir=args.out_dir, num_workers=0 if args.synthetic else 8)
+        embed_images(embedder, dataset, comm, out_dir=args.out_dir, num_workers=0 if args.synthetic else 8,
+                     raw_images=args.raw_images)
         if args.calibration and not have_cal and comm.is_main_process:
             if embedder.guard_stats is not None:
                 embedder.save_calibration(args.calibration, source=f'run.py embed, first batch, {embedder.guard_stats["images"]} images')
