@@ -43,7 +43,8 @@ extern "C" {
                               * 6: pg_gemm_plan replaces pg_gemm_route;
                               * 7: pg_vit_precise_plan, pg_op_x3_im2col, pg_op_sum_parts, pg_op_preln, pg_op_attention_x3;
                               * 7 (+ pg_aux_heads_forward, additive; + pg_fingerprint, pg_vit_fingerprint, additive;
-                              *    + pg_prep_ragged_plan / _create / _destroy / _forward and pg_prep_item, additive) */
+                              *    + pg_prep_ragged_plan / _create / _destroy / _forward and pg_prep_item, additive;
+                              *    + pg_haversine_blocks, pg_optics_graph, pg_optics_plan, pg_tune_optics_lds_points, additive) */
 
 const char* pg_last_error(void);
 int pg_abi_version(void);
@@ -488,6 +489,34 @@ int pg_haversine_pairs(const double* x, const void* y, int y_dtype, int64_t N, d
 /* Label smoothing (reference preprocessing/utils.py:7-19): out = exp(-(d - rowmin(d)) / constant), NaN/inf -> 0.
  * distances, out: DEVICE (N,M) fp64 (may alias). */
 int pg_smooth_labels(const double* distances, int N, int M, double constant, double* out, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * The prototype cluster table (reference dataset_creation/prototype/prototype.py:121-149): per-geocell OPTICS graphs, csrc/optics.hip.
+ * Cells are packed: cell c owns points cell_off[c] .. cell_off[c+1] and the row-major n x n matrix at element mat_off[c] (n its point
+ * count; mat_off[c+1] - mat_off[c] >= n * n).  cell_off and mat_off are HOST arrays of C + 1 int64 -- the calls check them before
+ * anything is launched, copy them to the device themselves, and SYNCHRONISE `stream` before they return.  C = 0 is a no-op.
+ * ------------------------------------------------------------------------------------------------ */
+/* pts DEVICE (N,2) fp64 [lng,lat] degrees, row r = packed point r; out DEVICE fp64: the great-circle distances in km among each cell's
+ * own points: element (i, j), i <= j, is pg_haversine_matrix's fp64 arithmetic bit for bit, (j, i) mirrors it (the matrix is exactly
+ * symmetric, as the reference's numpy matrix is), and every 0.0 and every pair of identical coordinates (the diagonal, exact
+ * duplicates) is written as `zero_as` (the reference: 1e-5, prototype.py:130-133).  One launch for all cells. */
+int pg_haversine_blocks(const double* pts, const int64_t* cell_off, const int64_t* mat_off, int C, double zero_as, double* out,
+                        void* stream);
+/* sklearn.cluster._optics.compute_optics_graph(metric='precomputed', max_eps=inf, min_samples) of every cell, bit for bit (the
+ * definition: csrc/optics.hip's header, restated in tests/_opticsref.py).  dist DEVICE fp64 (non-negative, inf allowed); the outputs are
+ * DEVICE arrays packed by cell_off from the first cell on: ordering int64 and pred int64 are LOCAL to the cell (0 .. n-1, pred -1 where
+ * unset), core and reach fp64.  PG_EINVAL, named and before any launch, for min_samples < 2, a cell of fewer than min_samples points and
+ * a cell of more than 32768 points. */
+int pg_optics_graph(const double* dist, const int64_t* cell_off, const int64_t* mat_off, int C, int min_samples, int64_t* ordering,
+                    double* core, double* reach, int64_t* pred, void* stream);
+/* What pg_optics_graph does with a cell of n points under the current knobs (host arithmetic, no GPU; the same refusals):
+ *   out[0]  the form of the ordering kernel: 0 = reach / pred / processed flags in LDS, 1 = in global memory (same bits)
+ *   out[1]  threads of the cell's workgroup
+ *   out[2]  the largest n of form 0
+ *   out[3]  the largest n accepted */
+int pg_optics_plan(int64_t n, int min_samples, int32_t out[4]);
+/* Lowers pg_optics_plan's out[2] (1 .. its default; 0 restores the default) so that tests reach form 1 at small n.  Process-wide. */
+int pg_tune_optics_lds_points(int max_points);
 
 /* ------------------------------------------------------------------------------------------------
  * Building-block ops (exported so the parity tests can check every kernel in isolation through the ABI).

@@ -16,7 +16,7 @@ OBJ = os.path.join(CSRC, "build")
 LIB = os.path.join(HERE, "libpigeon_hip.so")
 # the product library: production kernels only
 SOURCES = ["vit.hip", "gemm_plan.hip", "gemm_bf16.hip", "gemm_pp.hip", "gemm_pp6.hip", "gemm_tail.hip", "gemm_mid.hip", "attention.hip", "rowops.hip", "precise.hip",
-           "preprocess.hip", "geo_proto.hip", "head.hip", "refine.hip", "certainty.hip", "aux_heads.hip", "requeue.hip", "fingerprint.hip", "comm.hip"]
+           "preprocess.hip", "geo_proto.hip", "head.hip", "refine.hip", "certainty.hip", "aux_heads.hip", "requeue.hip", "fingerprint.hip", "comm.hip", "optics.hip"]
 HEADERS = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "pigeon_internal.h"), os.path.join(CSRC, "gemm_epi.h"),
            os.path.join(CSRC, "attention_common.h"), os.path.join(CSRC, "certainty_common.h"),
            os.path.join(os.path.dirname(HERE), "include", "pigeon_hip.h")]
@@ -61,7 +61,7 @@ def _build(OBJ: str, LIB: str, FLAGS, force: bool, verbose: bool, SOURCES) -> st
 
     def compile_one(job):
         s, o = job
-        cmd = [cc] + FLAGS + ["-I", CSRC] + (["-ffp-contract=off"] if s.endswith("preprocess.hip") else []) + ["-c", s, "-o", o]
+        cmd = [cc] + FLAGS + ["-I", CSRC] + (["-ffp-contract=off"] if s.endswith(("preprocess.hip", "optics.hip")) else []) + ["-c", s, "-o", o]
         if verbose:
             print("[pigeon_amd.build]", " ".join(cmd), flush=True)
         r = subprocess.run(cmd, capture_output=True, text=True)

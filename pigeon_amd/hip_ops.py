@@ -236,6 +236,80 @@ def smooth_labels(distances: torch.Tensor, constant: float) -> torch.Tensor:
     return out
 
 
+# ----------------------------------------------------------------------------------------- prototype cluster table
+def _cell_tables(who: str, cell_off: torch.Tensor, mat_off: Optional[torch.Tensor]):
+    """The CSR invariants of a packed batch of cells, on the host (the C calls read both tables there): cell_off rises from 0, cell c's
+    matrix has room for its n x n elements.  Returns (cell_off, mat_off) as contiguous int64 CPU tensors; mat_off=None packs densely."""
+    if cell_off.dtype != torch.int64 or cell_off.dim() != 1 or cell_off.numel() < 1:
+        raise _lib.PigeonHipError(f"{who}: cell_off must be an int64 vector of C + 1 entries")
+    off = cell_off.cpu().contiguous()
+    n = off[1:] - off[:-1]
+    if int(off[0]) != 0 or bool((n < 0).any()):
+        raise _lib.PigeonHipError(f"{who}: cell_off must rise from 0")
+    if mat_off is None:
+        mo = torch.zeros_like(off)
+        torch.cumsum(n * n, 0, out=mo[1:])
+    else:
+        if mat_off.dtype != torch.int64 or mat_off.shape != cell_off.shape:
+            raise _lib.PigeonHipError(f"{who}: mat_off must be an int64 vector as long as cell_off")
+        mo = mat_off.cpu().contiguous()
+        if int(mo[0]) < 0 or bool(((mo[1:] - mo[:-1]) < n * n).any()):
+            raise _lib.PigeonHipError(f"{who}: mat_off must leave every cell room for its n x n matrix")
+    return off, mo
+
+
+def haversine_blocks(pts: torch.Tensor, cell_off: torch.Tensor, zero_as: float = 1e-5):
+    """pg_haversine_blocks: pts (N,2) fp64 [lng,lat] on the device, cell_off (C+1,) int64 -> (dist, mat_off): the cells' own n x n
+    distance matrices in km, packed densely (cell c at dist[mat_off[c]:mat_off[c+1]], row-major), exactly symmetric (the upper
+    triangle is haversine_matrix's, bit for bit), zeros and identical points as `zero_as`.  One launch."""
+    _dev(pts, torch.float64)
+    _shape(pts, "pts", None, 2)
+    off, mo = _cell_tables("haversine_blocks", cell_off, None)
+    if int(off[-1]) != pts.shape[0]:
+        raise _lib.PigeonHipError(f"haversine_blocks: cell_off ends at {int(off[-1])}, pts has {pts.shape[0]} rows")
+    out = torch.empty((int(mo[-1]),), dtype=torch.float64, device=pts.device)
+    check(load().pg_haversine_blocks(_p(pts), _p(off), _p(mo), off.numel() - 1, float(zero_as), _p(out), _stream()),
+          "pg_haversine_blocks")
+    return out, mo
+
+
+def optics_graph(dist: torch.Tensor, cell_off: torch.Tensor, mat_off: torch.Tensor, min_samples: int) -> Dict[str, torch.Tensor]:
+    """pg_optics_graph: dist fp64 on the device (the packed matrices), cell_off / mat_off (C+1,) int64 -> ordering, core, reach, pred,
+    packed by cell_off; ordering and pred are local to the cell.  sklearn's compute_optics_graph(metric='precomputed'), bit for bit."""
+    _dev(dist, torch.float64)
+    if dist.dim() != 1:
+        raise _lib.PigeonHipError(f"optics_graph: dist must be the flat packed matrices, got shape {tuple(dist.shape)}")
+    off, mo = _cell_tables("optics_graph", cell_off, mat_off)
+    if int(mo[-1]) > dist.numel():
+        raise _lib.PigeonHipError(f"optics_graph: mat_off ends at {int(mo[-1])}, dist has {dist.numel()} elements")
+    min_samples = int(min_samples)
+    n = off[1:] - off[:-1]
+    if min_samples < 2:
+        raise _lib.PigeonHipError(f"optics_graph: min_samples must be at least 2 (got {min_samples})")
+    if n.numel() and int(n.min()) < min_samples:
+        raise _lib.PigeonHipError(f"optics_graph: cell {int(n.argmin())} has {int(n.min())} points, fewer than min_samples = {min_samples}")
+    N = int(off[-1])
+    ordering = torch.empty((N,), dtype=torch.int64, device=dist.device)
+    pred = torch.empty((N,), dtype=torch.int64, device=dist.device)
+    core = torch.empty((N,), dtype=torch.float64, device=dist.device)
+    reach = torch.empty((N,), dtype=torch.float64, device=dist.device)
+    check(load().pg_optics_graph(_p(dist), _p(off), _p(mo), off.numel() - 1, min_samples, _p(ordering), _p(core), _p(reach), _p(pred),
+                                 _stream()), "pg_optics_graph")
+    return {"ordering": ordering, "core": core, "reach": reach, "pred": pred}
+
+
+def optics_plan(n: int, min_samples: int) -> dict:
+    """pg_optics_plan: what pg_optics_graph does with a cell of n points under the current knobs (host arithmetic, no GPU)."""
+    out = (C.c_int32 * 4)()
+    check(load().pg_optics_plan(int(n), int(min_samples), out), "pg_optics_plan")
+    return {"form": int(out[0]), "threads": int(out[1]), "lds_points": int(out[2]), "max_points": int(out[3])}
+
+
+def tune_optics_lds_points(max_points: int) -> None:
+    """pg_tune_optics_lds_points: the largest cell whose ordering state stays in LDS (0 = the default).  Bit-identical either way."""
+    check(load().pg_tune_optics_lds_points(int(max_points)), "pg_tune_optics_lds_points")
+
+
 # ----------------------------------------------------------------------------------------- image preprocessing
 class Preprocessor:
     """CLIP preprocessing on the GPU for one input geometry: (N,H,W,3) uint8 RGB -> (N,3,336,336) pixel_values,
