@@ -279,7 +279,9 @@ def test_geo_kernels_match_reference_outputs(env, golden_dir):
     (preprocessing/geo_utils.py:40-74, preprocessing/utils.py:7-19) stored in tests/golden/geo.npz, and against the host
     restatement oracle/geo_oracle.py on fresh inputs.  fp64 in: 1e-12 relative.  fp32 points: deg2rad / cos(lat) run in
     fp32 on both sides; the device uses the correctly rounded cos, torch's CPU kernel is <= 1 ulp -- one fp32 ulp of
-    cos(lat) moves near-antipodal distances by up to 0.2 km, hence 0.5 km / 3e-5 there (stated, not bit-exact by contract)."""
+    cos(lat) moves near-antipodal distances by up to 0.2 km, hence 0.5 km / 3e-5 there (stated, not bit-exact by contract).
+    The per-element tier is tests/test_gpu_geo.py: longdouble truths with a derived bound (16 U), the fp32 arms against their own
+    contract, the shapes around the 256-wide blocks, the poles, the antimeridian and antipodes."""
     from oracle import geo_oracle
     from pigeon_amd import geo_utils
     g = _gold(golden_dir, "geo.npz")

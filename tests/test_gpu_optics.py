@@ -1,6 +1,7 @@
 """The prototype cluster table on the GPU (run with -m gpu on an MI355X): pg_haversine_blocks against pg_haversine_matrix (bits) and
 numpy (1e-12), pg_optics_graph against the numpy restatement tests/_opticsref.py on the device's own matrix and against sklearn's
-recorded arrays (array_equal on ordering, core distances, reachability, predecessors), both forms of the ordering kernel, and
+recorded arrays (array_equal on ordering, core distances, reachability, predecessors), both forms of the ordering kernel at every
+thread count, cells packed from a non-zero base, empty cells, a side stream, the batching of prototypes.optics_graph_cells, and
 ProtoDataset.generate against the CSV the reference wrote."""
 import os
 
@@ -185,6 +186,150 @@ def test_graph_equals_recorded_sklearn(ops, golden_dir):
         g = run_graph(ops, torch.from_numpy(D.reshape(-1).copy()).to(DEV), cell_off, mat_off, int(ms))
         for name in NAMES:
             assert np.array_equal(g[name], z[f"{name}_{n}"]), (int(n), name)
+
+
+# ------------------------------------------------------------------------------------------------ device paths off the beaten track
+SENTINEL, GUARD = -7, 64                                            # exact in int64 and in fp64
+
+
+def guarded(n, dtype):
+    return torch.full((n + GUARD,), SENTINEL, dtype=dtype, device=DEV)
+
+
+def raw_cells(ops, pts, cell_off, ms, stream=None):
+    """pg_haversine_blocks and pg_optics_graph through the C ABI, which (unlike the wrappers) takes a cell_off that does not start at 0:
+    pts is indexed by the packed row itself, the outputs are packed from the first cell on.  -> (dist, {ordering, core, reach, pred})
+    as numpy, every output in front of sentinel elements that must stay untouched."""
+    from pigeon_amd import _lib
+    L = _lib.load()
+    off = cell_off.contiguous()
+    n = off[1:] - off[:-1]
+    mo = torch.zeros_like(off)
+    torch.cumsum(n * n, 0, out=mo[1:])
+    N, C, total = int(off[-1] - off[0]), off.numel() - 1, int(mo[-1])
+    host = lambda t: ops._p(t)
+    dist = guarded(total, torch.float64)
+    before = pts.clone()
+    _lib.check(L.pg_haversine_blocks(ops._p(pts), host(off), host(mo), C, 1e-5, ops._p(dist), ops._stream()), "pg_haversine_blocks")
+    out = {"ordering": guarded(N, torch.int64), "core": guarded(N, torch.float64), "reach": guarded(N, torch.float64),
+           "pred": guarded(N, torch.int64)}
+    _lib.check(L.pg_optics_graph(ops._p(dist), host(off), host(mo), C, ms, ops._p(out["ordering"]), ops._p(out["core"]),
+                                 ops._p(out["reach"]), ops._p(out["pred"]), ops._stream()), "pg_optics_graph")
+    torch.cuda.synchronize()
+    assert torch.equal(pts.view(torch.int64), before.view(torch.int64)), "pts changed"
+    for name, t in [("dist", dist)] + list(out.items()):
+        assert bool((t[(total if name == "dist" else N):] == SENTINEL).all()), f"{name}: wrote past its end"
+    return dist[:total].cpu().numpy(), {k: v[:N].cpu().numpy() for k, v in out.items()}
+
+
+def test_cells_packed_from_a_nonzero_base(ops):
+    """cell_off[0] = 7: the first 7 rows of pts belong to nobody (NaN) and all three kernels index from the first cell on.  The
+    matrices and the four graph arrays are those of the same cells run from 0, bit for bit."""
+    rng = np.random.default_rng(7)
+    sizes = [3, 65, 257]
+    pts = np.concatenate([quantised(rng, n) for n in sizes])
+    shifted = torch.from_numpy(np.concatenate([np.full((7, 2), np.nan), pts])).to(DEV)
+    d7, g7 = raw_cells(ops, shifted, offsets(sizes) + 7, 3)
+    d0, g0 = raw_cells(ops, torch.from_numpy(pts).to(DEV), offsets(sizes), 3)
+    assert not np.isnan(d7).any() and np.array_equal(d7, d0)
+    for name in NAMES:
+        assert np.array_equal(g7[name], g0[name]), name
+    check_cells(g7, d7, offsets(sizes), offsets(np.square(sizes)), 3, "base 7")
+
+
+def test_haversine_blocks_with_empty_cells(ops):
+    """cells of 0, 3, 0, 0, 65 and 0 points: the rows are found across the empty cells, mat_off repeats where a cell is empty"""
+    rng = np.random.default_rng(65)
+    pts = torch.from_numpy(np.concatenate([quantised(rng, n) for n in (3, 65)])).to(DEV)
+    sizes = [0, 3, 0, 0, 65, 0]
+    dist, mat_off = ops.haversine_blocks(pts, offsets(sizes))
+    want, want_off = ops.haversine_blocks(pts, offsets([3, 65]))
+    torch.cuda.synchronize()
+    assert mat_off.tolist() == [0, 0, 9, 9, 9, 9 + 65 * 65, 9 + 65 * 65] and want_off.tolist() == [0, 9, 9 + 65 * 65]
+    assert dist.numel() == 9 + 65 * 65 and torch.equal(dist, want)
+    np.testing.assert_allclose(dist[9:].reshape(65, 65).cpu().numpy(), ref.cell_distances(pts[3:].cpu().numpy()), rtol=1e-12, atol=1e-9)
+
+
+def test_graph_global_form_1024_threads(ops):
+    """pg_tune_optics_lds_points(64) with cells of 1025 and 300 points: the 1024-thread and the 256-thread ordering kernel with their
+    state in global memory, the same bits as the LDS form and as the restatement"""
+    rng = np.random.default_rng(1025)
+    sizes = [1025, 300]
+    pts = np.concatenate([quantised(rng, n) for n in sizes])
+    cell_off = offsets(sizes)
+    dist, mat_off = ops.haversine_blocks(torch.from_numpy(pts).to(DEV), cell_off)
+    lds = run_graph(ops, dist, cell_off, mat_off, 3)
+    assert [(ops.optics_plan(n, 3)["form"], ops.optics_plan(n, 3)["threads"]) for n in sizes] == [(0, 1024), (0, 256)]
+    try:
+        ops.tune_optics_lds_points(64)
+        assert [(ops.optics_plan(n, 3)["form"], ops.optics_plan(n, 3)["threads"]) for n in sizes] == [(1, 1024), (1, 256)]
+        glob = run_graph(ops, dist, cell_off, mat_off, 3)
+    finally:
+        ops.tune_optics_lds_points(0)
+    for name in NAMES:
+        assert np.array_equal(lds[name], glob[name]), name
+    check_cells(glob, dist.cpu().numpy(), cell_off, mat_off, 3, "form 1, 1024 threads")
+
+
+def test_graph_global_form_by_size(ops):
+    """under the default knobs: one cell of pg_optics_plan's out[2] + 1 points -- the route every large geocell takes -- next to a
+    130-point cell"""
+    n = ops.optics_plan(2, 2)["lds_points"] + 1
+    plan = ops.optics_plan(n, 100)
+    assert plan["form"] == 1 and plan["threads"] == 1024 and n <= plan["max_points"]
+    rng = np.random.default_rng(8193)
+    sizes = [n, 130]
+    pts = np.concatenate([np.array([5.0, 50.0]) + rng.normal(0, 0.05, (m, 2)) for m in sizes])
+    cell_off = offsets(sizes)
+    dist, mat_off = ops.haversine_blocks(torch.from_numpy(pts).to(DEV), cell_off)
+    g = run_graph(ops, dist, cell_off, mat_off, 100)
+    check_cells(g, dist.cpu().numpy(), cell_off, mat_off, 100, "global form by size")
+
+
+def test_graph_on_a_side_stream(ops):
+    """both calls take torch's current stream and order their scratch on it: a side stream gives the default stream's bits"""
+    rng = np.random.default_rng(11)
+    sizes = [64, 65, 257, 1025]
+    pts = torch.from_numpy(np.concatenate([quantised(rng, n) for n in sizes])).to(DEV)
+    cell_off = offsets(sizes)
+    dist, mat_off = ops.haversine_blocks(pts, cell_off)
+    want = run_graph(ops, dist, cell_off, mat_off, 3)
+    torch.cuda.synchronize()
+    side = torch.cuda.Stream()
+    assert side.cuda_stream != torch.cuda.default_stream().cuda_stream
+    with torch.cuda.stream(side):
+        assert torch.cuda.current_stream().cuda_stream == side.cuda_stream
+        dist2, mat_off2 = ops.haversine_blocks(pts, cell_off)
+        got = run_graph(ops, dist2, cell_off, mat_off2, 3)
+    torch.cuda.synchronize()
+    assert torch.equal(mat_off, mat_off2) and torch.equal(dist, dist2)
+    for name in NAMES:
+        assert np.array_equal(got[name], want[name]), name
+
+
+def test_optics_graph_cells_batches(ops):
+    """prototypes.optics_graph_cells on interleaved rows with unsorted string labels, cells of 5, 40, 3, 130 and 70 rows at min_samples 4:
+    with the default memory budget (one batch) and with 8 * 70^2 bytes (four: the 130-row cell is over budget and goes alone) the
+    same arrays per cell; the 3-row cell is left out; `rows` are in row order; every cell's arrays are the restatement's on the cell's
+    own device matrix."""
+    from pigeon_amd import prototypes
+    rng = np.random.default_rng(4)
+    sizes = {"delta": 5, "alpha": 40, "echo": 3, "charlie": 130, "bravo": 70}
+    labels = rng.permutation(np.concatenate([[k] * n for k, n in sizes.items()]))
+    lnglat = quantised(rng, len(labels), side=12)
+    one = prototypes.optics_graph_cells(lnglat, labels, 4)
+    many = prototypes.optics_graph_cells(lnglat, labels, 4, memory_bytes=8 * 70 * 70)
+    assert sorted(one) == sorted(many) == ["alpha", "bravo", "charlie", "delta"]
+    for cell, n in sizes.items():
+        if cell == "echo":
+            continue
+        rows = np.flatnonzero(labels == cell)
+        assert len(rows) == n and np.array_equal(one[cell]["rows"], rows) and np.array_equal(many[cell]["rows"], rows)
+        D, _ = ops.haversine_blocks(torch.from_numpy(lnglat[rows]).to(DEV), offsets([n]), prototypes.ZERO_AS)
+        want = ref.graph(D.cpu().numpy().reshape(n, n), 4)
+        for name, w in zip(NAMES, want):
+            assert one[cell][name].dtype == w.dtype and np.array_equal(one[cell][name], w), (cell, name)
+            assert np.array_equal(many[cell][name], w), (cell, name, "small budget")
 
 
 def test_wrapper_refusals(ops):
