@@ -14,6 +14,8 @@ import numpy as np
 import pytest
 import torch
 
+from _decisionref import _head_tol_restated, _refine_tol_restated, _tol  # noqa: F401  (the restatements live there now)
+
 pytestmark = pytest.mark.gpu
 
 DEV = "cuda"
@@ -93,32 +95,6 @@ def test_refine_forward_ex_records(env):
                 assert t1 == -1 and t2 == -1 and r[7] == -1 and r[8] == -1
 
 
-def _tol(m, g, beta, en):
-    g2 = float(g @ g)
-    if not np.isfinite(m) and m > 0:
-        return np.inf
-    if g2 == 0:
-        return np.inf
-    return (m - en * float(g @ beta)) / (en * np.sqrt(g2) / 32.0)
-
-
-def _head_tol_restated(logits, e, W, idx, beta, wmax, wbmax):
-    C = W.shape[0]
-    en = np.linalg.norm(e)
-    c0 = idx[0]
-    best, code = np.inf, 0
-    for j in range(1, len(idx)):
-        t = _tol(logits[c0] - logits[idx[j]], W[c0] - W[idx[j]], beta, en)
-        if t < best:
-            best, code = t, j
-    if len(idx) < C:
-        gmax = np.linalg.norm(W[c0]) + wmax
-        t = (logits[c0] - logits[idx[-1]] - en * (float(W[c0] @ beta) + wbmax)) / (en * gmax / 32.0)
-        if t < best:
-            best, code = t, -1
-    return best, code
-
-
 @pytest.mark.parametrize("with_drift", [False, True])
 def test_head_certainty_vs_restatement(env, with_drift):
     ops, syn = env["ops"], env["syn"]
@@ -188,70 +164,6 @@ def test_head_tolerance_means_what_it_says(env):
             assert (int(o2["preds_geocell"][i]) == int(o["preds_geocell"][i])) == same, (i, f)
         moved += 1
     assert moved >= 8
-
-
-def _refine_tol_restated(rec, ints, L, cand, topk, n_eval, C, W, bankp, bankt, e, beta, wmax, wbmax, T, r, ch, fin_r, cell_off=None,
-                         member_off=None, member_idx=None):
-    en = np.linalg.norm(e)
-    S = L + rec[:, 0] / T
-    if ints[r, 0] < 0 and all(ints[j, 0] < 0 for j in range(topk)):
-        return np.inf, 0                                         # a set of empty cells: nothing can change
-    if not (fin_r >= 1e-30) or ints[r, 0] < 0:
-        return 0.0, -9                                           # underflow, or an empty cell winning a set that is not all empty
-
-    def pair_s(a, j):
-        pa, pj = ints[a, 0], ints[j, 0]
-        da, dj = -rec[a, 0], -rec[j, 0]
-        ia = (1.0 / T) / da if (pa >= 0 and da > 0) else 0.0
-        ij = (1.0 / T) / dj if (pj >= 0 and dj > 0) else 0.0
-        g = W[cand[a]] - W[cand[j]] + (ia * bankp[pa] if pa >= 0 else 0) - (ij * bankp[pj] if pj >= 0 else 0) + (ij - ia) * e
-        return _tol(S[a] - S[j], g, beta, en)
-    best, code = np.inf, 0
-    for j in range(topk):
-        if j == r:
-            continue
-        t = pair_s(r, j)
-        if t < best:
-            best, code = t, 1000 + j
-    for j in range(topk, n_eval):
-        t_in = _tol(L[topk - 1] - L[j], W[cand[topk - 1]] - W[cand[j]], beta, en)
-        t = t_in if r == topk - 1 else max(t_in, pair_s(r, j))
-        if t < best:
-            best, code = t, 2000 + j
-    if n_eval > topk and n_eval < C:
-        gmax = np.linalg.norm(W[cand[topk - 1]]) + wmax
-        t = (L[topk - 1] - L[n_eval - 1] - en * (float(W[cand[topk - 1]] @ beta) + wbmax)) / (en * gmax / 32.0)
-        if t < best:
-            best, code = t, 2999
-    for which, x in enumerate((r, ch)):
-        if which == 1 and ch == r:
-            break
-        p1, t1 = ints[x, 0], ints[x, 2]
-        if p1 >= 0:                                              # nearest prototype against EVERY other prototype of the cell
-            lo, hi = cell_off[cand[x]], cell_off[cand[x] + 1]
-            w = e - bankp[p1]
-            dw = np.linalg.norm(w)
-            for j in range(lo, hi):
-                if j == p1:
-                    continue
-                l = e - bankp[j]
-                dl = np.linalg.norm(l)
-                t = _tol(dl - dw, l / dl - w / dw, beta, en)
-                if t < best:
-                    best, code = t, 3000 + which
-        if t1 >= 0 and p1 >= 0:                                  # farthest member against every other member of the cluster
-            w = e - bankt[t1]
-            dw = np.linalg.norm(w)
-            for jj in range(member_off[p1], member_off[p1 + 1]):
-                j = member_idx[jj]
-                if j == t1:
-                    continue
-                l = e - bankt[j]
-                dl = np.linalg.norm(l)
-                t = _tol(dw - dl, w / dw - l / dl, beta, en)
-                if t < best:
-                    best, code = t, 4000 + which
-    return best, code
 
 
 @pytest.mark.parametrize("topk,k,T,max_km,with_drift", [(5, 9, 1.6, 1000.0, False), (5, 9, 1.6, 1000.0, True), (8, 8, 0.6, 1e5, False),
