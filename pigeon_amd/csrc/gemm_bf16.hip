@@ -46,7 +46,7 @@ __device__ __forceinline__ void tile_coords(const GemmArgs& g, int& tm, int& tn)
 template <typename T, int EPI, int TM, int TN, int WTM, int WTN>
 __device__ __forceinline__ void staged_epilogue(f32x16 (&acc)[TM][TN], const GemmArgs& g, char* smem, int wave, int lane,
                                                 int row0 /* first row of this wave's tile */, int col0) {
-    constexpr bool OUT16 = (EPI == EPI_QKV || EPI == EPI_GELU);
+    constexpr bool OUT16 = epi_is_out16(EPI);                // (this kernel has no LayerNorm-fold epilogues)
     constexpr int ROWPF = WTN + 4;                           // padded slab row, floats (272 B for WTN=64)
     const int lrow = lane & 31, lhalf = lane >> 5;
     float* slab = (float*)(smem + wave * (32 * ROWPF * 4));
@@ -210,17 +210,6 @@ __global__ __launch_bounds__(OT_WM * OT_WN * 64) void gemm_bf16_kernel(GemmArgs 
     staged_epilogue<T, EPI, TM, TN, WTM, WTN>(acc, g, smem, wave, lane, m0 + wm * WTM, n0 + wn * WTN);
 }
 
-template <typename KFN>
-static int launch_kernel(KFN kfn, bool& attr_set, size_t lds, dim3 grid, dim3 block, const GemmArgs& g, hipStream_t s) {
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) { pg_set_error("gemm: set LDS attr (%zu B): %s", lds, hipGetErrorString(e)); return PG_EHIP; }
-        attr_set = true;
-    }
-    hipLaunchKernelGGL(kfn, grid, block, lds, s, g);
-    return pg_check_launch("gemm16");
-}
-
 template <typename T>
 static int launch_one_tile(const GemmArgs& g0, int epi, hipStream_t s) {
     GemmArgs g = g0;
@@ -229,9 +218,10 @@ static int launch_one_tile(const GemmArgs& g0, int epi, hipStream_t s) {
     g.tilesN = g.N / OT_BN;
     g.ntiles = g.tilesM * g.tilesN;
     g.gn = g.tilesN;                                          // N-fastest raster
-    const size_t lds = 2 * (size_t)(OT_BM + OT_BN) * ROWB;
+    constexpr size_t lds = 2 * (size_t)(OT_BM + OT_BN) * ROWB;
+    static_assert(lds == 131072, "the error text below names the size");
     dim3 grid(g.ntiles), block(OT_WM * OT_WN * 64);
-#define PG_LAUNCH(E) { static bool a = false; return launch_kernel(gemm_bf16_kernel<T, E>, a, lds, grid, block, g, s); }
+#define PG_LAUNCH(E) { static bool a = false; return launch_kernel(gemm_bf16_kernel<T, E>, a, lds, grid, block, g, s, "gemm16", "gemm: set LDS attr (131072 B)"); }
     switch (epi) {
         case EPI_QKV: PG_LAUNCH(EPI_QKV)
         case EPI_GELU: PG_LAUNCH(EPI_GELU)

@@ -1,80 +1,8 @@
-// gemm_epi.h -- argument block and fused epilogue element functions shared by the GEMM kernels
-// (gemm_bf16.hip: one-tile-per-block kernels; gemm_pp.hip: persistent ping-pong kernel).
+// gemm_epi.h -- the fused epilogues of the GEMM kernels: the element arithmetic that all five kernel files share (gemm_bf16 /
+// gemm_pp / gemm_pp6 / gemm_tail / gemm_mid .hip) and the 32-row x 64-column slab epilogue of gemm_tail and gemm_mid.
+// The argument block and the device / host helpers around it: gemm_device.h.
 #pragma once
-#include "common.h"
-#include "pigeon_internal.h"
-
-#define BK 64
-#define ROWB 128   // bytes per LDS row (BK bf16)
-
-struct GemmArgs {
-    const uint16_t* A; int64_t lda;
-    const uint16_t* W; int64_t ldw;   // [N][K], row stride ldw elements
-    const float* bias;            // [N] or null
-    void* out; int64_t ldc;
-    int M, N, K;
-    float qscale; int qcols;
-    const float* aux;             // epi 3: position embedding [577][N]
-    int tilesM, tilesN, ntiles;
-    int part_tiles;               // tiles of ONE part (tilesM x tilesN); ntiles = ex.parts x part_tiles (EPI_F32, gemm_pp.hip)
-    int gn;                       // N tiles per raster group (see tile_coords)
-    int stagger;                  // gemm_pp: per-CU start stagger in shader cycles (0 = off; nothing sets it now); -7 arms PG_TS
-    int xcd_stagger_ticks;        // persistent kernels: XCD x starts x * ticks / 8 wall-clock ticks (100 MHz) late (0 = off)
-    PgGemmExtra ex;               // LayerNorm-fold epilogues (EPI_RESID_STAT / EPI_QKV_LN / EPI_GELU_LN)
-};
-
-// The kernels' launchers (gemm_plan.hip's pg_gemm_launch calls them); tilesM/tilesN/ntiles are filled in by the callee.
-// gemm_bf16.hip: the one-tile-per-block kernel (variant 8).  pg_gemm_one_tile_bn: its N tile for `variant`, 0 = not a one-tile
-// variant.
-int pg_gemm_one_tile_bn(int variant);
-int pg_gemm_one_tile_launch(int dtype, GemmArgs g, int epi, int variant, hipStream_t s);
-// gemm_pp.hip: persistent ping-pong kernel (variants 33, 36)
-int pg_gemm_pp_launch(int dtype, GemmArgs g, int epi, int variant, hipStream_t s);
-// gemm_pp6.hip: the same kernel with a 384 x 256 block tile, 16-bit-output epilogues and EPI_RESID_STAT (variant 56)
-bool pg_gemm_pp6_supported(int epi, int N, int K);
-int pg_gemm_pp6_launch(int dtype, GemmArgs g, int epi, hipStream_t s);
-
-// XCD-level start stagger of the persistent GEMMs.  Every tile of a launch takes the same time, so blocks that start
-// together reach their epilogues together: all 256 CUs then hit HBM at once (the fp32 residual read-modify-write of an
-// out-proj / fc2 tile is 640 KB per CU, 164 MB per round) while the matrix pipes idle, and during the mainloops HBM idles.
-// Delaying XCD x by x/8 of a tile period keeps the 32 CUs of an XCD in lock step -- they share operand panels through
-// their L2 at the same K position, which the per-CU stagger tried in round 1 destroyed -- but lets one XCD's epilogue run
-// under the other XCDs' mainloops.  The launch ends with the partial last round anyway (its few tiles go to XCD 0, which is
-// not delayed), so a spread below one tile period adds no tail.  Wall clock (100 MHz s_memrealtime), immune to DVFS.
-__device__ __forceinline__ void xcd_stagger_wait(int ticks) {
-    if (ticks <= 0) return;
-    const int xcd = blockIdx.x & 7;
-    if (xcd == 0) return;
-    const unsigned long long until = __builtin_amdgcn_s_memrealtime() + (unsigned long long)ticks * xcd / 8;
-    while (__builtin_amdgcn_s_memrealtime() < until) __builtin_amdgcn_s_sleep(16);
-}
-
-// gemm_tail.hip: rows [m_begin, M) of a problem in 32 x 64 one-wave tiles, bit-identical to the persistent kernels (variant 70
-// runs a whole problem through it; pg_gemm_launch uses it for the rows that do not fill the persistent kernels' last round)
-bool pg_gemm_tail_supported(int epi, int N, int K);
-int pg_gemm_tail_launch(int dtype, GemmArgs g, int epi, int m_begin, hipStream_t s);
-// gemm_mid.hip (round 6): a whole problem in 128 x 128 one-tile-per-block tiles through a 3-stage LDS ring, bit-identical to the
-// persistent kernels (variant 71 forces it; pg_gemm_launch picks it for batches too small to fill the persistent kernels' first round)
-bool pg_gemm_mid_supported(int epi, int N, int K);
-int pg_gemm_mid_launch(int dtype, GemmArgs g, int epi, hipStream_t s, int m_begin = 0);
-
-// Probe build only (-DPIGEON_PROBES): wall-clock stamps (100 MHz) from inside the persistent kernels, blocks 0 and 100, every wave, first 16 tiles:
-// buf[((blk * 16 + tile) * 8 + wave) * 12 + slot].  Armed by pg_dbg_timestamps(buf) (gemm_plan.hip), read by tools/epi_timeline.py.
-#ifdef PIGEON_PROBES
-#define PG_TS(g, iter, wave, slot)                                                                                             \
-    do {                                                                                                                       \
-        if ((g).stagger == -7 && (blockIdx.x == 0 || blockIdx.x == 100) && (threadIdx.x & 63) == 0 && (iter) < 16)             \
-            ((unsigned long long*)(g).aux)[(((blockIdx.x ? 1 : 0) * 16 + (iter)) * 8 + (wave)) * 12 + (slot)] =                \
-                __builtin_amdgcn_s_memrealtime();                                                                              \
-    } while (0)
-#else
-#define PG_TS(g, iter, wave, slot) do {} while (0)
-#endif
-
-__device__ __forceinline__ void glds16(const void* gptr, void* lds_base_uniform) {
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)gptr,
-                                     (__attribute__((address_space(3))) void*)lds_base_uniform, 16, 0, 0);
-}
+#include "gemm_device.h"
 
 // QuickGELU x * sigmoid(1.702 x) (modeling_clip.py QuickGELUActivation) as mul, v_exp_f32 (2^x), add, v_rcp_f32, mul:
 // the IEEE division of the obvious form expands to ~10 VALU instructions and made the fc1 epilogue cost ~6 us per tile.
@@ -113,9 +41,6 @@ __device__ __forceinline__ f32x4 quick_gelu4(f32x4 v) {
 // expressions -- including the association order of the row statistics -- live here and nowhere else.  A lane holds 8 outputs of
 // one row as two f32x4 (`lo`, `hi`); which columns those are (8 consecutive, or 4k.. and 32+4k.. for EPI_RESID_STAT) is the
 // caller's geometry, the arithmetic does not depend on it.
-template <int EPI> constexpr bool epi_is_ln() { return EPI == EPI_QKV_LN || EPI == EPI_GELU_LN; }
-template <int EPI> constexpr bool epi_is_qkv() { return EPI == EPI_QKV || EPI == EPI_QKV_LN; }
-template <int EPI> constexpr bool epi_is_out16() { return EPI == EPI_QKV || EPI == EPI_GELU || EPI == EPI_QKV_LN || EPI == EPI_GELU_LN; }
 
 // 16-bit-output epilogues (EPI_QKV, EPI_GELU and their LayerNorm-fold forms): 8 accumulators -> 8 packed 16-bit outputs.
 //   plain: y = acc + b;   LN fold: y = rstd * acc - (mean rstd) * colsum + c   (c = beta.W^T + b, s = colsum)
@@ -126,13 +51,13 @@ template <int EPI> constexpr bool epi_is_out16() { return EPI == EPI_QKV || EPI 
 template <typename T, int EPI>
 __device__ __forceinline__ u32x4 epi16_finish(f32x4 lo, f32x4 hi, const f32x4& b_lo, const f32x4& b_hi, const f32x4& s_lo,
                                               const f32x4& s_hi, float rstd, float mrs, bool q_strip, float qsc) {
-    if constexpr (epi_is_ln<EPI>()) {
+    if constexpr (epi_is_ln(EPI)) {
         lo = ln_fold4(lo, rstd, mrs, s_lo, b_lo);
         hi = ln_fold4(hi, rstd, mrs, s_hi, b_hi);
     } else {
         lo += b_lo; hi += b_hi;
     }
-    if constexpr (epi_is_qkv<EPI>()) {
+    if constexpr (epi_is_qkv(EPI)) {
         if (q_strip) { lo *= qsc; hi *= qsc; }
     } else {
         lo = quick_gelu4(lo); hi = quick_gelu4(hi);
@@ -206,4 +131,83 @@ __device__ __forceinline__ void epi_store_bf16x8(const GemmArgs& g, int row, int
     pk[0] = pack16x2<T>(lo[0], lo[1]); pk[1] = pack16x2<T>(lo[2], lo[3]);
     pk[2] = pack16x2<T>(hi[0], hi[1]); pk[3] = pack16x2<T>(hi[2], hi[3]);
     *(u32x4*)((uint16_t*)g.out + (int64_t)row * g.ldc + col) = pk;
+}
+
+// ==== The 32-row x 64-column slab epilogue of the kernels that store through plain pointers (gemm_mid.hip: half of a wave's
+// 64 x 64; gemm_tail.hip: its whole tile).  The two 16-row accumulator blocks acc0, acc1 (a lane owns row lane & 15 of a 16 x 16 block
+// and the 4 consecutive columns 4 (lane >> 4) ..) go through the wave's private LDS slab into row-major pieces -- lane (rr, cc)
+// holds 8 columns of rows rr, rr + 8, rr + 16, rr + 24 of the slab, whose first element is (row0, col0) of the problem -- and the
+// fused epilogue runs on those: pp_epilogue's geometry (gemm_pp.hip) and the expressions above, so a row's bits do not depend on
+// the kernel that computed it.  Rows past M are skipped.  The caller fences (wave_lds_fence) before it writes the slab again.
+// gemm_mid calls this function.  gemm_tail.hip still carries the same statements in its kernel body, token for token: called from
+// there (the argument block is the kernel parameter itself) hipcc allocates the kernel's registers differently, and the A/B against
+// the previous build (profiles/r07/gemm_shared_epilogue_ab.txt) did not stay inside its margin.  A change here is a change there.
+constexpr int EPI_SLAB_ROWPF = 64 + 4;                       // slab row in floats (the persistent kernels' padding)
+template <typename T, int EPI>
+__device__ __forceinline__ void epi_slab32(const GemmArgs& g, float* slab, int lane, int row0, int col0, const f32x4 (&acc0)[4],
+                                           const f32x4 (&acc1)[4]) {
+    constexpr bool OUT16 = epi_is_out16(EPI);
+    constexpr bool LN = epi_is_ln(EPI);
+    constexpr bool STAT = (EPI == EPI_RESID_STAT);
+    constexpr bool RESID = epi_is_resid(EPI);
+    constexpr int ROWPF = EPI_SLAB_ROWPF;
+    const int l15 = lane & 15, lq = lane >> 4;
+#pragma unroll
+    for (int ib = 0; ib < 2; ++ib)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) *(f32x4*)(slab + (ib * 16 + l15) * ROWPF + j * 16 + 4 * lq) = (ib ? acc1 : acc0)[j];
+    wave_lds_fence();
+
+    // EPI_RESID_STAT uses pp_epilogue's split-halves geometry (columns 4k.. and 32 + 4k.. per lane), everything else 8 consecutive
+    constexpr int HOFF = STAT ? 32 : 4;
+    const int rr = lane >> 3, cc = STAT ? (lane & 7) * 4 : (lane & 7) * 8;
+    const int col = col0 + cc;
+    const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
+    f32x4 b_lo = zero4, b_hi = zero4, s_lo = zero4, s_hi = zero4;
+    if (g.bias) { b_lo = *(const f32x4*)(g.bias + col); b_hi = *(const f32x4*)(g.bias + col + HOFF); }
+    if constexpr (LN) { s_lo = *(const f32x4*)(g.ex.colsum + col); s_hi = *(const f32x4*)(g.ex.colsum + col + 4); }
+    const float qsc = (epi_is_qkv(EPI) && col < g.qcols) ? g.qscale : 1.f;
+
+#pragma unroll
+    for (int it = 0; it < 4; ++it) {
+        const int r = it * 8 + rr;
+        const int row = row0 + r;
+        if (row >= g.M) continue;
+        f32x4 lo = *(const f32x4*)(slab + r * ROWPF + cc);
+        f32x4 hi = *(const f32x4*)(slab + r * ROWPF + cc + HOFF);
+        if constexpr (OUT16) {
+            float rstd = 0.f, mrs = 0.f;
+            if constexpr (LN) {
+                const u32x2 rs = *(const u32x2*)(g.ex.rowstat + (int64_t)row * 2);
+                // (the asm moves: see epi16_finish -- hipcc SLP-packs the fmas and broadcasts the wrong half otherwise)
+                asm("v_mov_b32 %0, %1" : "=v"(rstd) : "v"(rs[0]));
+                asm("v_mov_b32 %0, %1" : "=v"(mrs) : "v"(rs[1]));
+            }
+            *(u32x4*)((uint16_t*)g.out + (int64_t)row * g.ldc + col) =
+                epi16_finish<T, EPI>(lo, hi, b_lo, b_hi, s_lo, s_hi, rstd, mrs, col0 < g.qcols, qsc);
+        } else if constexpr (RESID) {
+            float* p = (float*)g.out + (int64_t)row * g.ldc + col;
+            const f32x4 x = epi_resid4(*(const f32x4*)p, lo, b_lo);
+            const f32x4 y = epi_resid4(*(const f32x4*)(p + HOFF), hi, b_hi);
+            *(f32x4*)p = x;
+            *(f32x4*)(p + HOFF) = y;
+            if constexpr (STAT) {
+                uint16_t* p16 = (uint16_t*)g.ex.x16 + (int64_t)row * g.ldc + col;
+                *(u32x2*)p16 = epi_copy16x4<T>(x);
+                *(u32x2*)(p16 + HOFF) = epi_copy16x4<T>(y);
+                float s1, s2;
+                epi_stat8(x, y, s1, s2);
+                s1 = row8_sum(s1);
+                s2 = row8_sum(s2);
+                if ((lane & 7) == 0) {
+                    float* sp = g.ex.statpart + ((int64_t)(col0 / 64) * g.ex.stat_rows + row) * 2;
+                    sp[0] = s1; sp[1] = s2;
+                }
+            }
+        } else {                                             // EPI_F32
+            float* p = (float*)g.out + (int64_t)row * g.ldc + col;
+            *(f32x4*)p = lo + b_lo;
+            *(f32x4*)(p + 4) = hi + b_hi;
+        }
+    }
 }

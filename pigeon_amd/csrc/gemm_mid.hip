@@ -41,106 +41,15 @@ constexpr int MD_STAGE = (MD_BM + MD_BN) * ROWB;               // 32 KB
 constexpr int MD_W_OFF = MD_BM * ROWB;
 constexpr int MD_NDMA = (MD_BM + MD_BN) / 8 / 4;               // DMAs per wave per K tile (8 rows x 128 B each): 8
 constexpr int MD_LDS = MD_STAGES * MD_STAGE;                   // 96 KB: one block per CU
-constexpr int MD_ROWPF = 64 + 4;                               // slab row in floats (the persistent kernels' padding)
-constexpr int MD_SLAB_BYTES = 32 * MD_ROWPF * 4;               // 8704 B per wave, overlaying stage 0 after the mainloop
-
-typedef __attribute__((address_space(3))) void lds_void;
-
-__device__ __forceinline__ void md_dma16(__amdgpu_buffer_rsrc_t rsrc, char* lds_wave_uniform, int voff, int soff) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lds_void*)lds_wave_uniform, 16, voff, soff, 0, 0);
-}
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t md_rsrc(const void* base, uint32_t bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), (short)0, (int)bytes, 0x00020000);
-}
-
-// fragment reads as inline asm (gemm_pp6.hip lds_read_b128): written as C++ loads, hipcc may put `s_waitcnt vmcnt(0)` in front of an LDS
-// read while a direct-to-LDS DMA is in flight -- it assumes the two can alias -- and the ring's prefetch would be serialised
-template <int OFF, typename V>
-__device__ __forceinline__ void md_lds_read(V& dst, uint32_t addr) {
-    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(OFF));
-}
-
-template <int EPI> constexpr bool md_out16() { return EPI == EPI_QKV || EPI == EPI_GELU || EPI == EPI_QKV_LN || EPI == EPI_GELU_LN; }
-template <int EPI> constexpr bool md_ln() { return EPI == EPI_QKV_LN || EPI == EPI_GELU_LN; }
+constexpr int MD_SLAB_BYTES = 32 * EPI_SLAB_ROWPF * 4;         // 8704 B per wave, overlaying stage 0 after the mainloop
 
 // the eight DMAs of one K tile of this wave: groups w, w + 4, .. (8 rows each); groups 0 .. 15 are A rows, 16 .. 31 W rows
 __device__ __forceinline__ void md_issue(__amdgpu_buffer_rsrc_t ra, __amdgpu_buffer_rsrc_t rw, char* stage, int wave,
                                          const int (&voffA)[4], const int (&voffW)[4], int soff) {
 #pragma unroll
-    for (int d = 0; d < 4; ++d) md_dma16(ra, stage + (wave + 4 * d) * 8 * ROWB, voffA[d], soff);
+    for (int d = 0; d < 4; ++d) dma16(ra, stage + (wave + 4 * d) * 8 * ROWB, voffA[d], soff);
 #pragma unroll
-    for (int d = 0; d < 4; ++d) md_dma16(rw, stage + MD_W_OFF + (wave + 4 * d) * 8 * ROWB, voffW[d], soff);
-}
-
-// One 32-row x 64-column slab of a wave: accumulator blocks -> LDS -> row-major pieces -> fused epilogue.  This is gemm_tail.hip's
-// epilogue (which is pp_epilogue's): same geometry, same gemm_epi.h expressions.
-template <typename T, int EPI, int H>
-__device__ __forceinline__ void md_slab(const GemmArgs& g, float* slab, int lane, int row0, int col0, const f32x4 (&acc)[4][4]) {
-    constexpr bool OUT16 = md_out16<EPI>();
-    constexpr bool LN = md_ln<EPI>();
-    constexpr bool STAT = (EPI == EPI_RESID_STAT);
-    constexpr bool RESID = (EPI == EPI_RESID || EPI == EPI_RESID_STAT);
-    const int l15 = lane & 15, lq = lane >> 4;
-#pragma unroll
-    for (int ib = 0; ib < 2; ++ib)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) *(f32x4*)(slab + (ib * 16 + l15) * MD_ROWPF + j * 16 + 4 * lq) = acc[2 * H + ib][j];
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_wave_barrier();
-    constexpr int HOFF = STAT ? 32 : 4;
-    const int rr = lane >> 3, cc = STAT ? (lane & 7) * 4 : (lane & 7) * 8;
-    const int col = col0 + cc;
-    const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
-    f32x4 b_lo = zero4, b_hi = zero4, s_lo = zero4, s_hi = zero4;
-    if (g.bias) { b_lo = *(const f32x4*)(g.bias + col); b_hi = *(const f32x4*)(g.bias + col + HOFF); }
-    if constexpr (LN) { s_lo = *(const f32x4*)(g.ex.colsum + col); s_hi = *(const f32x4*)(g.ex.colsum + col + 4); }
-    const float qsc = ((EPI == EPI_QKV || EPI == EPI_QKV_LN) && col < g.qcols) ? g.qscale : 1.f;
-#pragma unroll
-    for (int it = 0; it < 4; ++it) {
-        const int r = it * 8 + rr;
-        const int row = row0 + r;
-        if (row >= g.M) continue;
-        f32x4 lo = *(const f32x4*)(slab + r * MD_ROWPF + cc);
-        f32x4 hi = *(const f32x4*)(slab + r * MD_ROWPF + cc + HOFF);
-        if constexpr (OUT16) {
-            float rstd = 0.f, mrs = 0.f;
-            if constexpr (LN) {
-                const u32x2 rs = *(const u32x2*)(g.ex.rowstat + (int64_t)row * 2);
-                // (the asm moves: see gemm_pp.hip -- hipcc SLP-packs the fmas and broadcasts the wrong half otherwise)
-                asm("v_mov_b32 %0, %1" : "=v"(rstd) : "v"(rs[0]));
-                asm("v_mov_b32 %0, %1" : "=v"(mrs) : "v"(rs[1]));
-            }
-            *(u32x4*)((uint16_t*)g.out + (int64_t)row * g.ldc + col) =
-                epi16_finish<T, EPI>(lo, hi, b_lo, b_hi, s_lo, s_hi, rstd, mrs, col0 < g.qcols, qsc);
-        } else if constexpr (RESID) {
-            float* p = (float*)g.out + (int64_t)row * g.ldc + col;
-            const f32x4 x = epi_resid4(*(const f32x4*)p, lo, b_lo);
-            const f32x4 y = epi_resid4(*(const f32x4*)(p + HOFF), hi, b_hi);
-            *(f32x4*)p = x;
-            *(f32x4*)(p + HOFF) = y;
-            if constexpr (STAT) {
-                uint16_t* p16 = (uint16_t*)g.ex.x16 + (int64_t)row * g.ldc + col;
-                *(u32x2*)p16 = epi_copy16x4<T>(x);
-                *(u32x2*)(p16 + HOFF) = epi_copy16x4<T>(y);
-                float s1, s2;
-                epi_stat8(x, y, s1, s2);
-                s1 = row8_sum(s1);
-                s2 = row8_sum(s2);
-                if ((lane & 7) == 0) {
-                    float* sp = g.ex.statpart + ((int64_t)(col0 / 64) * g.ex.stat_rows + row) * 2;
-                    sp[0] = s1; sp[1] = s2;
-                }
-            }
-        } else {                                             // EPI_F32
-            float* p = (float*)g.out + (int64_t)row * g.ldc + col;
-            *(f32x4*)p = lo + b_lo;
-            *(f32x4*)(p + 4) = hi + b_hi;
-        }
-    }
-    // the next slab of this wave overwrites the same LDS: its reads above have returned (their values were consumed) before any
-    // later write of this wave is issued -- LDS operations of one wave execute in order
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_wave_barrier();
+    for (int d = 0; d < 4; ++d) dma16(rw, stage + MD_W_OFF + (wave + 4 * d) * 8 * ROWB, voffW[d], soff);
 }
 
 template <typename T, int EPI>
@@ -157,8 +66,8 @@ __global__ __launch_bounds__(MD_THREADS) void gemm_mid_kernel(GemmArgs g) {
     else { tn = L / g.tilesM; tm = L - tn * g.tilesM; }
     const int m0 = tm * MD_BM, n0 = tn * MD_BN;
     const int rows = min(MD_BM, g.M - m0);
-    const __amdgpu_buffer_rsrc_t ra = md_rsrc(g.A + (int64_t)m0 * g.lda, (uint32_t)rows * (uint32_t)g.lda * 2u);
-    const __amdgpu_buffer_rsrc_t rw = md_rsrc(g.W + (int64_t)n0 * g.ldw, (uint32_t)MD_BN * (uint32_t)g.ldw * 2u);
+    const __amdgpu_buffer_rsrc_t ra = make_rsrc(g.A + (int64_t)m0 * g.lda, (uint32_t)rows * (uint32_t)g.lda * 2u);
+    const __amdgpu_buffer_rsrc_t rw = make_rsrc(g.W + (int64_t)n0 * g.ldw, (uint32_t)MD_BN * (uint32_t)g.ldw * 2u);
     // per-lane DMA offsets (bytes) inside the operand panels: row (wave + 4 d) * 8 + (lane >> 3), logical 16-byte chunk
     // (lane & 7) ^ ((row >> 1) & 7) -- the swizzle on the SOURCE address, the LDS image is lane-linear (gemm_pp.hip)
     int voffA[4], voffW[4];
@@ -186,9 +95,9 @@ __global__ __launch_bounds__(MD_THREADS) void gemm_mid_kernel(GemmArgs g) {
             const int stepA = 16 * (int)g.lda * 2, stepW = 16 * (int)g.ldw * 2;
             auto issue = [&](int t, char* stage) {
 #pragma unroll
-                for (int gr = 0; gr < 16; ++gr) md_dma16(ra, stage + gr * 8 * ROWB, pvA[gr & 1] + (gr >> 1) * stepA, t * BK * 2);
+                for (int gr = 0; gr < 16; ++gr) dma16(ra, stage + gr * 8 * ROWB, pvA[gr & 1] + (gr >> 1) * stepA, t * BK * 2);
 #pragma unroll
-                for (int gr = 0; gr < 16; ++gr) md_dma16(rw, stage + MD_W_OFF + gr * 8 * ROWB, pvW[gr & 1] + (gr >> 1) * stepW, t * BK * 2);
+                for (int gr = 0; gr < 16; ++gr) dma16(rw, stage + MD_W_OFF + gr * 8 * ROWB, pvW[gr & 1] + (gr >> 1) * stepW, t * BK * 2);
             };
             issue(0, smem);
             if (nt > 1) issue(1, smem + MD_STAGE);
@@ -248,12 +157,11 @@ __global__ __launch_bounds__(MD_THREADS) void gemm_mid_kernel(GemmArgs g) {
             const uint32_t xo = (uint32_t)(((ks * 4 + lq) ^ sw) << 4) + (uint32_t)cur;
             const uint32_t aa = a_base + xo, ab = b_base + xo;
             typename T::v8 a[4], b[4];
-            md_lds_read<0 * 16 * ROWB>(a[0], aa); md_lds_read<1 * 16 * ROWB>(a[1], aa);
-            md_lds_read<2 * 16 * ROWB>(a[2], aa); md_lds_read<3 * 16 * ROWB>(a[3], aa);
-            md_lds_read<0 * 16 * ROWB>(b[0], ab); md_lds_read<1 * 16 * ROWB>(b[1], ab);
-            md_lds_read<2 * 16 * ROWB>(b[2], ab); md_lds_read<3 * 16 * ROWB>(b[3], ab);
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            __builtin_amdgcn_sched_barrier(0);
+            lds_read_b128<0 * 16 * ROWB>(a[0], aa); lds_read_b128<1 * 16 * ROWB>(a[1], aa);
+            lds_read_b128<2 * 16 * ROWB>(a[2], aa); lds_read_b128<3 * 16 * ROWB>(a[3], aa);
+            lds_read_b128<0 * 16 * ROWB>(b[0], ab); lds_read_b128<1 * 16 * ROWB>(b[1], ab);
+            lds_read_b128<2 * 16 * ROWB>(b[2], ab); lds_read_b128<3 * 16 * ROWB>(b[3], ab);
+            wait_lgkm0();
             // swapped operands (weights first) as in every GEMM kernel of the library
 #pragma unroll
             for (int i = 0; i < 4; ++i)
@@ -271,21 +179,18 @@ __global__ __launch_bounds__(MD_THREADS) void gemm_mid_kernel(GemmArgs g) {
     }
     float* slab = (float*)(smem + wave * MD_SLAB_BYTES);
     const int row0 = m0 + wm * 64, col0 = n0 + wn * 64;
-    md_slab<T, EPI, 0>(g, slab, lane, row0, col0, acc);
-    md_slab<T, EPI, 1>(g, slab, lane, row0 + 32, col0, acc);
+    // The wave's 64 x 64 as two slabs.  A slab's reads have returned (their values were consumed) before any later write of this
+    // wave to the same LDS is issued -- LDS operations of one wave execute in order; the fence makes the compiler keep that order.
+    epi_slab32<T, EPI>(g, slab, lane, row0, col0, acc[0], acc[1]);
+    wave_lds_fence();
+    epi_slab32<T, EPI>(g, slab, lane, row0 + 32, col0, acc[2], acc[3]);
+    wave_lds_fence();
 }
 
 template <typename T, int EPI>
 int launch_mid(const GemmArgs& g, int nblk, hipStream_t s) {
     static bool attr_set = false;
-    auto kfn = gemm_mid_kernel<T, EPI>;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, MD_LDS);
-        if (e != hipSuccess) { pg_set_error("gemm_mid: set LDS attr: %s", hipGetErrorString(e)); return PG_EHIP; }
-        attr_set = true;
-    }
-    hipLaunchKernelGGL(kfn, dim3(nblk), dim3(MD_THREADS), MD_LDS, s, g);
-    return pg_check_launch("gemm_mid");
+    return launch_kernel(gemm_mid_kernel<T, EPI>, attr_set, MD_LDS, dim3(nblk), dim3(MD_THREADS), g, s, "gemm_mid", "gemm_mid: set LDS attr");
 }
 
 template <typename T>
@@ -316,19 +221,15 @@ int pg_gemm_mid_launch(int dtype, GemmArgs g, int epi, hipStream_t s, int m_begi
     if (m_begin < 0 || m_begin >= g.M) return m_begin == g.M ? PG_OK : (pg_set_error("gemm_mid: m_begin = %d outside [0, %d)", m_begin, g.M), PG_EINVAL);
     if (m_begin > 0) {
         // the kernel indexes every row-major buffer by the row number: move the bases instead of teaching it an offset
-        const bool out16 = epi == EPI_QKV || epi == EPI_GELU || epi == EPI_QKV_LN || epi == EPI_GELU_LN;
         if (g.ex.stat_rows <= 0) g.ex.stat_rows = g.M;       // the slices of statpart keep the stride of the WHOLE problem
         g.A += (int64_t)m_begin * g.lda;
-        g.out = (char*)g.out + (int64_t)m_begin * g.ldc * (out16 ? 2 : 4);
+        g.out = (char*)g.out + (int64_t)m_begin * g.ldc * (epi_is_out16(epi) ? 2 : 4);
         if (g.ex.rowstat) g.ex.rowstat += (int64_t)m_begin * 2;
         if (g.ex.x16) g.ex.x16 = (uint16_t*)g.ex.x16 + (int64_t)m_begin * g.ldc;
         if (g.ex.statpart) g.ex.statpart += (int64_t)m_begin * 2;
         g.M -= m_begin;
     }
-    if ((int64_t)g.lda * 2 * MD_BM >= (1ll << 31) || (int64_t)g.ldw * 2 * MD_BN >= (1ll << 31)) {
-        pg_set_error("gemm_mid: operand panel exceeds the 2 GB buffer-descriptor range");
-        return PG_EINVAL;
-    }
+    if (int rc = pg_gemm_panel_check("gemm_mid", g.lda, g.ldw, MD_BM, MD_BN)) return rc;
     g.tilesM = (g.M + MD_BM - 1) / MD_BM;
     g.tilesN = g.N / MD_BN;
     g.ntiles = g.tilesM * g.tilesN;

@@ -205,7 +205,7 @@ constexpr double ROUND_EPI_PP6_RESID = 14.0, ROUND_EPI_PP6 = 9.0;         // ...
 constexpr double ROUND_EPI_PP_RESID = 20.0, ROUND_EPI_PP = 8.0;
 constexpr double TAIL_MID_EPI_RESID = 6.0, TAIL_MID_EPI = 5.0, TAIL_MID_LAUNCH_US = 3.0;   // gemm_mid on the tail: epilogue per round, a launch
 
-// (3) XCD stagger (gemm_epi.h): total spread = fraction x estimated tile period.  Tile periods measured on MI355X (profiles/r02):
+// (3) XCD stagger (gemm_device.h): total spread = fraction x estimated tile period.  Tile periods measured on MI355X (profiles/r02):
 // 256 x 256 tiles 25 us + 1.63 us per 64-wide K tile (fp32 residual epilogues; 10 us otherwise), 384 x 256 tiles 8 us (+4 us with
 // the GELU) + 2.44 us per K tile.
 constexpr float STAGGER_PP6_EPI = 8.f, STAGGER_PP6_EPI_GELU = 12.f, STAGGER_PP6_US_KT = 2.44f;
@@ -411,7 +411,7 @@ int pg_gemm_launch(int dtype, const void* A, int64_t lda, const void* W, int64_t
     }
     if ((epi == EPI_GELU || epi == EPI_RESID || epi >= EPI_RESID_STAT) && !bias) { pg_set_error("gemm: epilogue %d needs a bias", epi); return PG_EINVAL; }
     if (epi == EPI_RESID_STAT && (!g.ex.x16 || !g.ex.statpart || g.ex.ldx != ldc)) { pg_set_error("gemm: EPI_RESID_STAT needs x16 / statpart and ldx == ldc"); return PG_EINVAL; }
-    if ((epi == EPI_QKV_LN || epi == EPI_GELU_LN) && (!g.ex.colsum || !g.ex.rowstat)) { pg_set_error("gemm: LN epilogue needs colsum / rowstat"); return PG_EINVAL; }
+    if (epi_is_ln(epi) && (!g.ex.colsum || !g.ex.rowstat)) { pg_set_error("gemm: LN epilogue needs colsum / rowstat"); return PG_EINVAL; }
     if (epi == EPI_PATCH && !aux) { pg_set_error("gemm: patch epilogue needs aux"); return PG_EINVAL; }
     if (epi == EPI_GELU_X3 && (ldc != 3 * (int64_t)N || dtype != PG_DTYPE_F16 || N % 256 != 0 || K % 128 != 0)) {
         pg_set_error("gemm: EPI_GELU_X3 writes the fp16 triple [M][3N]: ldc == 3 N, fp16 operands, N %% 256 == 0, K %% 128 == 0 (ldc=%lld N=%d K=%d)",

@@ -46,15 +46,6 @@ constexpr int PP_SLAB_ROWF = 64 + 4;                       // padded slab row, f
 constexpr int PP_SLAB_BYTES = 32 * PP_SLAB_ROWF * 4;       // 8704 B per wave
 constexpr int PP_LDS = 160 * 1024;
 
-typedef __attribute__((address_space(3))) void lds_void;
-
-__device__ __forceinline__ void dma16(__amdgpu_buffer_rsrc_t rsrc, char* lds_wave_uniform, int voff, int soff) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lds_void*)lds_wave_uniform, 16, voff, soff, 0, 0);
-}
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* base, uint32_t bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), (short)0, (int)bytes, 0x00020000);
-}
-
 struct TileCtx {
     __amdgpu_buffer_rsrc_t ra, rw;
     int m0, n0;
@@ -66,6 +57,8 @@ struct TileCtx {
 // is plain N-fastest order.  A persistent round gives every XCD 32 consecutive ids, i.e. one (32/gn) x gn super-tile:
 // the unique operand bytes an XCD's L2 must fetch per K step are (32/gn + gn) panels (12 for 8 x 4, against 14.7 /
 // 18 for N-fastest rows of 12 / 16 tiles).
+// (gemm_pp6.hip make_tile6 repeats the decode with its own tile constants: written as one shared function, in any form
+// tried, hipcc orders four scalar instructions per kernel differently, and these two files' assembly is not allowed to move.)
 template <bool PARTS = false>
 __device__ __forceinline__ TileCtx make_tile(const GemmArgs& g, int L) {
     TileCtx c;
@@ -137,20 +130,6 @@ __device__ __forceinline__ void mma16(AccPP& acc, const Frag<T>& f) {
         }
 }
 
-__device__ __forceinline__ void wait_lgkm0() {
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_sched_barrier(0);
-}
-__device__ __forceinline__ void wait_vm0() {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __builtin_amdgcn_sched_barrier(0);
-}
-__device__ __forceinline__ void raw_barrier() {
-    __builtin_amdgcn_sched_barrier(0);
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_sched_barrier(0);
-}
-
 // EPI_RESID: addressing of the fp32 residual rows this lane adds into (store side: 16 lanes per row, 4 rows per
 // instruction, 8 instructions per 32-row slab).  The rows of slabs 0 and 1 are fetched during the SECOND-TO-LAST K tile of
 // the mainloop (their 64 registers are idle there), slabs 2 and 3 as soon as the epilogue has parked the accumulators of
@@ -164,8 +143,7 @@ struct XCtx {
 template <bool WIDE = false>
 __device__ __forceinline__ XCtx make_xctx(const GemmArgs& g, int row0, int col0, int lane) {
     XCtx x;
-    int rv = g.M - row0; rv = rv < 0 ? 0 : (rv > 128 ? 128 : rv);
-    rv = __builtin_amdgcn_readfirstlane(rv);   // descriptor stays in SGPRs (hipcc clamps with v_med3_i32, see gemm_pp6.hip rowstat_rsrc6)
+    const int rv = wave_valid_rows(g.M - row0, 128);
     const uint32_t nbytes = rv > 0 ? (uint32_t)(((int64_t)(rv - 1) * g.ldc + 64) * 4) : 0u;
     x.ro = make_rsrc((const char*)g.out + ((int64_t)row0 * g.ldc + col0) * 4, nbytes);
     if (WIDE) {                                              // EPI_RESID_STAT: split-halves geometry, see pp_epilogue
@@ -240,19 +218,13 @@ __device__ __forceinline__ void ktile_pp(AccPP& acc, const char* cur, char* nxt,
 // ---- epilogue: per wave, four 32-row x 64-column fp32 slabs transposed through LDS -------------------------------
 // A lane owns row m = lane&31 of the wave's 32x32 MFMA blocks; the slab turns that into row-major 16-byte pieces so a
 // wave-wide store covers whole 128-byte (16-bit out) / 256-byte (fp32 out) row segments.  The slab is private to the
-// wave, so only wave-level ordering is needed between its ds_writes and ds_reads (no block barrier).
-__device__ __forceinline__ void wave_lds_fence() {
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_wave_barrier();
-}
+// wave, so only wave-level ordering is needed between its ds_writes and ds_reads (wave_lds_fence, no block barrier).
 
 // Bias of the lane's row-major columns, fetched at the START of an output tile (before the K loop) and forced to
 // retire there: a global_load that is still "pending" in the compiler's scoreboard when the epilogue runs would make
 // it insert vmcnt(0) in front of every use -- which also drains the epilogue's own stores and the next tile's DMA.
-template <int EPI> constexpr bool epi_out16() { return EPI == EPI_QKV || EPI == EPI_GELU || EPI == EPI_QKV_LN || EPI == EPI_GELU_LN; }
-template <int EPI> constexpr bool epi_ln() { return EPI == EPI_QKV_LN || EPI == EPI_GELU_LN; }
 // 8 columns per lane on the store side (16-bit outputs, and the fp32 residual epilogue that also emits the 16-bit copy)
-template <int EPI> constexpr bool epi_wide() { return epi_out16<EPI>() || EPI == EPI_RESID_STAT; }
+template <int EPI> constexpr bool epi_wide() { return epi_is_out16(EPI) || EPI == EPI_RESID_STAT; }
 
 // Per-tile epilogue operands fetched at the START of the tile (or, for the next tile, before the current epilogue's
 // stores): bias (lo/hi), for the LN epilogues colsum (slo/shi) and (rstd, mean*rstd) of the 16 rows this lane will store.
@@ -266,7 +238,7 @@ __device__ __forceinline__ void load_bias(EpiBias<EPI>& b, const GemmArgs& g, in
         b.lo = *(const f32x4*)(g.bias + col);
         if (epi_wide<EPI>()) b.hi = *(const f32x4*)(g.bias + col + (EPI == EPI_RESID_STAT ? 32 : 4));
     }
-    if constexpr (epi_ln<EPI>()) {
+    if constexpr (epi_is_ln(EPI)) {
         b.slo = *(const f32x4*)(g.ex.colsum + col);
         b.shi = *(const f32x4*)(g.ex.colsum + col + 4);
     }
@@ -279,8 +251,7 @@ __device__ __forceinline__ void zero_bias(EpiBias<EPI>& b) {
 // (rstd, mean*rstd) of the 16 rows this lane stores: issued right after the tile's first wait, lands under the K loop
 template <int EPI>
 __device__ __forceinline__ void load_rowstat(u32x2 (&rs)[4][4], const GemmArgs& g, int row0, int rr) {
-    int rvs = g.M - row0; rvs = rvs < 0 ? 0 : (rvs > 128 ? 128 : rvs);
-    rvs = __builtin_amdgcn_readfirstlane(rvs);   // descriptor stays in SGPRs (hipcc clamps with v_med3_i32, see gemm_pp6.hip rowstat_rsrc6)
+    const int rvs = wave_valid_rows(g.M - row0, 128);
     __amdgpu_buffer_rsrc_t rr_s = make_rsrc((const char*)g.ex.rowstat + (int64_t)row0 * 8, (uint32_t)rvs * 8u);
 #pragma unroll
     for (int i = 0; i < 4; ++i)
@@ -291,7 +262,7 @@ __device__ __forceinline__ void load_rowstat(u32x2 (&rs)[4][4], const GemmArgs& 
 template <int EPI>
 __device__ __forceinline__ void pin_bias(EpiBias<EPI>& b) {
     // a use: the compiler's wait for the loads lands here
-    if constexpr (epi_ln<EPI>()) asm volatile("" : "+v"(b.lo), "+v"(b.hi), "+v"(b.slo), "+v"(b.shi));
+    if constexpr (epi_is_ln(EPI)) asm volatile("" : "+v"(b.lo), "+v"(b.hi), "+v"(b.slo), "+v"(b.shi));
     else if constexpr (epi_wide<EPI>()) asm volatile("" : "+v"(b.lo), "+v"(b.hi));
     else asm volatile("" : "+v"(b.lo));
 }
@@ -304,10 +275,10 @@ template <typename T, int EPI, int XEARLY, typename PREFETCH>
 __device__ __forceinline__ void pp_epilogue(AccPP& acc, const GemmArgs& g, char* smem, int wave, int lane,
                                             int row0, int col0, const EpiBias<EPI>& bias, const u32x2 (&rs)[4][4],
                                             PREFETCH&& prefetch_next, const XCtx& xc, u32x4 (&xq)[4][8], int dbg_iter = 0) {
-    constexpr bool OUT16 = epi_out16<EPI>();
-    constexpr bool LN = epi_ln<EPI>();
+    constexpr bool OUT16 = epi_is_out16(EPI);
+    constexpr bool LN = epi_is_ln(EPI);
     constexpr bool STAT = (EPI == EPI_RESID_STAT);
-    constexpr bool RESID = (EPI == EPI_RESID || EPI == EPI_RESID_STAT);
+    constexpr bool RESID = epi_is_resid(EPI);
     constexpr bool WIDE = epi_wide<EPI>();
     constexpr bool X3 = (EPI == EPI_GELU_X3);                // fp16 triple [M][3N]: 4 columns per lane like EPI_F32, three 8-byte stores
     constexpr int ROWPF = PP_SLAB_ROWF;
@@ -324,7 +295,7 @@ __device__ __forceinline__ void pp_epilogue(AccPP& acc, const GemmArgs& g, char*
     constexpr int HOFF = STAT ? 32 : 4;                      // column distance between the lane's two f32x4
     const int rr = lane / LPR, cc = STAT ? (lane & 7) * 4 : (lane % LPR) * CPL;
     const int col = col0 + cc;
-    const float qsc = (EPI == EPI_QKV || EPI == EPI_QKV_LN) && col < g.qcols ? g.qscale : 1.f;
+    const float qsc = epi_is_qkv(EPI) && col < g.qcols ? g.qscale : 1.f;
 
     if constexpr (EPI == EPI_PATCH) {
         prefetch_next();
@@ -350,8 +321,7 @@ __device__ __forceinline__ void pp_epilogue(AccPP& acc, const GemmArgs& g, char*
         // Output (and, for EPI_RESID*, residual input) through a buffer descriptor based at the wave's (row0, col0):
         // rows past M fail the bounds check (stores dropped, loads return 0), so there is no exec-mask branching and
         // no per-store 64-bit address arithmetic: voffset is one VGPR, the slab/iteration row offset is an SGPR.
-        int rv = g.M - row0; rv = rv < 0 ? 0 : (rv > 128 ? 128 : rv);
-        rv = __builtin_amdgcn_readfirstlane(rv);   // descriptor stays in SGPRs (hipcc clamps with v_med3_i32, see gemm_pp6.hip rowstat_rsrc6)
+        const int rv = wave_valid_rows(g.M - row0, 128);
         // (EPI_GELU_X3: a row's three pieces sit N fp16 elements apart -- the range reaches 2N past the lane's first piece)
         const uint32_t nbytes = rv > 0 ? (uint32_t)(((int64_t)(rv - 1) * g.ldc + 64 + (X3 ? 2 * g.N : 0)) * ESZ) : 0u;
         __amdgpu_buffer_rsrc_t ro = make_rsrc((const char*)g.out + ((int64_t)row0 * g.ldc + col0) * ESZ, nbytes);
@@ -526,7 +496,7 @@ __global__ __launch_bounds__(512) void gemm_pp_kernel(GemmArgs g) {
     // waves, so its count is not static: full drain.)
     // (EPI_RESID_STAT issues more; 16 is a safe lower bound.  The LN epilogues prefetch after slab 0: 12 stores follow.)
     // (EPI_GELU_X3 issues 96; vmcnt counts to 63)
-    constexpr int NST = (EPI == EPI_PATCH) ? 0 : (EPI == EPI_F32 ? 32 : (EPI == EPI_GELU_X3 ? 63 : (epi_ln<EPI>() ? 12 : 16)));
+    constexpr int NST = (EPI == EPI_PATCH) ? 0 : (EPI == EPI_F32 ? 32 : (EPI == EPI_GELU_X3 ? 63 : (epi_is_ln(EPI) ? 12 : 16)));
     bool first = true;
     int dbg_iter = 0;                                        // tile counter of the probe build's time stamps (dead code otherwise)
 
@@ -543,7 +513,7 @@ __global__ __launch_bounds__(512) void gemm_pp_kernel(GemmArgs g) {
         raw_barrier();                                       // B_0: K tile 0 visible, previous epilogue's slabs released
         PG_TS(g, dbg_iter, wave, 0);
         u32x2 rs[4][4];
-        if constexpr (epi_ln<EPI>()) load_rowstat<EPI>(rs, g, c.m0 + wm * 128, err);
+        if constexpr (epi_is_ln(EPI)) load_rowstat<EPI>(rs, g, c.m0 + wm * 128, err);
         constexpr int XEARLY = EPI == EPI_RESID ? 1 : (EPI == EPI_RESID_STAT ? 2 : 0);
         XCtx xc;
         u32x4 xq[4][8];
@@ -609,14 +579,7 @@ __global__ __launch_bounds__(512) void gemm_pp_kernel(GemmArgs g) {
 template <typename T, int EPI>
 int launch_pp(const GemmArgs& g, int nblk, hipStream_t s) {
     static bool attr_set = false;
-    auto kfn = gemm_pp_kernel<T, EPI>;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, PP_LDS);
-        if (e != hipSuccess) { pg_set_error("gemm_pp: set LDS attr: %s", hipGetErrorString(e)); return PG_EHIP; }
-        attr_set = true;
-    }
-    hipLaunchKernelGGL(kfn, dim3(nblk), dim3(512), PP_LDS, s, g);
-    return pg_check_launch("gemm_pp");
+    return launch_kernel(gemm_pp_kernel<T, EPI>, attr_set, PP_LDS, dim3(nblk), dim3(512), g, s, "gemm_pp", "gemm_pp: set LDS attr");
 }
 
 template <typename T>
@@ -654,10 +617,7 @@ int pg_gemm_pp_launch(int dtype, GemmArgs g, int epi, int variant, hipStream_t s
         pg_set_error("gemm_pp: N %% 256 or K %% 128 != 0 (N=%d K=%d)", g.N, g.K);
         return PG_EINVAL;
     }
-    if ((int64_t)g.lda * 2 * PP_BM >= (1ll << 31) || (int64_t)g.ldw * 2 * PP_BN >= (1ll << 31)) {
-        pg_set_error("gemm_pp: operand panel exceeds the 2 GB buffer-descriptor range");
-        return PG_EINVAL;
-    }
+    if (int rc = pg_gemm_panel_check("gemm_pp", g.lda, g.ldw, PP_BM, PP_BN)) return rc;
     g.tilesM = (g.M + PP_BM - 1) / PP_BM;
     g.tilesN = g.N / PP_BN;
     g.part_tiles = g.tilesM * g.tilesN;

@@ -31,39 +31,13 @@ constexpr int P6_LDS = 2 * P6_STAGE;                       // 160 KB
 constexpr int P6_NDMA = P6_TM + 4;                         // DMAs per wave per K tile (6 A + 4 W)
 static_assert(8 * P6_SLAB_BYTES <= P6_STAGE, "slabs must fit into stage 1");
 
-typedef __attribute__((address_space(3))) void lds_void;
-
-__device__ __forceinline__ void dma16(__amdgpu_buffer_rsrc_t rsrc, char* lds_wave_uniform, int voff, int soff) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lds_void*)lds_wave_uniform, 16, voff, soff, 0, 0);
-}
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* base, uint32_t bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), (short)0, (int)bytes, 0x00020000);
-}
-__device__ __forceinline__ void wait_lgkm0() {
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_sched_barrier(0);
-}
-__device__ __forceinline__ void wait_vm0() {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __builtin_amdgcn_sched_barrier(0);
-}
-__device__ __forceinline__ void raw_barrier() {
-    __builtin_amdgcn_sched_barrier(0);
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_sched_barrier(0);
-}
-__device__ __forceinline__ void wave_lds_fence() {
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_wave_barrier();
-}
-
 struct Tile6 {
     __amdgpu_buffer_rsrc_t ra, rw;
     int m0, n0;
     int sa, sw;                                              // bytes between two 64-row DMA groups of A / W
 };
 
-// same band / super-tile order as gemm_pp.hip make_tile (8 x 4 super-tiles per XCD round), in 384-row panels
+// same band / super-tile order as gemm_pp.hip make_tile (8 x 4 super-tiles per XCD round; why it is a copy: there), in 384-row panels
 __device__ __forceinline__ Tile6 make_tile6(const GemmArgs& g, int L) {
     Tile6 c;
     const int gmax = g.gn >= 32 ? 1 : 32 / g.gn;
@@ -106,13 +80,8 @@ constexpr int P6_RB = 2 * P6_TM;                           // 16-row accumulator
 typedef f32x4 Acc6[P6_RB][4];
 template <typename T> struct Frag6 { typename T::v8 a[P6_TM], b[4]; };
 
-// Fragment reads as inline asm from ONE address register per operand: written as C++ loads, hipcc precomputes and keeps
-// live an address VGPR per (stage, k-step, operand) -- 16 registers this kernel does not have (it spilled 73).  The
-// k-step's chunk is an XOR on the address (disjoint bits, see ktile6), the 16-row blocks are immediates (<= 10 KB).
-template <int OFF, typename V>
-__device__ __forceinline__ void lds_read_b128(V& dst, uint32_t addr) {
-    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(OFF));
-}
+// Fragment reads from ONE address register per operand (lds_read_b128, gemm_device.h): the k-step's chunk is an XOR on the address
+// (disjoint bits, see ktile6), the 16-row blocks are immediates (<= 10 KB).
 template <typename T, bool WITH_B>
 __device__ __forceinline__ void load_frag6(Frag6<T>& f, uint32_t aA, uint32_t aB) {
     lds_read_b128<0 * 16 * ROWB>(f.a[0], aA); lds_read_b128<1 * 16 * ROWB>(f.a[1], aA); lds_read_b128<2 * 16 * ROWB>(f.a[2], aA);
@@ -248,14 +217,8 @@ __device__ __forceinline__ void load_bias6(Bias6& b, const GemmArgs& g, int col)
 }
 __device__ __forceinline__ void pin_bias6(Bias6& b) { asm volatile("" : "+v"(b.lo), "+v"(b.hi)); }
 
-template <int EPI> constexpr bool ln6() { return EPI == EPI_QKV_LN || EPI == EPI_GELU_LN; }
-template <int EPI> constexpr bool qkv6() { return EPI == EPI_QKV || EPI == EPI_QKV_LN; }
-
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t rowstat_rsrc6(const GemmArgs& g, int row0) {
-    int rvs = g.M - row0; rvs = rvs < 0 ? 0 : (rvs > P6_TM * 32 ? P6_TM * 32 : rvs);
-    // wave-uniform, but hipcc clamps with v_med3_i32 (there is no scalar med3): the record count, and with it the whole
-    // descriptor, would sit in VGPRs and every statistics load of the epilogue would be wrapped in a waterfall loop
-    rvs = __builtin_amdgcn_readfirstlane(rvs);
+    const int rvs = wave_valid_rows(g.M - row0, P6_TM * 32);
     return make_rsrc((const char*)g.ex.rowstat + (int64_t)row0 * 8, (uint32_t)rvs * 8u);
 }
 
@@ -280,14 +243,13 @@ __device__ __forceinline__ void epilogue6_park16(Acc6& acc, const GemmArgs& g, c
                                                  const Bias6& b01, const Bias6& b23, const Bias6& s01, const Bias6& s23,
                                                  const RowStatP& rs0, __amdgpu_buffer_rsrc_t rrs,
                                                  PREFETCH_DMA&& prefetch_dma, PREFETCH_BIAS&& prefetch_bias, int dbg_iter = 0) {
-    constexpr bool LN = ln6<EPI>();
+    constexpr bool LN = epi_is_ln(EPI);
     const int l15 = lane & 15, lq = lane >> 4;
     char* slab = smem + P6_SLAB_OFF + wave * P6_SLAB_BYTES;
     const int rr = lane >> 3, c8 = lane & 7;
     const bool q_strip = col0 < g.qcols;                     // wave-uniform: qcols is a multiple of 64
-    const float qsc = (qkv6<EPI>() && q_strip) ? g.qscale : 1.f;
-    int rv = g.M - row0; rv = rv < 0 ? 0 : (rv > P6_TM * 32 ? P6_TM * 32 : rv);
-    rv = __builtin_amdgcn_readfirstlane(rv);
+    const float qsc = (epi_is_qkv(EPI) && q_strip) ? g.qscale : 1.f;
+    const int rv = wave_valid_rows(g.M - row0, P6_TM * 32);
     const uint32_t nbytes = rv > 0 ? (uint32_t)(((int64_t)(rv - 1) * g.ldc + 64) * 2) : 0u;
     __amdgpu_buffer_rsrc_t ro = make_rsrc((const char*)g.out + ((int64_t)row0 * g.ldc + col0) * 2, nbytes);
     const int voff = (rr * (int)g.ldc + c8 * 8) * 2;
@@ -305,7 +267,7 @@ __device__ __forceinline__ void epilogue6_park16(Acc6& acc, const GemmArgs& g, c
         for (int ib = 0; ib < 2; ++ib) {
             float rstd = 0.f, mrs = 0.f;
             // LN: each half through an asm move of its own (hipcc SLP-packs the fmas into v_pk_fma_f32 and drops the op_sel of the
-            // high half of the loaded pair: gemm_pp.hip)
+            // high half of the loaded pair: gemm_epi.h epi16_finish)
             if constexpr (LN) {
                 asm("v_mov_b32 %0, %1" : "=v"(rstd) : "v"(rs[i & 1].v[ib][0]));
                 asm("v_mov_b32 %0, %1" : "=v"(mrs) : "v"(rs[i & 1].v[ib][1]));
@@ -359,8 +321,7 @@ struct ResidCtx6 {
 };
 __device__ __forceinline__ ResidCtx6 make_resid6(const GemmArgs& g, int row0, int col0, int lane) {
     ResidCtx6 r;
-    int rv = g.M - row0; rv = rv < 0 ? 0 : (rv > P6_TM * 32 ? P6_TM * 32 : rv);
-    rv = __builtin_amdgcn_readfirstlane(rv);                 // descriptors stay in SGPRs (rowstat_rsrc6)
+    const int rv = wave_valid_rows(g.M - row0, P6_TM * 32);
     const uint32_t nel = rv > 0 ? (uint32_t)((int64_t)(rv - 1) * g.ldc + 64) : 0u;
     r.ro = make_rsrc((const char*)g.out + ((int64_t)row0 * g.ldc + col0) * 4, nel * 4u);
     r.rx16 = make_rsrc((const char*)g.ex.x16 + ((int64_t)row0 * g.ldc + col0) * 2, nel * 2u);
@@ -498,7 +459,7 @@ __global__ __launch_bounds__(512) void gemm_pp6_kernel(GemmArgs g) {
         RowStatP rsp;
         __amdgpu_buffer_rsrc_t rrs = c.ra;                   // placeholder for the plain epilogues (never dereferenced)
         if constexpr (!RSTAT) load_bias6<16>(b23, g, col0 + 32 + ecc);
-        if constexpr (ln6<EPI>()) {
+        if constexpr (epi_is_ln(EPI)) {
             cs.lo = *(const f32x4*)(g.ex.colsum + col0 + ecc);
             cs.hi = *(const f32x4*)(g.ex.colsum + col0 + ecc + BHOFF);
             rrs = rowstat_rsrc6(g, row0);
@@ -540,30 +501,20 @@ __global__ __launch_bounds__(512) void gemm_pp6_kernel(GemmArgs g) {
 template <typename T, int EPI>
 int launch_pp6(const GemmArgs& g, int nblk, hipStream_t s) {
     static bool attr_set = false;
-    auto kfn = gemm_pp6_kernel<T, EPI>;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, P6_LDS);
-        if (e != hipSuccess) { pg_set_error("gemm_pp6: set LDS attr: %s", hipGetErrorString(e)); return PG_EHIP; }
-        attr_set = true;
-    }
-    hipLaunchKernelGGL(kfn, dim3(nblk), dim3(512), P6_LDS, s, g);
-    return pg_check_launch("gemm_pp6");
+    return launch_kernel(gemm_pp6_kernel<T, EPI>, attr_set, P6_LDS, dim3(nblk), dim3(512), g, s, "gemm_pp6", "gemm_pp6: set LDS attr");
 }
 
 }  // namespace
 
 // true if this (epilogue, shape) has a 384 x 256 kernel
 bool pg_gemm_pp6_supported(int epi, int N, int K) {
-    return (epi == EPI_QKV || epi == EPI_GELU || epi == EPI_QKV_LN || epi == EPI_GELU_LN || epi == EPI_RESID_STAT) && N % P6_BN == 0 &&
+    return (epi_is_out16(epi) || epi == EPI_RESID_STAT) && N % P6_BN == 0 &&
            K % (2 * BK) == 0 && K >= 4 * BK;
 }
 
 int pg_gemm_pp6_launch(int dtype, GemmArgs g, int epi, hipStream_t s) {
     if (!pg_gemm_pp6_supported(epi, g.N, g.K)) { pg_set_error("gemm_pp6: unsupported epilogue / shape (epi=%d N=%d K=%d)", epi, g.N, g.K); return PG_EINVAL; }
-    if ((int64_t)g.lda * 2 * P6_BM >= (1ll << 31) || (int64_t)g.ldw * 2 * P6_BN >= (1ll << 31)) {
-        pg_set_error("gemm_pp6: operand panel exceeds the 2 GB buffer-descriptor range");
-        return PG_EINVAL;
-    }
+    if (int rc = pg_gemm_panel_check("gemm_pp6", g.lda, g.ldw, P6_BM, P6_BN)) return rc;
     g.tilesM = (g.M + P6_BM - 1) / P6_BM;
     g.tilesN = g.N / P6_BN;
     g.ntiles = g.tilesM * g.tilesN;
@@ -578,7 +529,7 @@ int pg_gemm_pp6_launch(int dtype, GemmArgs g, int epi, hipStream_t s) {
     }
     const int cap = pg_gemm_grid_cus();
     const int nblk = g.ntiles < cap ? g.ntiles : cap;
-    if ((epi == EPI_QKV_LN || epi == EPI_GELU_LN) && (!g.ex.colsum || !g.ex.rowstat)) { pg_set_error("gemm_pp6: LN epilogue needs colsum / rowstat"); return PG_EINVAL; }
+    if (epi_is_ln(epi) && (!g.ex.colsum || !g.ex.rowstat)) { pg_set_error("gemm_pp6: LN epilogue needs colsum / rowstat"); return PG_EINVAL; }
     if (epi == EPI_RESID_STAT && (!g.ex.x16 || !g.ex.statpart || g.ex.ldx != g.ldc || !g.bias)) { pg_set_error("gemm_pp6: EPI_RESID_STAT needs bias, x16 / statpart and ldx == ldc"); return PG_EINVAL; }
 #define P6_DISPATCH(TT)                                                          \
     switch (epi) {                                                               \

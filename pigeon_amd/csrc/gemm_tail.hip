@@ -22,11 +22,6 @@ namespace {
 
 constexpr int TL_BM = 32, TL_BN = 64;
 constexpr int TL_DEPTH = 8;                                  // k-steps (of 32) in flight per wave: 6 x 16 bytes per lane each (48 KB per wave)
-constexpr int TL_ROWPF = 64 + 4;                             // slab row in floats (same padding as the persistent kernels)
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t tl_rsrc(const void* base, uint32_t bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), (short)0, (int)bytes, 0x00020000);
-}
 
 template <typename T> struct FragTL { typename T::v8 a[2], b[4]; };
 
@@ -41,16 +36,9 @@ __device__ __forceinline__ void load_frag_tl(FragTL<T>& f, __amdgpu_buffer_rsrc_
     for (int j = 0; j < 4; ++j) f.b[j] = __builtin_bit_cast(typename T::v8, __builtin_amdgcn_raw_buffer_load_b128(rw, vw[j], kbytes, 0));
 }
 
-template <int EPI> constexpr bool tl_out16() { return EPI == EPI_QKV || EPI == EPI_GELU || EPI == EPI_QKV_LN || EPI == EPI_GELU_LN; }
-template <int EPI> constexpr bool tl_ln() { return EPI == EPI_QKV_LN || EPI == EPI_GELU_LN; }
-
 template <typename T, int EPI>
 __global__ __launch_bounds__(64) void gemm_tail_kernel(GemmArgs g, int m_begin) {
-    __shared__ __attribute__((aligned(16))) float slab[TL_BM * TL_ROWPF];
-    constexpr bool OUT16 = tl_out16<EPI>();
-    constexpr bool LN = tl_ln<EPI>();
-    constexpr bool STAT = (EPI == EPI_RESID_STAT);
-    constexpr bool RESID = (EPI == EPI_RESID || EPI == EPI_RESID_STAT);
+    __shared__ __attribute__((aligned(16))) float slab[TL_BM * EPI_SLAB_ROWPF];
     const int lane = threadIdx.x;
     // Block b runs on XCD b % 8 (round-robin dispatch).  XCD x gets the column tiles tn = x (mod 8): its L2 then holds one
     // eighth of W (1 MB for fc2) instead of all of it -- with the plain (tm, tn) order every XCD pulled the whole weight
@@ -65,8 +53,8 @@ __global__ __launch_bounds__(64) void gemm_tail_kernel(GemmArgs g, int m_begin) 
     const int row0 = m_begin + tm * TL_BM, col0 = tn * TL_BN;
     const int l15 = lane & 15, lq = lane >> 4;
     const int rows = min(TL_BM, g.M - row0);
-    const __amdgpu_buffer_rsrc_t ra = tl_rsrc(g.A + (int64_t)row0 * g.lda, (uint32_t)rows * (uint32_t)g.lda * 2u);
-    const __amdgpu_buffer_rsrc_t rw = tl_rsrc(g.W + (int64_t)col0 * g.ldw, (uint32_t)TL_BN * (uint32_t)g.ldw * 2u);
+    const __amdgpu_buffer_rsrc_t ra = make_rsrc(g.A + (int64_t)row0 * g.lda, (uint32_t)rows * (uint32_t)g.lda * 2u);
+    const __amdgpu_buffer_rsrc_t rw = make_rsrc(g.W + (int64_t)col0 * g.ldw, (uint32_t)TL_BN * (uint32_t)g.ldw * 2u);
     int va[2], vw[4];
 #pragma unroll
     for (int i = 0; i < 2; ++i) va[i] = (i * 16 + l15) * (int)g.lda * 2 + lq * 16;
@@ -103,13 +91,17 @@ __global__ __launch_bounds__(64) void gemm_tail_kernel(GemmArgs g, int m_begin) 
         }
     }
 
-    // accumulators -> slab -> row-major pieces: lane (rr, cc) holds 8 consecutive columns of rows rr, rr + 8, rr + 16, rr + 24
+    // The tile is one slab: accumulators -> LDS -> row-major pieces -> fused epilogue.  These are the statements of gemm_epi.h
+    // epi_slab32 (which gemm_mid calls), kept here as a copy: see there.  A change here is a change there.
+    constexpr bool OUT16 = epi_is_out16(EPI);
+    constexpr bool LN = epi_is_ln(EPI);
+    constexpr bool STAT = (EPI == EPI_RESID_STAT);
+    constexpr bool RESID = epi_is_resid(EPI);
 #pragma unroll
     for (int ib = 0; ib < 2; ++ib)
 #pragma unroll
-        for (int j = 0; j < 4; ++j) *(f32x4*)(slab + (ib * 16 + l15) * TL_ROWPF + j * 16 + 4 * lq) = acc[ib][j];
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_wave_barrier();
+        for (int j = 0; j < 4; ++j) *(f32x4*)(slab + (ib * 16 + l15) * EPI_SLAB_ROWPF + j * 16 + 4 * lq) = acc[ib][j];
+    wave_lds_fence();
 
     // EPI_RESID_STAT uses pp_epilogue's split-halves geometry (columns 4k.. and 32 + 4k.. per lane), everything else 8 consecutive
     constexpr int HOFF = STAT ? 32 : 4;
@@ -119,20 +111,20 @@ __global__ __launch_bounds__(64) void gemm_tail_kernel(GemmArgs g, int m_begin) 
     f32x4 b_lo = zero4, b_hi = zero4, s_lo = zero4, s_hi = zero4;
     if (g.bias) { b_lo = *(const f32x4*)(g.bias + col); b_hi = *(const f32x4*)(g.bias + col + HOFF); }
     if constexpr (LN) { s_lo = *(const f32x4*)(g.ex.colsum + col); s_hi = *(const f32x4*)(g.ex.colsum + col + 4); }
-    const float qsc = ((EPI == EPI_QKV || EPI == EPI_QKV_LN) && col < g.qcols) ? g.qscale : 1.f;
+    const float qsc = (epi_is_qkv(EPI) && col < g.qcols) ? g.qscale : 1.f;
 
 #pragma unroll
     for (int it = 0; it < 4; ++it) {
         const int r = it * 8 + rr;
         const int row = row0 + r;
         if (row >= g.M) continue;
-        f32x4 lo = *(const f32x4*)(slab + r * TL_ROWPF + cc);
-        f32x4 hi = *(const f32x4*)(slab + r * TL_ROWPF + cc + HOFF);
+        f32x4 lo = *(const f32x4*)(slab + r * EPI_SLAB_ROWPF + cc);
+        f32x4 hi = *(const f32x4*)(slab + r * EPI_SLAB_ROWPF + cc + HOFF);
         if constexpr (OUT16) {
             float rstd = 0.f, mrs = 0.f;
             if constexpr (LN) {
                 const u32x2 rs = *(const u32x2*)(g.ex.rowstat + (int64_t)row * 2);
-                // (the asm moves: see gemm_pp.hip -- hipcc SLP-packs the fmas and broadcasts the wrong half otherwise)
+                // (the asm moves: see epi16_finish -- hipcc SLP-packs the fmas and broadcasts the wrong half otherwise)
                 asm("v_mov_b32 %0, %1" : "=v"(rstd) : "v"(rs[0]));
                 asm("v_mov_b32 %0, %1" : "=v"(mrs) : "v"(rs[1]));
             }
@@ -195,10 +187,7 @@ bool pg_gemm_tail_supported(int epi, int N, int K) {
 int pg_gemm_tail_launch(int dtype, GemmArgs g, int epi, int m_begin, hipStream_t s) {
     if (!pg_gemm_tail_supported(epi, g.N, g.K)) { pg_set_error("gemm_tail: unsupported epilogue / shape (epi=%d N=%d K=%d)", epi, g.N, g.K); return PG_EINVAL; }
     if (m_begin < 0 || m_begin >= g.M) return PG_OK;
-    if ((int64_t)g.lda * 2 * TL_BM >= (1ll << 31) || (int64_t)g.ldw * 2 * TL_BN >= (1ll << 31)) {
-        pg_set_error("gemm_tail: operand panel exceeds the 2 GB buffer-descriptor range");
-        return PG_EINVAL;
-    }
+    if (int rc = pg_gemm_panel_check("gemm_tail", g.lda, g.ldw, TL_BM, TL_BN)) return rc;
     g.tilesM = (g.M - m_begin + TL_BM - 1) / TL_BM;
     g.tilesN = g.N / TL_BN;
     g.ntiles = g.tilesM * g.tilesN;

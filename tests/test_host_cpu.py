@@ -589,3 +589,45 @@ def test_vit_precise_plan_host_properties():
     finally:
         L.pg_tune_gemm_mid(1); L.pg_tune_exact_fusion(1); L.pg_tune_exact_products(3)
     assert sweep() == first
+
+
+def test_build_headers_cover_every_include(tmp_path):
+    """pigeon_amd/build.py rebuilds an object when its source or ANY header of build.HEADERS is newer -- so every `#include "..."`
+    under csrc/ must resolve to a file of that list (a header outside it rebuilds nothing when it changes: x3.h once), and touching
+    x3.h must make the objects of its two includers stale.  The staleness rule is checked on copies with set mtimes; nothing is built."""
+    import re
+    import shutil
+    from pigeon_amd import build
+    root = os.path.dirname(build.HERE)
+    headers = {os.path.realpath(h) for h in build.HEADERS}
+    assert all(os.path.isfile(h) for h in headers)
+    assert os.path.realpath(os.path.join(build.CSRC, "x3.h")) in headers
+    files = [os.path.join(build.CSRC, f) for f in sorted(os.listdir(build.CSRC)) if f.endswith((".h", ".hip"))]
+    assert {os.path.basename(f) for f in files} >= set(build.SOURCES)
+    includers = {}
+    for f in files:
+        for inc in re.findall(r'^[ \t]*#[ \t]*include[ \t]*"([^"]+)"', open(f).read(), re.M):
+            target = os.path.realpath(os.path.join(os.path.dirname(f), inc))
+            assert target in headers, f"{os.path.basename(f)} includes {inc}: not in build.HEADERS"
+            includers.setdefault(os.path.basename(target), set()).add(os.path.basename(f))
+    assert {"gemm_pp.hip", "precise.hip"} <= includers["x3.h"]
+
+    def copy(path):
+        dst = os.path.join(tmp_path, os.path.relpath(path, root))
+        os.makedirs(os.path.dirname(dst), exist_ok=True)
+        shutil.copyfile(path, dst)
+        os.utime(dst, (1000, 1000))
+        return dst
+
+    hdrs = [copy(h) for h in build.HEADERS]
+    for src in ("gemm_pp.hip", "precise.hip"):
+        s = copy(os.path.join(build.CSRC, src))
+        obj = os.path.join(tmp_path, src.replace(".hip", ".o"))
+        assert build._stale(obj, [s] + hdrs)                       # no object yet
+        open(obj, "wb").close()
+        os.utime(obj, (2000, 2000))
+        assert not build._stale(obj, [s] + hdrs)
+    os.utime(os.path.join(tmp_path, os.path.relpath(os.path.join(build.CSRC, "x3.h"), root)), (3000, 3000))
+    for src in ("gemm_pp.hip", "precise.hip"):
+        s = os.path.join(tmp_path, os.path.relpath(os.path.join(build.CSRC, src), root))
+        assert build._stale(os.path.join(tmp_path, src.replace(".hip", ".o")), [s] + hdrs), src
