@@ -140,7 +140,7 @@ int pg_vit_mma_dtype(const pg_vit* h);
  * is a host value); allocates and frees a small scratch buffer.  Not for the hot path.
  * pg_vit_fingerprint: the digests of every parameter buffer pg_vit_forward reads (packed 16-bit weights, folded column sums and
  * biases, LayerNorm parameters, class and position embeddings), each with its byte size and a per-buffer seed, folded in a fixed
- * order (csrc/vit.hip) with the layer count, the MFMA operand dtype and whether LayerNorm is folded.  The exact tier's split-weight
+ * order (csrc/vit_weights.hip) with the layer count, the MFMA operand dtype and whether LayerNorm is folded.  The exact tier's split-weight
  * copy (cfg.precise) is not included: handles with and without it give the same value.  Two launches on the null stream, one
  * synchronous copy back (~0.6 GB read for ViT-L).  Any change of a weight that changes a stored bit changes the result. */
 int pg_fingerprint(const void* data, size_t bytes, uint64_t seed, uint64_t out[2], void* stream);
@@ -586,7 +586,7 @@ int pg_op_cast_f32(const float* x, void* y, int out_dtype, int64_t n, void* stre
  * or neither): also the 16-bit copy (x16_dtype) of the NEW row and its (rstd, mean*rstd), as pg_op_rowstat_cast would give. */
 int pg_op_preln(float* x, const float* cls, const float* pos0, const float* gamma, const float* beta, int64_t rows, float eps,
                 void* x16, int x16_dtype, float* rowstat, void* stream);
-/* S independent products in ONE persistent launch (the exact mode's K-split GEMMs, csrc/vit.hip precise_gemm): part p computes
+/* S independent products in ONE persistent launch (the exact mode's K-split GEMMs, csrc/vit_precise.hip precise_gemm): part p computes
  * parts[p] (M,N) fp32 = A[:, p*Kp:(p+1)*Kp] x W[:, p*Kp:(p+1)*Kp]^T (+ bias for p = 0); A (M, >= S*Kp) and W (N, >= S*Kp) 16-bit with
  * leading dimensions lda / ldw.  N % 256 == 0, Kp % 128 == 0, 1 <= S <= 8.  Each part is bit-identical to pg_op_gemm16_ld on its slice. */
 int pg_op_gemm16_parts(int dtype, const void* A, int64_t lda, const void* W, int64_t ldw, const float* bias, float* parts,

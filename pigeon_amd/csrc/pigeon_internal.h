@@ -36,7 +36,7 @@ int pg_default_gemm_variant();                   // env PIGEON_GEMM_VARIANT or t
 int pg_gemm_grid_cus();                         // the persistent GEMMs' grid: compute units of the device, capped by env PIGEON_GEMM_BLOCKS
 int pg_gemm_raster_gn();                       // pg_tune_gemm_raster / env PIGEON_GEMM_RASTER_GN: N tiles per raster group of the 384 x 256 kernel (0 = default 4, -1 = all)
 unsigned long long pg_tune_epoch();             // bumped by every pg_tune_gemm_* call: captured hipGraphs of an older epoch are stale
-// the exact tier's form of one GEMM (vit.hip precise_plan): 0 = gemm_mid.hip, S >= 1 = the 256 x 256 persistent kernel in S K-parts
+// the exact tier's form of one GEMM (vit_precise.hip precise_plan): 0 = gemm_mid.hip, S >= 1 = the 256 x 256 persistent kernel in S K-parts
 int pg_gemm_precise_route(int M, int N, int Ktot, bool resid, const int* cand, int ncand);
 
 // GEMM variants (env PIGEON_GEMM_VARIANT, the `variant` argument of pg_op_gemm16*): the numbers are ABI.  33 and 36 are the two

@@ -1,7 +1,7 @@
 """The fast tier's 16-bit chain restated in fp64 (torch only; test infrastructure, no kernel and no product code is used).
 
 pg_vit_forward / pg_vit_forward_hidden is the ViT-L/14-336 encoder with 16-bit MFMA operands.  `fast_hidden` is the same network in
-fp64 arithmetic that rounds ONLY where the product rounds -- read from csrc/vit.hip (the chain and the load-time packing of the
+fp64 arithmetic that rounds ONLY where the product rounds -- read from csrc/vit.hip (the chain), csrc/vit_weights.hip (the load-time packing of the
 weights), csrc/gemm_epi.h (the epilogues), csrc/rowops.hip (im2col, pre-LayerNorm, LayerNorm, row statistics, token mean) and
 csrc/attention.hip:
 

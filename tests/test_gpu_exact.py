@@ -22,7 +22,7 @@ DEV = "cuda"
 F16, BF16, F32 = torch.float16, torch.bfloat16, torch.float32
 TAIL_ROWS = 768                                                    # pg_tune_gemm_tail_rows' default, set explicitly by the fixture
 # name -> (epilogue, N, K, variant, rows per image).  Variant 0 = the product's default path; the exact tier's two launch on 36.
-# Leading dimensions as csrc/vit.hip passes them: lda = ldw = K (the patch matrix's K is already padded from 588 to 640), ldc = N.
+# Leading dimensions as csrc/vit.hip and csrc/vit_precise.hip pass them: lda = ldw = K (the patch matrix's K is already padded from 588 to 640), ldc = N.
 LAUNCHES = {
     "patch": (X.EPI_PATCH, 1024, 640, 0, 576), "qkv_ln": (X.EPI_QKV_LN, 3072, 1024, 0, 577), "out": (X.EPI_RESID_STAT, 1024, 1024, 0, 577),
     "fc1_ln": (X.EPI_GELU_LN, 4096, 1024, 0, 577), "fc2": (X.EPI_RESID_STAT, 1024, 4096, 0, 577),

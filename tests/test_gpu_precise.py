@@ -232,7 +232,7 @@ def test_precise_encoder_vs_reference_golden(env, golden_dir, name, capsys):
         assert _rel(rows, torch.from_numpy(gz["lhs_rows"])) < 10 * EXACT_TOL
     assert e_exact < EXACT_TOL
     assert e_exact < e_fast / 20
-    # the same batch again: the same bits.  Another batch SIZE may cut its GEMMs into another number of K-parts (vit.hip
+    # the same batch again: the same bits.  Another batch SIZE may cut its GEMMs into another number of K-parts (gemm_plan.hip
     # precise_parts: a pure function of the shape), i.e. another fp32 summation order: equal to ~1e-7, two orders below the
     # exact tier's own floor (rel_tol_exact 5e-6)
     assert torch.equal(enc.forward_precise(px).cpu(), emb.cpu())

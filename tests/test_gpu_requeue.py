@@ -162,7 +162,7 @@ def test_deferred_engine_on_the_real_classes(env, tmp_path):
 
     def same(x, y, ex_rows, what):
         """fast rows bit for bit; rows from the exact tier to its own reproducibility: the K-part count of its GEMMs is chosen by batch
-        shape (vit.hip precise_parts), so two passes of different size differ in fp32 summation order (~1e-7)."""
+        shape (gemm_plan.hip precise_parts), so two passes of different size differ in fp32 summation order (~1e-7)."""
         if x.dtype.is_floating_point and x.dim() >= 1 and x.shape[0] == ex_rows.shape[0]:
             assert torch.equal(x[~ex_rows], y[~ex_rows]), what
             if bool(ex_rows.any()):

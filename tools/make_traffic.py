@@ -41,7 +41,7 @@ CLASSES = {"gemm_qkv": (("gemm_pp6_kernel<T_F16, 6>", "gemm_pp6_kernel<T_F16, 0>
            "attention": (("attention8_kernel",), 2 * 3072 + 2 * 1024),          # (attention_f32_kernel: the exact pass, a few images)
            "layernorm": (("layernorm_kernel",), 4 * 1024 + 2 * 1024),
            "refine_candidates": (("refine_candidates_kernel<false>", "refine_candidates_kernel"), None)}    # <true>: the certainty pass
-TAIL_SPLIT = ("gemm_fc1", "gemm_fc2")                # the product's tail policy: K >= 2048 or N >= 4096 (vit.hip PG_DEFAULT_GEMM_TAIL_*)
+TAIL_SPLIT = ("gemm_fc1", "gemm_fc2")                # the product's tail policy: K >= 2048 or N >= 4096 (gemm_plan.hip PG_DEFAULT_GEMM_TAIL_*)
 res = {"note": "rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE (separate passes) over bench.py, one launch = %d token rows; KiB as "
                "reported; hbm_bytes_per_launch_corrected = 2 x FETCH_SIZE (gfx950 under-report of wide coalesced reads, "
                "MI355X_MICROARCH.md) + WRITE_SIZE; algorithmic_bytes = activation rows in + out (+ weights once)" % rows}
