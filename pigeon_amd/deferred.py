@@ -169,8 +169,13 @@ class DeferredExact:
         b = int(st['tol'].shape[0])
         px = st.get('pixel_values')
         if b == 0:
-            # an empty batch (a rank whose shard is empty must still be able to step): nothing to queue, nothing to patch -- it takes its
-            # place in the order of hand-out and carries the head's (empty) outputs as they are
+            if comm.world_size > 1:
+                # the other ranks would wait in this step's all-gathers (and in the padded exact passes) for a rank that never joins
+                # them: refused before any collective.  `distributed.shard_batches` deals every rank the same number of rows.
+                raise ValueError(f'DeferredExact.submit: empty batch on rank {comm.rank} of {comm.world_size} -- the other ranks would '
+                                 f'block in the step\'s all-gathers; every rank must submit the same number of rows (> 0) per step')
+            # an empty batch in a single process (the tail of a loader): nothing to queue, nothing to patch -- it takes its place in the
+            # order of hand-out and carries the head's (empty) outputs as they are
             st['pixel_values'] = None
             empty = self._empty_result(st, index, meta)
             if not self.pending:
@@ -180,10 +185,11 @@ class DeferredExact:
             return self._advance(final=False)
         can_fix = bool(getattr(model, 'exact_top1', False)) and px is not None and not st.get('exact_tier', False)
         if self.ring is not None and (b > self.B or (comm.world_size > 1 and b != self.B)):
-            out = self.flush()                                   # another batch geometry: settle what is pending, start over
+            # another batch geometry: settle what is pending and start over with new storage -- for THIS step's state, which is not
+            # computed a second time (the encoder is the expensive part, and an auto-calibration still collecting would see the
+            # batch twice)
+            settled = self.flush()
             self.ring = None
-            st['pixel_values'] = None
-            return out + self.submit(pixel_values, embedding, index, meta)
         if self.ring is None:
             self._alloc(st, b)
         rank, B, WB = comm.rank, self.B, self.WB
@@ -228,7 +234,7 @@ class DeferredExact:
                 if self.q_pixels is not None:
                     # another pixel dtype / geometry (e.g. fp16 pixels from the GPU preprocessing after fp32 tensors): settle what is
                     # queued in the old one, then start a new queue (every rank sees the same change in the same step)
-                    settled = self.flush()
+                    settled = settled + self.flush()
                     self.counters.zero_()
                     self.flushed = [0] * comm.world_size
                     self._prev_appended = [0] * comm.world_size

@@ -256,7 +256,7 @@ def evaluate_model(model: SuperGuessr, dataset, metrics: Optional[Callable] = No
 def evaluate(model: str, dataset, yfcc: bool, landmarks: bool, base_model=None, heading: bool = False,
              refine: bool = True, geocell_path: Optional[str] = None, proto_path: Optional[str] = None,
              dataset_path=None, bank=None, head_state: Optional[str] = None, multi_task: bool = False,
-             calibration: Optional[str] = None):
+             calibration: Optional[str] = None, embedding_rel_tol: Optional[float] = None):
     """reference evaluation/evaluate.py:10-85.
 
     `base_model`: as in the reference a STRING -- config.CLIP_MODEL for the pretrained tower, or the path of a checkpoint whose
@@ -275,6 +275,9 @@ def evaluate(model: str, dataset, yfcc: bool, landmarks: bool, base_model=None, 
     `calibration` (a path; pigeon_amd/certainty.py): if the file exists it is loaded AFTER the weights and before the first batch
     (`SuperGuessr.load_calibration`: a file measured on other weights raises); if not, the run calibrates on its first batch as
     without the argument and rank 0 writes the file at the end (in a multi-rank job: rank 0's own measurement).
+    `embedding_rel_tol` (precomputed embeddings, `base_model=None`): the relative error the dataset's embeddings carry, passed to
+    `SuperGuessr`.  None: the fast path's tolerance (1e-3, or what a calibration file says) -- right for files written by
+    `run.py embed`; embeddings of the exact encoder or of the fp32 reference are declared with 5e-6.
     """
     import os
     from . import config as cfg
@@ -300,8 +303,9 @@ def evaluate(model: str, dataset, yfcc: bool, landmarks: bool, base_model=None, 
                                    f'({why})') from why
             base_model = HipCLIPVisionModel(state_dict)
             print(f'Initialized base model with weights from: {path} (pretrained tower unavailable: checkpoint only)')
+    tol_kw = {} if embedding_rel_tol is None else {'embedding_rel_tol': float(embedding_rel_tol)}
     full_model = SuperGuessr(base_model, panorama=True, hierarchical=False, multi_task=multi_task, heading=heading,
-                             freeze_base=True, yfcc=yfcc, num_candidates=50, geocell_path=geocell_path)
+                             freeze_base=True, yfcc=yfcc, num_candidates=50, geocell_path=geocell_path, **tol_kw)
     # the reference's torch.load raises on a missing checkpoint (:46); only the explicit random-init names skip loading
     for ckpt in (head_state, model):
         if ckpt in (None, '', 'none', 'random'):

@@ -68,8 +68,11 @@ class SuperGuessr(nn.Module):
           .last_margin   (B,) fp32  logit(top-1) - logit(top-2);  .last_bound (B,) fp32 the margin change the threshold stands for
           .last_reencoded (n,) int64  the samples the exact tier re-encoded (empty when it is off)
         With a ProtoRefiner, `pigeon_amd.evaluate.certain_forward` extends the same statement to the refined cell and point.
-        Caller-supplied `embedding`s are judged against `embedding_rel_tol` (keyword; default `margin_rel_tol_exact`: they carry no
-        16-bit error of this forward).
+        Caller-supplied `embedding`s are judged against `embedding_rel_tol`.  Without the keyword that is the fast path's tolerance
+        in force at the time of the call (`certainty.rel_tol`: 1e-3 uncalibrated, the calibrated value afterwards) -- what embeddings
+        written by the 16-bit encoder (`run.py embed`) carry; a loaded calibration file sets 1.1 x its `image_residual_rms` instead.
+        A caller whose embeddings come from the exact encoder (or the fp32 reference) says so: `embedding_rel_tol=5e-6`, the value
+        of `margin_rel_tol_exact`.  An explicit keyword always wins.
         Extra keywords: `debias` (default True / env PIGEON_DEBIAS: the calibrated systematic part of the 16-bit encoder's error is
         subtracted from every fast embedding -- pg_embedding_debias -- instead of only being accounted for in the certainty test),
         `exact_top1`, `margin_kappa` (z-score, default 3.6), `margin_rel_tol` (default 1e-3 = the contract's embedding
@@ -87,7 +90,7 @@ class SuperGuessr(nn.Module):
                                    rel_tol=float(kwargs.pop('margin_rel_tol', os.environ.get('PIGEON_MARGIN_REL_TOL', 1e-3))),
                                    rel_tol_exact=float(kwargs.pop('margin_rel_tol_exact', 5e-6)), debias=kwargs.pop('debias', None))
         self.margin_autocalibrate = bool(kwargs.pop('margin_autocalibrate', True))
-        self.embedding_rel_tol = float(kwargs.pop('embedding_rel_tol', self.certainty.rel_tol_exact))
+        self.embedding_rel_tol = kwargs.pop('embedding_rel_tol', None)     # None: the fast path's tolerance at the time of the call
         self.last_margin = self.last_certain = self.last_tol = None
         self.last_state = None
         if len(kwargs) > 0:
@@ -142,7 +145,7 @@ class SuperGuessr(nn.Module):
         self._rel_tol0 = self.certainty.rel_tol              # the constructor's uncalibrated tolerance: what a weight load goes back to
         if self.exact_top1 and isinstance(self.base_model, HipCLIPVisionModel):
             self.base_model.enable_precise(True)             # pack the split-weight copy with the first build, not inside a request
-        self._embedding_rel_tol0 = None                      # `embedding_rel_tol` as it was before a calibration file set it (load_state gives it back)
+        self._embedding_rel_tol0 = None                      # (`embedding_rel_tol` as given, None included,) before a calibration file set it: load_state gives it back
         self.calibration_header = None                       # header of the calibration file in force (None: none loaded)
         print(f'Initialized SuperGuessr classification model with {self.num_cells} geocells.')
         if calibration is not None:
@@ -168,6 +171,16 @@ class SuperGuessr(nn.Module):
     @property
     def margin_rel_tol_exact(self) -> float:
         return self.certainty.rel_tol_exact
+
+    @property
+    def embedding_rel_tol(self) -> float:
+        """What caller-supplied embeddings are judged against: the explicit value (constructor keyword, assignment, or a calibration
+        file loaded without a base model), else the fast path's tolerance as it is NOW."""
+        return self.certainty.rel_tol if self._embedding_rel_tol is None else self._embedding_rel_tol
+
+    @embedding_rel_tol.setter
+    def embedding_rel_tol(self, v):
+        self._embedding_rel_tol = None if v is None else float(v)
 
     def _set_hidden_size(self):
         if self.base_model is not None:
@@ -209,7 +222,7 @@ class SuperGuessr(nn.Module):
         # after the weights, `evaluate()` does it in that order)
         self.certainty = Certainty(self.certainty.kappa, self._rel_tol0, self.certainty.rel_tol_exact, debias=self.certainty.debias)
         if self._embedding_rel_tol0 is not None:
-            self.embedding_rel_tol, self._embedding_rel_tol0 = self._embedding_rel_tol0, None
+            self.embedding_rel_tol, self._embedding_rel_tol0 = self._embedding_rel_tol0[0], None
         self.calibration_header = None
         self._cal_buffer = []
         self._engines = {}
@@ -342,8 +355,8 @@ class SuperGuessr(nn.Module):
         head_in = self._head_rows(embedding)
         # Which error the tolerances are compared with: the calibrated fast-path error (pixels through the 16-bit encoder), the exact
         # tier's floor (pixels through the exact encoder), or -- caller-supplied embeddings, which carry no error of THIS forward --
-        # `embedding_rel_tol` (default: the exact tier's floor; whoever feeds embeddings written by `run.py embed`'s 16-bit path
-        # passes that path's error instead).  No systematic part in the last two cases.
+        # `embedding_rel_tol` (default: the fast path's tolerance, since `run.py embed` writes the 16-bit path's embeddings; whoever
+        # feeds exact ones declares it with the keyword).  No systematic part in the last two cases.
         at_floor = exact_tier or px is None
         st = self._head_with_tol(head_in, exact=at_floor)
         st['embedding'], st['head_in'], st['pixel_values'], st['exact_tier'] = embedding, head_in, px, exact_tier
@@ -556,7 +569,7 @@ class SuperGuessr(nn.Module):
                     raise CalibrationError(f'{path!r}: no image_residual_rms in the file\'s statistics -- cannot set embedding_rel_tol')
                 tol = 1.1 * float(resid)                   # the safety factor `Certainty.calibrate` puts on rel_tol
             if self._embedding_rel_tol0 is None:
-                self._embedding_rel_tol0 = self.embedding_rel_tol
+                self._embedding_rel_tol0 = (self._embedding_rel_tol,)
             self.embedding_rel_tol = float(tol)
             self.calibration_header = header
             return header

@@ -64,6 +64,12 @@ argp.add_argument('--calibration', default=None, metavar='FILE',
                        "vector all ranks already share, `evaluate` rank 0's own.  An explicit calibration run: python -m pigeon_amd.calibrate")
 
 
+argp.add_argument('--embedding-rel-tol', dest='embedding_rel_tol', type=float, default=None, metavar='TOL',
+                  help="evaluate on precomputed embeddings: the relative error they carry, against which their certainty is judged.  "
+                       "Default: the 16-bit path's tolerance (1e-3, or what --calibration says), as `embed` writes them; 5e-6 declares "
+                       "embeddings of the exact encoder or of the fp32 reference")
+
+
 class _SyntheticImages(torch.utils.data.Dataset):
     def __init__(self, n, panorama):
         self.n, self.panorama = n, panorama
@@ -166,7 +172,7 @@ def _dispatch(args, comm):
                 dataset = dataset['test'] if args.test else dataset['val']
         results = evaluate(args.name, dataset, yfcc=args.yfcc, base_model=_vision_model(args), refine=True,
                            landmarks=args.landmarks, geocell_path=geocell_path, bank=bank, heading=args.heading,
-                           multi_task=args.multitask, calibration=args.calibration)
+                           multi_task=args.multitask, calibration=args.calibration, embedding_rel_tol=args.embedding_rel_tol)
         if comm.is_main_process:
             print({k: (v if not hasattr(v, 'shape') or v.shape == () else tuple(v.shape)) for k, v in results.items() if k != 'exact_passes'})
             if 'geocell_certain' in results:

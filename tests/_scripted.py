@@ -50,6 +50,7 @@ class ScriptedModel:
         self.exact_top1 = exact_top1
         self.exact_cost_s = exact_cost_s
         self.calls = []                                   # ('exact', slots) per exact pass
+        self.encodes = []                                 # ('pixels' | 'embedding', rows) per encode_head call
         self.last_certain = None
         self._eng = {}
 
@@ -78,6 +79,7 @@ class ScriptedModel:
         return emb
 
     def encode_head(self, pixel_values=None, embedding=None):
+        self.encodes.append(('pixels', int(pixel_values.shape[0])) if pixel_values is not None else ('embedding', int(embedding.shape[0])))
         if pixel_values is not None:
             rows = pixel_values.reshape(pixel_values.shape[0], 48).float()
             st = self._head(self._embed(rows, fast=True))

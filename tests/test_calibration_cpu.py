@@ -241,8 +241,9 @@ def test_refusals_leave_the_object_unchanged(geocells, tmp_path):
 
 def test_precomputed_embeddings_take_their_tolerance_from_the_file(geocells, tmp_path):
     path, c = _file(tmp_path, fp=FP_B, panels=1)                                       # any fingerprint, any panels: no encoder to compare with
-    m = _model(geocells, fp=None)
-    assert m.embedding_rel_tol == 5e-6                                                 # the default stays the exact tier's floor
+    resid = c.stats["image_residual_rms"]
+    m = _model(geocells, fp=None, embedding_rel_tol=5e-6)                              # the caller DECLARES exact embeddings
+    assert m.embedding_rel_tol == 5e-6                                                 # ... and is taken at their word: the exact tier's floor
     m.load_calibration(path)
     assert m.embedding_rel_tol == 1.1 * c.stats["image_residual_rms"] and m.embedding_rel_tol > 5e-6
     assert not m.certainty.calibrated and m.certainty.bias is None                     # nothing else moves: there is no fast path here
@@ -263,6 +264,31 @@ def test_precomputed_embeddings_take_their_tolerance_from_the_file(geocells, tmp
     torch.save({"cell_layer.bias": torch.zeros(m.num_cells)}, ck)
     m.load_state(ck)
     assert m.embedding_rel_tol == 5e-6 and m.calibration_header is None
+    # without a declaration: the fast path's tolerance at the time of the call (embeddings written by the 16-bit encoder) -- the
+    # constructor's uncalibrated one, whatever `certainty.rel_tol` becomes, the file's while one is loaded, and back after a weight load
+    d = _model(geocells, fp=None)
+    assert d.embedding_rel_tol == d.certainty.rel_tol == 1e-3
+    assert _model(geocells, fp=None, margin_rel_tol=4e-4).embedding_rel_tol == 4e-4
+    d.certainty.rel_tol = 7e-5
+    assert d.embedding_rel_tol == 7e-5
+    d.certainty.rel_tol = 1e-3
+    d.load_calibration(path)
+    assert d.embedding_rel_tol == 1.1 * resid and d.certainty.rel_tol == 1e-3
+    d.load_state(ck)
+    assert d.embedding_rel_tol == 1e-3 and d.calibration_header is None
+    d.certainty.rel_tol = 7e-5
+    assert d.embedding_rel_tol == 7e-5                                                 # (restored to "no explicit value", not to a number)
+    # an explicit value survives the same round trip, and wins over the fast path's
+    x = _model(geocells, fp=None, embedding_rel_tol=2e-4, margin_rel_tol=4e-4)
+    assert x.embedding_rel_tol == 2e-4
+    x.load_calibration(path)
+    x.load_state(ck)
+    assert x.embedding_rel_tol == 2e-4
+    # with a tower: the calibrated tolerance once there is one
+    t = _model(geocells)
+    assert t.embedding_rel_tol == 1e-3
+    t.load_calibration(_file(tmp_path, "tower.npz", c=c)[0])
+    assert t.embedding_rel_tol == t.certainty.rel_tol == c.rel_tol
 
 
 def test_clip_embedding_takes_the_same_vector(geocells, tmp_path):
@@ -318,3 +344,7 @@ def test_command_lines_accept_calibration(tmp_path, monkeypatch, capsys):
     import inspect
     from pigeon_amd.evaluate import evaluate
     assert inspect.signature(evaluate).parameters["calibration"].default is None
+    # precomputed embeddings: the error they carry can be declared on both surfaces (default: the 16-bit path's)
+    assert inspect.signature(evaluate).parameters["embedding_rel_tol"].default is None
+    assert run.argp.parse_args(["evaluate", "head.model"]).embedding_rel_tol is None
+    assert run.argp.parse_args(["evaluate", "head.model", "--embedding-rel-tol", "5e-6"]).embedding_rel_tol == 5e-6

@@ -370,6 +370,82 @@ def test_deferred_engine_empty_batch_keeps_its_place():
     assert order == [0] and out[0]["refined_LLH"].shape == (0, 2)
 
 
+def _same_result(a, b, where):
+    for k in a:
+        if torch.is_tensor(a[k]):
+            assert torch.equal(a[k], b[k]), (where, k)
+    for k in a["state"]:
+        if torch.is_tensor(a["state"][k]):
+            assert torch.equal(a["state"][k], b["state"][k]), (where, "state", k)
+    assert a["queued"] == b["queued"], where
+
+
+@pytest.mark.parametrize("form", ["immediate", "deferred"])
+def test_deferred_engine_batch_larger_than_the_ring_is_encoded_once(form):
+    """Steps of 3, 3, 5, 5 rows: the third does not fit the ring allocated for 3 rows.  The engine settles what is pending and
+    allocates anew FOR THE STATE IT HAS -- `encode_head` runs exactly once per submitted step (encoding the batch again costs a
+    whole encoder pass, and an auto-calibration that is still collecting would be handed the same pixels twice) -- and every step is
+    handed out once, in order, bit-equal to settling that step by itself."""
+    from _scripted import ScriptedModel, ScriptedRefiner, make_pixels
+    from oracle import requeue_oracle
+    from pigeon_amd.deferred import DeferredExact
+    g = torch.Generator().manual_seed(21)
+    steps = []
+    for i, B in enumerate((3, 3, 5, 5)):
+        flags = lambda p: (torch.rand(B, generator=g) > p).float().tolist()        # noqa: E731
+        steps.append(make_pixels(flags(0.4), flags(0.1), flags(0.3), flags(0.1), seed=500 + i))
+    kw = dict(immediate=True) if form == "immediate" else dict(min_flush=4, max_lag=5)
+    out, order, _, eng, m = _run_engine(steps, **kw)
+    assert m.encodes == [("pixels", 3), ("pixels", 3), ("pixels", 5), ("pixels", 5)]
+    assert order == [0, 1, 2, 3] and eng.B == 5 and eng.check_nothing_dropped() == 0
+    alone = []
+    for i, px in enumerate(steps):                                                  # every step settled by itself, in order
+        ma = ScriptedModel()
+        ea = DeferredExact(ma, ScriptedRefiner(), ops=requeue_oracle, immediate=True)
+        res = ea.submit(px, meta=i)
+        assert len(res) == 1 and ma.encodes == [("pixels", int(px.shape[0]))]
+        alone.append(res[0])
+    for i in range(4):
+        _same_result(alone[i], out[i], i)
+    assert any(bool(r["exact"].any()) for r in out.values())                       # rows were queued on both sides of the change
+    assert sum(n for _, n in m.calls) == sum(int(r["exact"].sum()) for r in out.values())
+
+
+class _RecordingComm:
+    """Two ranks without processes: every collective is logged and then fails (nobody is on the other side)."""
+    rank, world_size = 0, 2
+
+    def __init__(self):
+        self.log = []
+
+    def gather_many(self, tensors, out=None):
+        self.log.append([tuple(t.shape) for t in tensors])
+        raise RuntimeError("collective entered: the other rank never arrives")
+
+
+def test_deferred_engine_refuses_an_empty_batch_with_several_ranks():
+    """With world_size > 1 an empty batch cannot step: the other ranks would sit in the step's two all-gathers (and in the padded
+    exact passes).  `submit` raises a ValueError naming the cause BEFORE any collective; `distributed.shard_batches` never deals an
+    empty shard (tests/test_distributed_cpu.py).  One rank: test_deferred_engine_empty_batch_keeps_its_place."""
+    from _scripted import ScriptedModel, ScriptedRefiner, make_pixels
+    from oracle import requeue_oracle
+    from pigeon_amd.deferred import DeferredExact
+    for kw in (dict(immediate=True), dict(min_flush=4, max_lag=5)):
+        comm = _RecordingComm()
+        eng = DeferredExact(ScriptedModel(), ScriptedRefiner(), comm=comm, ops=requeue_oracle, **kw)
+        with pytest.raises(ValueError, match="empty batch") as ei:
+            eng.submit(make_pixels([], seed=2))
+        assert "rank 0 of 2" in str(ei.value) and "all-gather" in str(ei.value)
+        assert comm.log == [] and eng.n_submitted == 0 and not eng.pending
+        with pytest.raises(ValueError, match="empty batch"):
+            eng.submit(embedding=torch.zeros((0, 4, 8)))
+        assert comm.log == []
+        # ... and the stand-in does what it says: a non-empty step reaches the first all-gather
+        with pytest.raises(RuntimeError, match="collective entered"):
+            eng.submit(make_pixels([1, 1, 1], seed=3))
+        assert len(comm.log) == 1
+
+
 def test_deferred_engine_pixel_dtype_change_settles_and_restarts_the_queue():
     """fp32 pixel tensors, then fp16 ones (what the GPU preprocessing hands over): the rows queued in the old geometry are settled
     first, the queue restarts, every step is handed out once and in order (bench.py's ingest leg did exactly this and failed)."""
