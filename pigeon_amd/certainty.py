@@ -64,6 +64,25 @@ _HEADER_KEYS = ('format_version', 'fingerprint', 'layers', 'mma_dtype', 'ln_fold
 _STATE_SCALARS = (('rel_tol', float), ('rel_tol_exact', float), ('kappa', float), ('debias', bool), ('force_exact', bool),
                   ('calibrated', bool))
 
+# The numbers of the measurement, each stated here once (`Certainty.calibrate`; `CLIPEmbedding` and `SuperGuessr` import them).
+SAFETY = 1.1                    # a tolerance is this x the residual it was measured from
+KEEP_BIAS_BELOW = 0.9           # a fitted systematic part is kept when the held-out residual is below this share of the total error
+CONTRACT_SHARE = 0.85           # the 16-bit path is outside the embedding contract above this share of it over all images ...
+CONTRACT_SHARE_WORST = 0.95     # ... or above this share on the worst image
+
+
+def outside_contract(image_rel_err: float, worst_image_rel_err: float, contract: float = 1e-3) -> bool:
+    """The `force_exact` verdict on the RAW 16-bit error (overall, worst image) -- also of a job's ranks together (`combine_ranks`)."""
+    return image_rel_err > CONTRACT_SHARE * contract or worst_image_rel_err > CONTRACT_SHARE_WORST * contract
+
+
+def combine_ranks(every):
+    """One verdict and one vector for a data-parallel job.  `every`: per rank (image_rel_err, worst_image_rel_err, bias or None) ->
+    (the largest of each error: all ranks act on the worst measurement; the mean of the ranks' vectors, None if any rank kept none)."""
+    vecs = [e[2] for e in every]
+    bias = None if any(b is None for b in vecs) else torch.stack(vecs).mean(dim=0)
+    return max(e[0] for e in every), max(e[1] for e in every), bias
+
 
 class CalibrationError(ValueError):
     """A calibration file that cannot be used: unreadable, of an unknown format version, or measured on other weights / another
@@ -117,7 +136,7 @@ class Certainty:
         return x - x.norm(dim=1, keepdim=True) * bias.to(x.device)
 
     @torch.no_grad()
-    def calibrate(self, fast: torch.Tensor, exact: torch.Tensor, safety: float = 1.1, use_drift: bool = True,
+    def calibrate(self, fast: torch.Tensor, exact: torch.Tensor, safety: float = SAFETY, use_drift: bool = True,
                   fast_images: Optional[torch.Tensor] = None, exact_images: Optional[torch.Tensor] = None,
                   contract: float = 1e-3) -> dict:
         """fast, exact: (n,1024) embeddings of the same n samples (panel means for panoramas).  Sets `rel_tol` (and `drift` when a
@@ -153,13 +172,13 @@ class Certainty:
             corr = self.apply_bias(held_f.reshape((-1, held_f.shape[-1])), b_half).reshape(held_f.shape).mean(dim=1)
             ref = held_e.mean(dim=1)
             resid = float(((corr - ref).norm(dim=1) / ref.norm(dim=1).clamp_min(1e-30)).pow(2).mean().sqrt())
-            st['residual_rms'] = resid
+            st['residual_rms'] = st['held_out_residual_rms'] = resid        # (the second keeps the figure when the fit is rejected)
             st['drift_norm'] = float(rel_img.reshape((-1, rel_img.shape[-1])).mean(dim=0).norm())
             # the same held-out residual per IMAGE (not per panel mean): what an embedding this path writes out still carries
             corr_i = self.apply_bias(held_f.reshape((-1, held_f.shape[-1])), b_half)
             held_ei = held_e.reshape((-1, held_e.shape[-1]))
             held_image_resid = float(((corr_i - held_ei).norm(dim=1) / held_ei.norm(dim=1).clamp_min(1e-30)).pow(2).mean().sqrt())
-            if resid < 0.9 * total:
+            if resid < KEEP_BIAS_BELOW * total:
                 bias = rel_img.reshape((-1, rel_img.shape[-1])).mean(dim=0).contiguous()
                 st['drift_used'] = st['debias'] = True
             else:
@@ -170,7 +189,7 @@ class Certainty:
             resid = float((held - beta_half).norm(dim=1).pow(2).mean().sqrt())
             st['residual_rms'] = resid
             st['drift_norm'] = float(rel.mean(dim=0).norm())
-            if resid < 0.9 * total:
+            if resid < KEEP_BIAS_BELOW * total:
                 drift = rel.mean(dim=0).contiguous()
                 st['drift_used'] = True
         if fast_images is not None and exact_images is not None and fast_images.numel():
@@ -178,7 +197,7 @@ class Certainty:
             st['image_rel_err'] = float((fi - ei).norm() / ei.norm().clamp_min(1e-30))
             st['worst_image_rel_err'] = float(((fi - ei).norm(dim=1) / ei.norm(dim=1).clamp_min(1e-30)).max())
             # (the verdict is taken on the RAW 16-bit error also when a bias is subtracted afterwards: the conservative reading)
-            self.force_exact = st['image_rel_err'] > 0.85 * contract or st['worst_image_rel_err'] > 0.95 * contract
+            self.force_exact = outside_contract(st['image_rel_err'], st['worst_image_rel_err'], contract)
             if bias is not None:
                 ci = self.apply_bias(fi, bias)              # (in sample: the bias was fitted on these images)
                 st['image_rel_err_debiased'] = float((ci - ei).norm() / ei.norm().clamp_min(1e-30))

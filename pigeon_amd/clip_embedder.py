@@ -17,6 +17,7 @@ import torch
 from torch import Tensor
 
 from . import hip_ops, synthetic
+from .certainty import SAFETY, CalibrationError, Certainty, combine_ranks, outside_contract, require_fingerprint
 from .config import CLIP_MODEL, OPENAI_CLIP_MEAN, OPENAI_CLIP_STD
 from .packing import PackedImages, as_rgb_array, check_rgb_u8, chunk_by_bytes, pack_images, pack_into, packed_layout  # noqa: F401  (re-exported)
 from .utils import load_state_dict
@@ -421,10 +422,9 @@ class CLIPEmbedding(torch.nn.Module):
         self.contract_guard = (contract_guard or os.environ.get('PIGEON_EMBED_GUARD', 'exact')).lower()
         if self.contract_guard not in ('exact', 'raise', 'off'):
             raise ValueError(f"contract_guard must be 'exact', 'raise' or 'off', got {self.contract_guard!r}")
-        self.guard_stats = None                  # what the first forward measured (None until then / with the guard off)
-        self.force_exact = False
-        self.debias = os.environ.get('PIGEON_DEBIAS', '1') not in ('', '0')
-        self.bias = None                         # (1024,) fp32: the systematic part `_check_contract` measured, subtracted from every fast embedding
+        self.guard_stats = None                  # what the first forward measured / a file said (None until then / with the guard off)
+        # the measurement and its verdict (pigeon_amd/certainty.py): `bias`, `force_exact` and the calibration file are views of it
+        self.certainty = Certainty()
 
         if load_checkpoint:
             sd = torch.load(model_name, map_location='cpu')
@@ -440,31 +440,33 @@ class CLIPEmbedding(torch.nn.Module):
         if calibration is not None:
             self.load_calibration(calibration)
 
+    bias = property(lambda self: self.certainty.bias, doc="(1024,) fp32 or None: the systematic part subtracted from every fast embedding")
+    force_exact = property(lambda self: self.certainty.force_exact, doc="every image is encoded in the exact mode")
+    debias = property(lambda self: self.certainty.debias)
+
     # ---- calibration as a file (pigeon_amd/certainty.py) ----
     def save_calibration(self, path: str, source: str = '') -> str:
         """Write what the first forward's guard measured -- the bias this module subtracts (in a data-parallel job: the one vector
         all ranks share) and the verdict -- as a calibration file keyed by the encoder's weight fingerprint.  `panels` is 1: the
         tolerance in the file is a per-image one.  A `SuperGuessr` on precomputed embeddings (base_model=None) or another
         `CLIPEmbedding` loads it; a panorama `SuperGuessr` with an encoder wants a file measured on panoramas."""
-        from .certainty import CalibrationError, Certainty
-        st = self.guard_stats
+        st, c = self.guard_stats, self.certainty
         if st is None:
             raise CalibrationError('CLIPEmbedding.save_calibration: nothing measured yet (the guard runs in the first forward; '
                                    "contract_guard='off' never measures)")
-        c = Certainty(debias=self.debias)
-        # the per-image error of what this module returns: what is left after the bias (held out), or the raw error without one
-        resid = st.get('residual_rms') if (self.bias is not None or st.get('image_rel_err') is None) else st.get('image_rel_err')
+        # The file's tolerance is the per-image error of what THIS module returns, by its own rule and not `calibrate`'s: what is left
+        # after the bias (held out) -- or, without a bias, the raw error of the whole batch (`image_rel_err`, a norm over all images,
+        # where `calibrate` records the RMS of the per-image ratios).  Banks were built from files that say this; it stays.
+        resid = st.get('residual_rms') if (c.bias is not None or st.get('image_rel_err') is None) else st.get('image_rel_err')
         if resid is None:
             raise CalibrationError('CLIPEmbedding.save_calibration: the guard statistics hold no per-image error')
         resid = float(resid)
-        c.bias = None if self.bias is None else self.bias.detach().to('cpu', torch.float32).clone()
-        c.force_exact = bool(self.force_exact)
-        c.rel_tol = max(1.1 * resid, 2.0 * c.rel_tol_exact)
-        c.calibrated = True
+        c.rel_tol = max(SAFETY * resid, 2.0 * c.rel_tol_exact)
+        # ... and its statistics are the guard's (on top of a loaded file's), not the panorama-shaped ones `calibrate` reports
         c.stats = dict(st.get('file_stats') or {})
         c.stats.update({k: v for k, v in st.items() if isinstance(v, (bool, int, float, str))})
         c.stats.update(samples=int(st['images']), image_residual_rms=resid, rel_tol=c.rel_tol, kappa=c.kappa,
-                       force_exact=c.force_exact, debias=self.bias is not None)
+                       force_exact=c.force_exact, debias=c.bias is not None)
         base = self.clip_model.base_model
         meta = base.encoder_config()
         meta['source'] = source or f"CLIPEmbedding, {st['images']} images"
@@ -472,10 +474,9 @@ class CLIPEmbedding(torch.nn.Module):
 
     def load_calibration(self, path: str) -> dict:
         """Take `bias` and `force_exact` from a calibration file and fill `guard_stats`: the first forward then measures nothing and
-        joins no collective (every rank of a job loads the same file instead).  The file is checked before anything changes: an
-        unreadable file, an unknown format_version and a fingerprint that is not this encoder's are refused (CalibrationError, both
-        fingerprints named).  Any `panels` is accepted: the bias is per image.  Returns the header."""
-        from .certainty import Certainty, require_fingerprint
+        joins no collective (every rank of a job loads the same file instead).  The file is loaded into a fresh `Certainty` and checked
+        before anything changes: an unreadable file, an unknown format_version and a fingerprint that is not this encoder's are refused
+        (CalibrationError, both fingerprints named).  Any `panels` is accepted: the bias is per image.  Returns the header."""
         sd, header = Certainty.load(path)
         c = Certainty()
         c.load_state_dict(sd)
@@ -488,7 +489,7 @@ class CLIPEmbedding(torch.nn.Module):
               'outside': bool(c.force_exact), 'from_file': str(path), 'fingerprint': header['fingerprint'], 'file_stats': dict(c.stats)}
         if 'image_residual_rms' in c.stats:
             st['residual_rms'] = c.stats['image_residual_rms']
-        self.bias, self.force_exact, self.guard_stats, self.calibration_header = c.bias, bool(c.force_exact), st, header
+        self.certainty, self.guard_stats, self.calibration_header = c, st, header
         return header
 
     def _get_embedding(self, image) -> Tensor:
@@ -512,60 +513,51 @@ class CLIPEmbedding(torch.nn.Module):
             if self.force_exact:
                 return base.embed_precise(pixel_values)
             emb = base.embed(pixel_values)
-            if self.bias is not None:
+            bias = self.certainty.bias_on(emb.device)
+            if bias is not None:
                 # the 16-bit encoder's measured systematic error taken out of every image's embedding (pigeon_amd/certainty.py `debias`)
-                hip_ops.embedding_debias(emb, self.bias if self.bias.device == emb.device else self.bias.to(emb.device))
+                hip_ops.embedding_debias(emb, bias)
             return emb
 
-    def _check_contract(self, base, pixel_values: Tensor, max_images: int = 32, contract: float = 1e-3) -> dict:
-        """Once per set of weights: the 16-bit encoder against the exact one on up to `max_images` images of the first batch.
+    def _check_contract(self, base, pixel_values: Tensor, max_images: int = 32) -> dict:
+        """Once per set of weights: the 16-bit encoder against the exact one on up to `max_images` images of the first batch -- the
+        measurement; `_judge` is what follows from it.
         (A first batch of fewer than 8 images measures the error but fits no bias: nothing is subtracted for the lifetime of this
         object -- hand the embed path a full first batch, as `run.py embed` does, or set PIGEON_DEBIAS=0 on both entry points.)"""
         px = _to_device_pixels(pixel_values[:max_images], base._dummy.device)
-        fast, exact = base.embed(px), base.embed_precise(px)
-        err = (fast - exact).norm(dim=1) / exact.norm(dim=1).clamp_min(1e-30)
-        st = {'images': int(px.shape[0]), 'image_rel_err': float((fast - exact).norm() / exact.norm().clamp_min(1e-30)),
-              'worst_image_rel_err': float(err.max()), 'contract': contract}
-        # one verdict for a data-parallel job (`run.py embed` under torchrun): every rank measures its own first batch; all ranks act on
-        # the worst measurement, so that the files they write together do not mix encoders
+        return self._judge(base.embed(px), base.embed_precise(px))
+
+    def _judge(self, fast: Tensor, exact: Tensor, contract: float = 1e-3) -> dict:
+        """(n,1024) embeddings of the same images by the two encoders -> `certainty` (bias, verdict) and `guard_stats`: one image per
+        sample through `Certainty.calibrate` -- the fit on the even images, the residual on the odd ones, the verdict on the RAW error
+        (the conservative reading) -- and, in a data-parallel job (`run.py embed` under torchrun), `combine_ranks` over what every
+        rank measured on its own first batch, so that the files the ranks write together mix neither encoders nor vectors."""
+        c = self.certainty
+        # (`use_drift`: without PIGEON_DEBIAS there is nothing here that a drift vector could be handed to -- no fit at all)
+        cs = c.calibrate(fast, exact, fast_images=fast, exact_images=exact, contract=contract, use_drift=c.debias)
+        st = {'images': cs['samples'], 'image_rel_err': cs['image_rel_err'], 'worst_image_rel_err': cs['worst_image_rel_err'],
+              'contract': contract}
+        if 'held_out_residual_rms' in cs:                            # a fit was made (8 images or more); kept or not, it is reported
+            st['bias_norm'], st['residual_rms'] = cs['drift_norm'], cs['held_out_residual_rms']
         import torch.distributed as dist
         if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
-            every = [None] * dist.get_world_size()
-            dist.all_gather_object(every, (st['image_rel_err'], st['worst_image_rel_err']))
-            st['image_rel_err_all_ranks'] = max(e[0] for e in every)
-            st['worst_image_rel_err_all_ranks'] = max(e[1] for e in every)
-        # the part of that error that is the SAME for every image (relative to |e|): with PIGEON_DEBIAS (default on) it is subtracted from
-        # every fast embedding this module returns (pg_embedding_debias), when a held-out half of the images confirms that what is left
-        # is smaller.  The verdict below is taken on the RAW error (the conservative reading).
-        bias = None
-        if self.debias and px.shape[0] >= 8:
-            rel = (fast - exact) / exact.norm(dim=1, keepdim=True).clamp_min(1e-30)
-            from .certainty import Certainty
-            held = Certainty.apply_bias(fast[1::2], rel[0::2].mean(dim=0))
-            left = float(((held - exact[1::2]).norm(dim=1) / exact[1::2].norm(dim=1).clamp_min(1e-30)).pow(2).mean().sqrt())
-            raw = float(err.pow(2).mean().sqrt())
-            st['bias_norm'], st['residual_rms'] = float(rel.mean(dim=0).norm()), left
-            if left < 0.9 * raw:
-                bias = rel.mean(dim=0).contiguous()
-        if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
-            every = [None] * dist.get_world_size()                   # one vector for the whole job: the mean of the ranks', if all keep one
-            dist.all_gather_object(every, None if bias is None else bias.cpu())
-            bias = None if any(b is None for b in every) else torch.stack(every).mean(dim=0).to(fast.device)
-        self.bias = bias
-        st['debias'] = bias is not None
-        overall = st.get('image_rel_err_all_ranks', st['image_rel_err'])
-        worst = st.get('worst_image_rel_err_all_ranks', st['worst_image_rel_err'])
-        st['outside'] = overall > 0.85 * contract or worst > 0.95 * contract
+            errs, vecs = [None] * dist.get_world_size(), [None] * dist.get_world_size()
+            dist.all_gather_object(errs, (st['image_rel_err'], st['worst_image_rel_err']))
+            dist.all_gather_object(vecs, None if c.bias is None else c.bias.cpu())
+            st['image_rel_err_all_ranks'], st['worst_image_rel_err_all_ranks'], bias = combine_ranks([e + (b,) for e, b in zip(errs, vecs)])
+            c.bias = None if bias is None else bias.to(fast.device)
+            c.force_exact = outside_contract(st['image_rel_err_all_ranks'], st['worst_image_rel_err_all_ranks'], contract)
+        st['debias'], st['outside'] = c.bias is not None, c.force_exact
         self.guard_stats = st
         print(f"pigeon_amd.CLIPEmbedding: 16-bit encoder vs exact encoder on {st['images']} images of the first batch: "
               f"{st['image_rel_err']:.2e} relative overall, worst image {st['worst_image_rel_err']:.2e} (contract {contract:g})"
-              + (f"; its systematic part ({st['bias_norm']:.2e}) is subtracted from every embedding, {st['residual_rms']:.2e} left" if bias is not None else ""))
+              + (f"; its systematic part ({st['bias_norm']:.2e}) is subtracted from every embedding, {st['residual_rms']:.2e} left" if c.bias is not None else ""))
         if st['outside']:
             if self.contract_guard == 'raise':
+                c.force_exact = False                                # ('raise' never encodes in the exact mode: the caller has been told)
                 raise RuntimeError('CLIPEmbedding: the 16-bit encoder is outside the 1e-3 embedding contract on these weights '
                                    f"({st['image_rel_err']:.2e} overall, worst image {st['worst_image_rel_err']:.2e}); construct with "
                                    "contract_guard='exact' to encode in the exact mode")
-            self.force_exact = True
             print('pigeon_amd.CLIPEmbedding: outside the embedding contract on these weights -- every image will be encoded in the '
                   'exact mode (about 3x the time per image).')
         return st

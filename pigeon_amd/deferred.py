@@ -34,7 +34,7 @@ CPU tests and bench.py --dry-run pass torch stand-ins, which are test infrastruc
 from __future__ import annotations
 
 from collections import deque
-from typing import Dict, List, Optional
+from typing import Dict, List, NamedTuple, Optional
 
 import torch
 
@@ -43,6 +43,32 @@ from .utils import TopK
 
 # what a multi-task model's state carries on top (pg_aux_heads_forward): rank-local reports like tol / margin / sens, never gathered
 AUX_KEYS = ('aux_preds', 'aux_cls', 'aux_tol', 'aux_code')
+
+
+class Col(NamedTuple):
+    """One tensor a step carries from `submit` to the result handed out."""
+    name: str
+    where: str                  # 'ring': gathered, world x B rows per step | 'local': this rank's B rows, never gathered
+    src: str                    # 'state': that key of encode_head / exact_rows | 'index' | 'refiner': forward_certain | 'queue': the queue decision
+    when: str = 'always'        # | 'refiner': with one | 'present': when the state has it | 'logits': that and `keep_logits`
+    dtype: Optional[torch.dtype] = None     # dtype and shape after the rows, where the state does not give them
+    tail: tuple = ()
+
+
+# Every column, once.  Ring columns in the order of the step's two all-gathers (the state's and the index BEFORE the refinement; the
+# queue's, then the refiner's, after it); an exact pass patches the 'state' and 'refiner' columns, `certain` and `exact`.
+COLUMNS = (
+    *(Col(k, 'ring', 'state') for k in ('embedding', 'topk_indices', 'topk_values', 'preds_LLH', 'preds_geocell')),
+    Col('index', 'ring', 'index', dtype=torch.int64),
+    Col('certain', 'ring', 'queue', dtype=torch.bool),           # one byte per row, 0 / 1: the kernels write it as uint8
+    Col('cause', 'ring', 'queue', dtype=torch.int32),
+    Col('exact', 'ring', 'queue', dtype=torch.bool),
+    Col('refined_LLH', 'ring', 'refiner', 'refiner', torch.float32, (2,)),
+    Col('refined_geocell', 'ring', 'refiner', 'refiner', torch.int64),
+    *(Col(k, 'local', 'state', 'present') for k in ('tol', 'margin', 'sens') + AUX_KEYS),
+    Col('logits', 'local', 'state', 'logits'),
+    Col('refine_tol', 'local', 'refiner', 'refiner', torch.float32),
+    Col('refine_code', 'local', 'refiner', 'refiner', torch.int32))
 
 
 class LocalComm:
@@ -86,32 +112,32 @@ class DeferredExact:
         self.dev = None                           # the model's device, known at the first submit
 
     # ------------------------------------------------------------------------------------------------ storage
-    def _alloc(self, st: dict, B: int, index_dtype=torch.int64):
+    def _carries(self, c: Col, st: dict) -> bool:
+        """`Col.when`, for this engine and a step's state."""
+        if c.when == 'always':
+            return True
+        if c.when == 'refiner':
+            return self.refiner is not None
+        return st.get(c.name) is not None and (c.when == 'present' or self.keep_logits)
+
+    @staticmethod
+    def _zeros(c: Col, rows: int, st: dict) -> torch.Tensor:
+        """`rows` rows of column c: dtype and shape as the table says, or as the state's own tensor has them."""
+        dtype, tail = (c.dtype, c.tail) if c.src != 'state' else (st[c.name].dtype, tuple(st[c.name].shape[1:]))
+        return torch.zeros((rows,) + tail, dtype=dtype, device=st['tol'].device)
+
+    def _alloc(self, st: dict, B: int):
         dev = st['tol'].device
         W = self.comm.world_size
         self.B, self.W, self.WB, self.dev = B, W, W * B, dev
-        R, n = self.R, self.R * W * B
-        emb = st['embedding']
-        ring = {'embedding': torch.zeros((n,) + tuple(emb.shape[1:]), dtype=emb.dtype, device=dev)}
-        for k in ('topk_values', 'topk_indices', 'preds_LLH', 'preds_geocell'):
-            ring[k] = torch.zeros((n,) + tuple(st[k].shape[1:]), dtype=st[k].dtype, device=dev)
-        ring['index'] = torch.zeros((n,), dtype=index_dtype, device=dev)
-        if self.refiner is not None:
-            ring['refined_LLH'] = torch.zeros((n, 2), dtype=torch.float32, device=dev)
-            ring['refined_geocell'] = torch.zeros((n,), dtype=torch.int64, device=dev)
-        ring['certain'] = torch.zeros((n,), dtype=torch.bool, device=dev)       # one byte per row, 0 / 1: the kernels write it as uint8
-        ring['cause'] = torch.zeros((n,), dtype=torch.int32, device=dev)
-        ring['exact'] = torch.zeros((n,), dtype=torch.bool, device=dev)
-        self.ring = ring
-        loc = {}                                      # this rank's own reports: never gathered, patched through the remap
-        # (aux_*: the auxiliary heads of a multi-task model -- SuperGuessr._head_with_tol -- absent otherwise)
-        for k in ('tol', 'margin', 'sens') + AUX_KEYS + (('logits',) if self.keep_logits and 'logits' in st else ()):
-            if k in st and st[k] is not None:
-                loc[k] = torch.zeros((R * B,) + tuple(st[k].shape[1:]), dtype=st[k].dtype, device=dev)
-        if self.refiner is not None:
-            loc['refine_tol'] = torch.zeros((R * B,), dtype=torch.float32, device=dev)
-            loc['refine_code'] = torch.zeros((R * B,), dtype=torch.int32, device=dev)
-        self.local = loc
+        R = self.R
+        cols = [c for c in COLUMNS if self._carries(c, st)]
+        self.ring = {c.name: self._zeros(c, R * W * B, st) for c in cols if c.where == 'ring'}
+        self.local = {c.name: self._zeros(c, R * B, st) for c in cols if c.where == 'local'}     # never gathered, patched through the remap
+        # what a step moves, by source (looked up here, not per step): its first all-gather; its second, around the queue count
+        names = lambda where, *srcs: [c.name for c in cols if c.where == where and c.src in srcs]     # noqa: E731
+        self.gather1, self.gather2 = names('ring', 'state', 'index'), (names('ring', 'queue'), names('ring', 'refiner'))
+        self.local_refiner = names('local', 'refiner')
         self._false = torch.zeros((B,), dtype=torch.bool, device=dev)
         self._true = torch.ones((B,), dtype=torch.bool, device=dev)
         self._arange = torch.arange(B, device=dev, dtype=torch.int64)
@@ -177,7 +203,7 @@ class DeferredExact:
             # an empty batch in a single process (the tail of a loader): nothing to queue, nothing to patch -- it takes its place in the
             # order of hand-out and carries the head's (empty) outputs as they are
             st['pixel_values'] = None
-            empty = self._empty_result(st, index, meta)
+            empty = self._empty_result(st, meta)
             if not self.pending:
                 return [empty]
             self.pending.append(dict(step=self.n_submitted, slot=-1, b=0, meta=meta, appended=None, can_fix=False, ready=empty))
@@ -204,6 +230,7 @@ class DeferredExact:
         index = index.to(dev)
         exact_tier = bool(st.get('exact_tier', False))
         thr = st['thr']
+        new = dict(st, index=index)                               # this step's value of every column, as it becomes known
         for k, buf in self.local.items():
             if k in st:
                 buf[lbase:lbase + b].copy_(st[k])
@@ -212,19 +239,18 @@ class DeferredExact:
         own = slice(gbase + rank * b, gbase + (rank + 1) * b)
         self._mark(marks)
         # the gather BEFORE the refinement: `north_star` / the reference's accelerator.gather (preprocessing/embed.py:36-37)
-        comm.gather_many([st['embedding'], st['topk_indices'], st['topk_values'], st['preds_LLH'], st['preds_geocell'], index],
-                         out=[slab('embedding'), slab('topk_indices'), slab('topk_values'), slab('preds_LLH'), slab('preds_geocell'),
-                              slab('index')])
+        comm.gather_many([new[k] for k in self.gather1], out=[slab(k) for k in self.gather1])
         self._mark(marks)
         rtol = rcode = None
         W_head = model.cell_layer.weight.data
         if self.refiner is not None:
             # THE refinement of this rank's slice (pg_refine_forward_ex = pg_refine_forward + the records the certainty pass reads)
-            llh_r, cell_r, rtol, rcode, self.boundary_checked = self.refiner.forward_certain(
+            new['refined_LLH'], new['refined_geocell'], rtol, rcode, self.boundary_checked = self.refiner.forward_certain(
                 ring['embedding'][own], ring['preds_LLH'][own], ring['topk_indices'][own], ring['topk_values'][own], W_head,
                 st['wstats'], st.get('drift'))
-            self.local['refine_tol'][lbase:lbase + b].copy_(rtol)
-            self.local['refine_code'][lbase:lbase + b].copy_(rcode)
+            new.update(refine_tol=rtol, refine_code=rcode)
+            for k in self.local_refiner:
+                self.local[k][lbase:lbase + b].copy_(new[k])
         wants_queue = bool(getattr(model, 'exact_top1', False)) and px is not None
         if wants_queue:
             # (also a rank whose whole batch went through the exact encoder -- `exact_tier`: it queues nothing, but in a data-parallel job
@@ -246,13 +272,12 @@ class DeferredExact:
             ops.rows_to_slots(px_rows, row_slot, self.q_pixels)
         else:
             certain, cause, _ = ops.requeue_append(st['tol'], rtol, rcode, thr, False)
-        small = [certain.view(torch.bool), cause, (self._true if exact_tier else self._false)[:b], self.counters[:1]]
-        outs = [slab('certain'), slab('cause'), slab('exact'), self.counts_all[slot]]
-        if self.refiner is not None:
-            small += [llh_r, cell_r]
-            outs += [slab('refined_LLH'), slab('refined_geocell')]
+        new.update(certain=certain.view(torch.bool), cause=cause, exact=(self._true if exact_tier else self._false)[:b])
+        # the queue's columns, the queue count, then the refiner's
+        queue, refined = self.gather2
         self._mark(marks)
-        comm.gather_many(small, out=outs)
+        comm.gather_many([new[k] for k in queue] + [self.counters[:1]] + [new[k] for k in refined],
+                         out=[slab(k) for k in queue] + [self.counts_all[slot]] + [slab(k) for k in refined])
         self.host_counts[slot].copy_(self.counts_all[slot], non_blocking=True)
         if self.events[slot] is not None:
             self.events[slot].record()
@@ -269,21 +294,25 @@ class DeferredExact:
         return self._advance(final=True)
 
     # ------------------------------------------------------------------------------------------------ host side of the queue
-    def _empty_result(self, st: dict, index, meta) -> dict:
-        dev = st['tol'].device
-        k = int(getattr(self.model, 'num_candidates', st['topk_indices'].shape[1]))
-        z = lambda dt, *shape: torch.zeros((0,) + shape, dtype=dt, device=dev)     # noqa: E731
-        state = {kk: st[kk] for kk in ('embedding', 'topk_values', 'topk_indices', 'preds_LLH', 'preds_geocell', 'tol', 'margin', 'sens',
-                                       'logits') + AUX_KEYS if kk in st}
-        state.update(certain=z(torch.bool), exact=z(torch.bool), cause=z(torch.int32), pixel_values=None)
-        res = dict(embedding=st['embedding'], topk_indices=st['topk_indices'][:, :k], topk_values=st['topk_values'][:, :k],
-                   preds_LLH=st['preds_LLH'], preds_geocell=st['preds_geocell'], index=z(torch.int64), certain=z(torch.bool),
-                   exact=z(torch.bool), cause=z(torch.int32), queued=[0] * self.comm.world_size, step=self.n_submitted, meta=meta, state=state)
-        if self.refiner is not None:
-            res['refined_LLH'], res['refined_geocell'] = z(torch.float32, 2), z(torch.int64)
-            state.update(refined_LLH=res['refined_LLH'], refined_geocell=res['refined_geocell'], refine_tol=z(torch.float32),
-                         refine_code=z(torch.int32))
-        return res
+    def _result(self, ring: dict, local: dict, b: int, queued: List[int], step: int, meta) -> dict:
+        """The dict handed out: `ring` (the gathered rows of every ring column) with `topk_*` cut to num_candidates, plus `state`:
+        this rank's rows of all columns but the index, `topk_*` whole, in the form `package` takes."""
+        own = slice(self.comm.rank * b, (self.comm.rank + 1) * b)
+        state = {k: v[own] for k, v in ring.items() if k != 'index'}
+        state.update(local, pixel_values=None)
+        k = int(getattr(self.model, 'num_candidates', ring['topk_indices'].shape[1]))
+        return dict(ring, topk_indices=ring['topk_indices'][:, :k], topk_values=ring['topk_values'][:, :k], queued=queued, step=step,
+                    meta=meta, state=state)
+
+    def _empty_result(self, st: dict, meta) -> dict:
+        """An empty batch: the head's (empty) outputs as they are -- every 'state' column the state has -- and no rows of the others."""
+        got = {'ring': {}, 'local': {}}
+        for c in COLUMNS:
+            if c.src == 'state' and c.name in st:
+                got[c.where][c.name] = st[c.name]
+            elif c.src != 'state' and self._carries(c, st):
+                got[c.where][c.name] = self._zeros(c, 0, st)
+        return self._result(got['ring'], got['local'], 0, [0] * self.comm.world_size, self.n_submitted, meta)
 
     def _learn(self, upto_step: int):
         last_known = None
@@ -366,27 +395,24 @@ class DeferredExact:
         sx = model.exact_rows(seg)                                # exact encoder + head + tolerance at the exact tier's floor
         thr_x = model.certainty.threshold(exact=True)
         rtol = rcode = None
+        new = dict(sx)                                            # the patched columns' new rows
         if self.refiner is not None:
-            llh_x, cell_x, rtol, rcode, _ = self.refiner.forward_certain(sx['embedding'], sx['preds_LLH'], sx['topk_indices'],
-                                                                         sx['topk_values'], model.cell_layer.weight.data,
-                                                                         model.wstats(True), None)
-            sx['refine_tol'], sx['refine_code'] = rtol, rcode
+            new['refined_LLH'], new['refined_geocell'], rtol, rcode, _ = self.refiner.forward_certain(
+                sx['embedding'], sx['preds_LLH'], sx['topk_indices'], sx['topk_values'], model.cell_layer.weight.data, model.wstats(True), None)
+            new.update(refine_tol=rtol, refine_code=rcode)
         certain_x, _, _ = ops.requeue_append(sx['tol'], rtol, rcode, thr_x, False)
+        new.update(certain=certain_x.view(torch.bool), exact=self._true_cap[:n_pad])
         dst = ops.requeue_take(self.slot_dst, head, n_own, n_pad)
-        cols = [('embedding', sx['embedding']), ('topk_indices', sx['topk_indices']), ('topk_values', sx['topk_values']),
-                ('preds_LLH', sx['preds_LLH']), ('preds_geocell', sx['preds_geocell']), ('certain', certain_x.view(torch.bool)),
-                ('exact', self._true_cap[:n_pad])]
-        if self.refiner is not None:
-            cols += [('refined_LLH', llh_x), ('refined_geocell', cell_x)]
-        srcs = [c for _, c in cols] + [dst]
+        cols = [k for k in self.ring if k not in ('index', 'cause')]      # (a row keeps its place and the cause of its re-encoding)
+        srcs = [new[k] for k in cols] + [dst]
         if W > 1 or getattr(comm, 'force_rccl', False):
             srcs = comm.gather_many(srcs)                         # every rank patches every rank's rows of its copy of the ring
         dst_all = srcs[-1]
-        for (k, _), src in zip(cols, srcs[:-1]):
+        for k, src in zip(cols, srcs[:-1]):
             ops.scatter_rows(src, dst_all, self.ring[k])
         for k, buf in self.local.items():                         # this rank's own reports (margin, tolerances, logits)
-            if k in sx:
-                ops.scatter_rows(sx[k], dst, buf, remap=(self.WB, self.B, rank * self.B))
+            if k in new:
+                ops.scatter_rows(new[k], dst, buf, remap=(self.WB, self.B, rank * self.B))
         for r in range(W):
             self.flushed[r] += lens[r]
         self._mark(span)
@@ -404,28 +430,12 @@ class DeferredExact:
     def _emit(self, rec: dict) -> dict:
         if 'ready' in rec:
             return rec['ready']
-        comm = self.comm
-        rank, b = comm.rank, rec['b']
+        b = rec['b']
         gbase, lbase = rec['slot'] * self.WB, rec['slot'] * self.B
-        n = comm.world_size * b
-        ring = self.ring
-        res = {k: ring[k][gbase:gbase + n].clone() for k in ring}
-        k = int(getattr(self.model, 'num_candidates', res['topk_indices'].shape[1]))
-        own = slice(rank * b, (rank + 1) * b)
-        state = {'embedding': res['embedding'][own], 'topk_values': res['topk_values'][own], 'topk_indices': res['topk_indices'][own],
-                 'preds_LLH': res['preds_LLH'][own], 'preds_geocell': res['preds_geocell'][own],
-                 'certain': res['certain'][own], 'exact': res['exact'][own], 'cause': res['cause'][own], 'pixel_values': None}
-        if self.refiner is not None:
-            state['refined_LLH'], state['refined_geocell'] = res['refined_LLH'][own], res['refined_geocell'][own]
-        for kk, buf in self.local.items():
-            state[kk] = buf[lbase:lbase + b].clone()
-        res['topk_indices'] = res['topk_indices'][:, :k]
-        res['topk_values'] = res['topk_values'][:, :k]
-        prev = self._prev_appended
-        res['queued'] = [a - p for a, p in zip(rec['appended'], prev)]      # rows each rank sent to the exact tier in this step
+        queued = [a - p for a, p in zip(rec['appended'], self._prev_appended)]   # rows each rank sent to the exact tier in this step
         self._prev_appended = rec['appended']
-        res['step'], res['meta'], res['state'] = rec['step'], rec['meta'], state
-        return res
+        return self._result({k: v[gbase:gbase + self.comm.world_size * b].clone() for k, v in self.ring.items()},
+                            {k: v[lbase:lbase + b].clone() for k, v in self.local.items()}, b, queued, rec['step'], rec['meta'])
 
     def check_nothing_dropped(self) -> int:
         """Rows that did not fit the queue since creation (host synchronisation).  The queue is sized so that this is 0."""

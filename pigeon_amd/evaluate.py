@@ -15,12 +15,14 @@ import numpy as np
 import torch
 
 from .config import DECAY_CONSTANT, EVAL_BATCH_SIZE_PER_GPU
+from .deferred import DeferredExact, as_model_output
 from .distributed import Communicator
 from .geo_utils import haversine_np
 from .proto_refiner import ProtoRefiner, load_refiner_cache
 from .super_guessr import SuperGuessr
 
 logger = logging.getLogger('train')
+LABEL_KEYS = ('labels', 'labels_clf', 'labels_multi_task', 'labels_climate', 'labels_month')      # of a batch, in `package`'s order
 
 
 def percentage_within_radius(distances: np.ndarray, km: float) -> float:
@@ -131,11 +133,8 @@ def certain_forward(model: SuperGuessr, refiner: Optional[ProtoRefiner], pixel_v
     caller need not run the refiner again; multi-task models: aux_tol (B,) f32 the tolerance of the climate and month argmaxes,
     aux_code (B,) i32 which class sets it -- `head_tol` is already the minimum over the geocell, climate and month decisions)."""
     res = model.engine(refiner).submit(pixel_values, embedding)[0]
-    st = dict(res['state'])
-    if getattr(model, 'multi_task', False):
-        out = model.package(st, labels, labels_clf, labels_multi_task, labels_climate, labels_month)
-    else:
-        out = model.package(st, labels, labels_clf)
+    out = as_model_output(model, res, labels, labels_clf, labels_multi_task, labels_climate, labels_month)
+    st = res['state']
     info = dict(certain=st['certain'], cause=st['cause'], head_tol=st['tol'], refine_tol=st.get('refine_tol'),
                 refine_code=st.get('refine_code'), boundary_checked=model.engine(refiner).boundary_checked if refiner is not None else None,
                 reencoded=torch.nonzero(st['exact']).flatten(), refined_LLH=st.get('refined_LLH'),
@@ -174,7 +173,6 @@ def evaluate_model(model: SuperGuessr, dataset, metrics: Optional[Callable] = No
     # (:114-140).  Here a batch's rows that the 16-bit encoder cannot settle are queued on the device and re-encoded by the exact
     # encoder 40+ images at a time (pigeon_amd.deferred): a batch is appended when all its rows are settled -- a few iterations
     # late, in order -- and `flush()` settles the rest after the loop.  No host synchronisation per batch.
-    from .deferred import DeferredExact
     engine = DeferredExact(model, refiner)
 
     def collect(done):
@@ -182,11 +180,7 @@ def evaluate_model(model: SuperGuessr, dataset, metrics: Optional[Callable] = No
         nonlocal combined_loss, n_seen
         for res in done:
             meta = res['meta']
-            if multi_task:
-                outputs = model.package(dict(res['state']), meta.get('labels'), meta.get('labels_clf'), meta.get('labels_multi_task'),
-                                        meta.get('labels_climate'), meta.get('labels_month'))
-            else:
-                outputs = model.package(dict(res['state']), meta.get('labels'), meta.get('labels_clf'))
+            outputs = as_model_output(model, res, *(meta.get(k) for k in LABEL_KEYS))
             if outputs.loss_clf is not None:
                 combined_loss = combined_loss + outputs.loss_clf.detach() * meta['n_keys']   # :81-82 (`len(data)` as the reference)
             # :84-95.  The reference decides with `outputs.loss_reg > 0` -- a comparison of a device value on the host, i.e. a
@@ -211,9 +205,7 @@ def evaluate_model(model: SuperGuessr, dataset, metrics: Optional[Callable] = No
     with torch.no_grad():
         for data in eval_data:
             # :80 `model(**data)` and :98 `refiner(...)`, with what the refiner will consume checked as well
-            keep = {'labels': data.get('labels'), 'labels_clf': data.get('labels_clf'), 'n_keys': len(data),
-                    'labels_multi_task': data.get('labels_multi_task'), 'labels_climate': data.get('labels_climate'),
-                    'labels_month': data.get('labels_month')}
+            keep = dict({k: data.get(k) for k in LABEL_KEYS}, n_keys=len(data))
             collect(engine.submit(data.get('pixel_values'), data.get('embedding'), meta=keep))
         collect(engine.flush())
     dropped = engine.check_nothing_dropped()
@@ -379,7 +371,6 @@ class PanoramaPipeline:
 
     def __init__(self, model: SuperGuessr, refiner: Optional[ProtoRefiner], comm: Optional[Communicator] = None,
                  min_flush: Optional[int] = None, max_lag: int = 12, ops=None, pass_quantum: Optional[int] = None):
-        from .deferred import DeferredExact
         self.model, self.refiner = model, refiner
         self.comm = comm or Communicator()
         self.engine = DeferredExact(model, refiner, self.comm, ops=ops, min_flush=min_flush, max_lag=max_lag,

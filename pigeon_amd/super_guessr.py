@@ -21,7 +21,7 @@ from torch import nn, Tensor
 from torch.nn.parameter import Parameter
 
 from . import hip_ops
-from .certainty import CalibrationError, Certainty, require_fingerprint
+from .certainty import SAFETY, CalibrationError, Certainty, require_fingerprint
 from .geo_utils import haversine_matrix, smooth_labels
 from .clip_embedder import HipCLIPVisionModel
 from .config import CLIP_EMBED_DIM, GEOCELL_PATH, GEOCELL_PATH_YFCC
@@ -567,7 +567,7 @@ class SuperGuessr(nn.Module):
                 resid = new.stats.get('image_residual_rms')
                 if resid is None or not (float(resid) > 0.0):
                     raise CalibrationError(f'{path!r}: no image_residual_rms in the file\'s statistics -- cannot set embedding_rel_tol')
-                tol = 1.1 * float(resid)                   # the safety factor `Certainty.calibrate` puts on rel_tol
+                tol = SAFETY * float(resid)                # the safety factor `Certainty.calibrate` puts on rel_tol
             if self._embedding_rel_tol0 is None:
                 self._embedding_rel_tol0 = (self._embedding_rel_tol,)
             self.embedding_rel_tol = float(tol)

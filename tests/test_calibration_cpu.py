@@ -319,6 +319,109 @@ def test_clip_embedding_takes_the_same_vector(geocells, tmp_path):
         CLIPEmbedding("unused", device="cpu", clip_model=_Tower(FP_A)).save_calibration(str(tmp_path / "none.npz"))
 
 
+# ------------------------------------------------------------------------------------------------ the embedder's judgement
+_CASES = ((32, 3e-4), (32, 1e-6), (9, 3e-4), (7, 3e-4), (1, 3e-4))        # (images, scale of the systematic part); a bias is kept in 0 and 2
+# What `CLIPEmbedding.save_calibration` wrote for the five cases BEFORE the embedder held a `Certainty` (commit 070f2c5, the same draws
+# through `_check_contract` on the CPU with `_to_device_pixels` patched to the identity): sum of the bias in fp64 (None: no vector),
+# force_exact, rel_tol, stats['image_residual_rms'].  Cases 1, 3, 4 take both figures from `image_rel_err`, not from `calibrate`.
+_PARENT_ROWS = ((-0.0002794648283028778, False, 5.642319847538602e-05, 5.129381679580547e-05),
+                (None, False, 5.506579982466065e-05, 5.005981802241877e-05),
+                (0.000738847422000255, False, 6.034937759977766e-05, 5.486307054525241e-05),
+                (None, False, 0.0003260129655245692, 0.0002963754232041538),
+                (None, False, 0.0003382560011232272, 0.00030750545556657016))
+
+
+@pytest.fixture(scope="module")
+def judged():
+    """The five scripted (fast, exact) pairs, each through a fresh embedder's judgement -> [(embedder, fast, exact)]."""
+    torch.manual_seed(0)
+    out = []
+    for n, scale in _CASES:
+        exact = torch.randn(n, 1024)
+        beta = torch.randn(1024) / 32 * scale
+        fast = exact + exact.norm(dim=1, keepdim=True) * (beta + torch.randn(n, 1024) / 32 * 5e-5)
+        e = CLIPEmbedding("unused", device="cpu", clip_model=_Tower(FP_A), contract_guard="exact")
+        assert e.certainty.debias and e.guard_stats is None and e.bias is None and e.force_exact is False
+        e._judge(fast, exact)
+        out.append((e, fast, exact))
+    return out
+
+
+def _restated(fast, exact):
+    """The guard's arithmetic for one image per sample, in independent torch expressions -> (bias or None, expected guard_stats)."""
+    n = fast.shape[0]
+    err = (fast - exact).norm(dim=1) / exact.norm(dim=1)
+    st = {"images": n, "image_rel_err": float((fast - exact).norm() / exact.norm()), "worst_image_rel_err": float(err.max()), "contract": 1e-3}
+    bias = None
+    if n >= 8:
+        rel = (fast - exact) / exact.norm(dim=1, keepdim=True)
+        held = fast[1::2] - fast[1::2].norm(dim=1, keepdim=True) * rel[0::2].mean(dim=0)          # what pg_embedding_debias would return
+        left = float(((held - exact[1::2]).norm(dim=1) / exact[1::2].norm(dim=1)).pow(2).mean().sqrt())
+        st["bias_norm"], st["residual_rms"] = float(rel.mean(dim=0).norm()), left
+        if left < 0.9 * float(err.pow(2).mean().sqrt()):
+            bias = rel.mean(dim=0)
+    st["debias"] = bias is not None
+    st["outside"] = st["image_rel_err"] > 0.85e-3 or st["worst_image_rel_err"] > 0.95e-3
+    return bias, st
+
+
+def test_embedder_judgement_is_certainty_calibrate(judged):
+    kept = []
+    for (e, fast, exact), (n, _) in zip(judged, _CASES):
+        bias, want = _restated(fast, exact)
+        kept.append(bias is not None)
+        assert (e.bias is None) == (bias is None) and (bias is None or torch.equal(e.bias, bias)), n
+        assert e.guard_stats == want, n                               # every figure with ==, and exactly these keys
+        assert ("bias_norm" in e.guard_stats) == ("residual_rms" in e.guard_stats) == (n >= 8)
+        assert e.force_exact is False and e.calibration_header is None
+        # the same object is what `Certainty.calibrate` leaves behind
+        c = Certainty(debias=True)
+        cs = c.calibrate(fast, exact, fast_images=fast, exact_images=exact)
+        assert (c.bias is None) == (bias is None) and (bias is None or torch.equal(c.bias, bias)) and c.force_exact is e.force_exact
+        assert cs["image_rel_err"] == want["image_rel_err"] and cs["worst_image_rel_err"] == want["worst_image_rel_err"]
+        assert e.certainty.bias is e.bias and e.certainty.bias_on(torch.device("cpu")) is e.bias
+    assert kept == [True, False, True, False, False]
+    # outside the contract: the verdict, and what 'raise' does with it
+    exact = judged[0][2]
+    fast = exact * (1 + 9e-4)
+    out = CLIPEmbedding("unused", device="cpu", clip_model=_Tower(FP_A), contract_guard="exact")
+    assert out._judge(fast, exact)["outside"] is True and out.force_exact is True and out.guard_stats["outside"] is True
+    strict = CLIPEmbedding("unused", device="cpu", clip_model=_Tower(FP_A), contract_guard="raise")
+    with pytest.raises(RuntimeError, match="outside the 1e-3 embedding contract"):
+        strict._judge(fast, exact)
+    assert strict.guard_stats["outside"] is True and strict.force_exact is False
+
+
+def test_rank_combination():
+    from pigeon_amd.certainty import combine_ranks, outside_contract
+    g = torch.Generator().manual_seed(4)
+    v = [torch.randn(1024, generator=g) * 1e-5 for _ in range(3)]
+    overall, worst, bias = combine_ranks([(3e-4, 9.6e-4, v[0]), (5e-4, 4e-4, v[1]), (2e-4, 3e-4, v[2])])
+    assert (overall, worst) == (5e-4, 9.6e-4) and torch.equal(bias, torch.stack(v).mean(dim=0))
+    assert outside_contract(overall, worst) and not outside_contract(5e-4, 4e-4) and outside_contract(8.6e-4, 4e-4)
+    for missing in range(3):                                          # one rank kept none: none for the job
+        every = [(1e-4, 2e-4, None if r == missing else v[r]) for r in range(3)]
+        assert combine_ranks(every) == (1e-4, 2e-4, None)
+    assert combine_ranks([(1e-4, 2e-4, None)] * 3)[2] is None
+
+
+def test_embedder_saves_what_it_always_saved(judged, tmp_path):
+    for i, ((e, fast, exact), row) in enumerate(zip(judged, _PARENT_ROWS)):
+        bias, st = _restated(fast, exact)
+        sd, h = Certainty.load(e.save_calibration(str(tmp_path / f"c{i}.npz")))
+        assert h["panels"] == 1 and h["samples"] == fast.shape[0] and h["fingerprint"] == FP_A
+        assert (sd["bias"] is None) == (bias is None) and (bias is None or torch.equal(sd["bias"], bias)) and sd["drift"] is None
+        # the embedder's own rule, with ==: the held-out residual after a kept bias, else the whole batch's raw error
+        resid = st["residual_rms"] if bias is not None else st["image_rel_err"]
+        assert sd["stats"]["image_residual_rms"] == resid and sd["rel_tol"] == max(1.1 * resid, 1e-5) and sd["force_exact"] is False
+        # ... and the recorded rows (approx: a sum over 32k elements may be split differently on another machine; the two rules differ by 2 %)
+        got = (None if sd["bias"] is None else float(sd["bias"].double().sum()), sd["force_exact"], sd["rel_tol"], sd["stats"]["image_residual_rms"])
+        assert got == pytest.approx(row, rel=1e-6), i
+        # every member of the file's statistics: the guard's scalars and the six the file adds
+        assert sd["stats"] == dict(st, samples=st["images"], image_residual_rms=resid, rel_tol=sd["rel_tol"], kappa=3.6, force_exact=False)
+        assert e.save_calibration(str(tmp_path / "again.npz")) and Certainty.load(str(tmp_path / "again.npz"))[0]["stats"] == sd["stats"]
+
+
 # ------------------------------------------------------------------------------------------------ command lines
 def test_command_lines_accept_calibration(tmp_path, monkeypatch, capsys):
     import importlib

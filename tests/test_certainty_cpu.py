@@ -462,3 +462,68 @@ def test_deferred_engine_pixel_dtype_change_settles_and_restarts_the_queue():
     order += [res["meta"] for res in eng.flush()]
     assert order == [0, 1, 2, 3] and m.calls == [("exact", 2), ("exact", 2)] and eng.q_pixels.dtype == torch.float16
     assert eng.check_nothing_dropped() == 0
+
+
+# ---- what DeferredExact hands out: keys, dtypes and shapes, as a literal table (the scripted tests above check the values) --------
+_B, _K, _KX, _CELLS = 3, 3, 7, 11          # rows of the step; ScriptedModel: num_candidates, k + extra candidates, cells
+_RING = {"embedding": ("float32", (4, 8)), "topk_values": ("float32", (_K,)), "topk_indices": ("int64", (_K,)), "preds_LLH": ("float64", (2,)),
+         "preds_geocell": ("int64", ()), "index": ("int64", ()), "certain": ("bool", ()), "cause": ("int32", ()), "exact": ("bool", ())}
+_RING_REFINER = {"refined_LLH": ("float32", (2,)), "refined_geocell": ("int64", ())}
+_STATE = {"embedding": ("float32", (4, 8)), "topk_values": ("float32", (_KX,)), "topk_indices": ("int64", (_KX,)), "preds_LLH": ("float64", (2,)),
+          "preds_geocell": ("int64", ()), "certain": ("bool", ()), "cause": ("int32", ()), "exact": ("bool", ()),
+          "tol": ("float32", ()), "margin": ("float32", ()), "sens": ("float32", ())}
+_STATE_REFINER = dict(_RING_REFINER, refine_tol=("float32", ()), refine_code=("int32", ()))
+_STATE_LOGITS = {"logits": ("float32", (_CELLS,))}
+_STATE_AUX = {"aux_preds": ("float32", (10,)), "aux_cls": ("int64", (2,)), "aux_tol": ("float32", ()), "aux_code": ("int32", ())}
+
+
+def _layout(d):
+    """{key: (dtype, shape after the row dimension)} of the tensors, {key: type} of the rest; the rows are checked by the caller."""
+    return {k: (str(v.dtype).replace("torch.", ""), tuple(v.shape[1:])) if torch.is_tensor(v) else type(v) for k, v in d.items() if k != "state"}
+
+
+@pytest.mark.parametrize("refiner,keep_logits,aux", [(True, True, False), (True, False, False), (False, True, False), (False, False, False),
+                                                     (True, True, True)])
+def test_deferred_engine_result_layout(refiner, keep_logits, aux):
+    """One settled step with a re-encoded row, then an empty batch: the key sets, dtypes and shapes of the result and of its `state`
+    (`topk_*` cut to num_candidates in the result, whole in the state), copies of the engine's storage, not views."""
+    from _scripted import ScriptedModel, ScriptedRefiner, make_pixels
+    from oracle import requeue_oracle
+    from pigeon_amd.deferred import AUX_KEYS, DeferredExact
+    assert AUX_KEYS == tuple(_STATE_AUX)
+
+    class Aux(ScriptedModel):
+        def _aux(self, st):
+            for k, (dt, tail) in _STATE_AUX.items():
+                st[k] = torch.zeros((st["tol"].shape[0],) + tail, dtype=getattr(torch, dt))
+            return st
+
+        def encode_head(self, pixel_values=None, embedding=None):
+            return self._aux(super().encode_head(pixel_values, embedding))
+
+        def exact_rows(self, pixel_rows):
+            return self._aux(super().exact_rows(pixel_rows))
+
+    eng = DeferredExact(Aux() if aux else ScriptedModel(), ScriptedRefiner() if refiner else None, ops=requeue_oracle, immediate=True,
+                        keep_logits=keep_logits)
+    (full,) = eng.submit(make_pixels([1, 0, 1], seed=1), meta="m")
+    (empty,) = eng.submit(make_pixels([], seed=2))
+    (empty_first,) = DeferredExact(Aux() if aux else ScriptedModel(), ScriptedRefiner() if refiner else None, ops=requeue_oracle,
+                                   immediate=True, keep_logits=keep_logits).submit(make_pixels([], seed=2))      # before any storage exists
+    assert full["exact"].tolist() == [False, True, False] and full["queued"] == [1] and empty["queued"] == [0]
+    assert (full["step"], full["meta"], empty["step"], empty["meta"], empty_first["step"]) == (0, "m", 1, None, 0)
+    rest = {"queued": list, "step": int, "meta": str}
+    want_res = dict(_RING, **(_RING_REFINER if refiner else {}))
+    want_state = dict(_STATE, pixel_values=type(None), **(_STATE_REFINER if refiner else {}), **(_STATE_AUX if aux else {}))
+    assert _layout(full) == dict(want_res, **rest)
+    assert _layout(full["state"]) == dict(want_state, **(_STATE_LOGITS if keep_logits else {}))
+    # an empty batch carries the head's (empty) outputs as they are: the logits also when the ring keeps none
+    for e in (empty, empty_first):
+        assert _layout(e) == dict(want_res, **dict(rest, meta=type(None)))
+        assert _layout(e["state"]) == dict(want_state, **_STATE_LOGITS)
+    for res, rows in ((full, _B), (empty, 0), (empty_first, 0)):
+        for d in (res, res["state"]):
+            assert all(v.shape[0] == rows for v in d.values() if torch.is_tensor(v))
+    held = {t.untyped_storage().data_ptr() for t in list(eng.ring.values()) + list(eng.local.values())}
+    for d in (full, full["state"]):
+        assert not any(v.untyped_storage().data_ptr() in held for v in d.values() if torch.is_tensor(v))

@@ -193,6 +193,36 @@ def test_both_paths_subtract_the_files_vector(env, vit2, geocells, tmp_path):
     assert torch.equal(_guessr(env, vit2, geocells, exact_top1=False, calibration=path)(pixel_values=px).embedding, out.embedding)
 
 
+def test_embedder_guard_is_certainty_calibrate(env, geocells, tmp_path):
+    """The guard of `CLIPEmbedding` at its default, on a 2-layer tower and 16 images (the smallest shape with an even / odd split of 8
+    images or more and a bias to subtract): what its first forward measures is what `Certainty.calibrate` measures on the same two
+    encoders; the file it saves sets a precomputed-embedding model's tolerance; a second embedder given the file measures nothing
+    and returns the same bits."""
+    from pigeon_amd.certainty import SAFETY, Certainty
+    from pigeon_amd.clip_embedder import CLIPEmbedding, HipCLIPVisionModel
+    from pigeon_amd.super_guessr import SuperGuessr
+    vit = HipCLIPVisionModel(seed=5, layers=2).to(DEV)
+    px = env["syn"].make_pixels(16, seed=21).to(DEV)
+    e = CLIPEmbedding("unused", device=DEV, clip_model=vit)
+    first = e(px)
+    st = e.guard_stats
+    assert st["images"] == 16 and "bias_norm" in st and "residual_rms" in st and "from_file" not in st
+    fast, exact = vit.embed(px), vit.embed_precise(px)
+    c = Certainty(debias=True)
+    cs = c.calibrate(fast, exact, fast_images=fast, exact_images=exact)
+    assert (c.bias is None) == (e.bias is None) and (c.bias is None or torch.equal(c.bias, e.bias))
+    assert c.force_exact is e.force_exact and cs["image_rel_err"] == st["image_rel_err"] and st["debias"] == (e.bias is not None)
+    print(f"   guard on the 2-layer tower: {st}")
+    assert not e.force_exact                                                            # (this tower is inside the contract)
+    assert torch.equal(first, fast if e.bias is None else env["ops"].embedding_debias(fast.clone(), e.bias))
+    path = e.save_calibration(str(tmp_path / "e.npz"))
+    resid = Certainty.load(path)[0]["stats"]["image_residual_rms"]
+    m = SuperGuessr(None, panorama=False, freeze_base=True, geocell_path=geocells, calibration=path)
+    assert SAFETY == 1.1 and m.embedding_rel_tol == 1.1 * resid and resid > 0
+    e2 = CLIPEmbedding("unused", device=DEV, clip_model=vit, calibration=path)
+    assert torch.equal(e2(px), first) and e2.guard_stats["from_file"] == path and (e2.bias is None) == (e.bias is None)
+
+
 # ------------------------------------------------------------------------------------------------ 4. two objects, one file, the same bits
 @pytest.fixture(scope="module")
 def vit24(env):
