@@ -44,7 +44,8 @@ extern "C" {
                               * 7: pg_vit_precise_plan, pg_op_x3_im2col, pg_op_sum_parts, pg_op_preln, pg_op_attention_x3;
                               * 7 (+ pg_aux_heads_forward, additive; + pg_fingerprint, pg_vit_fingerprint, additive;
                               *    + pg_prep_ragged_plan / _create / _destroy / _forward and pg_prep_item, additive;
-                              *    + pg_haversine_blocks, pg_optics_graph, pg_optics_plan, pg_tune_optics_lds_points, additive) */
+                              *    + pg_haversine_blocks, pg_optics_graph, pg_optics_plan, pg_tune_optics_lds_points, additive;
+                              *    + pg_region_locate, pg_region_classify, pg_region_nearest, pg_region_plan, pg_tune_region_wave_edges, additive) */
 
 const char* pg_last_error(void);
 int pg_abi_version(void);
@@ -517,6 +518,59 @@ int pg_optics_graph(const double* dist, const int64_t* cell_off, const int64_t* 
 int pg_optics_plan(int64_t n, int min_samples, int32_t out[4]);
 /* Lowers pg_optics_plan's out[2] (1 .. its default; 0 restores the default) so that tests reach form 1 at small n.  Process-wide. */
 int pg_tune_optics_lds_points(int max_points);
+
+/* ------------------------------------------------------------------------------------------------
+ * Exact point-in-region lookup (csrc/regions.hip): the device half of `Country_accuracy` and of the geocell labels.
+ * Replaces: find_country / country_accuracy (reference evaluation/metrics.py:56-88: geopandas sindex `covered_by`, else `nearest`;
+ * shapely `contains`) and generate_cell_labels (preprocessing/dataset_preprocessing.py:60-94, the same lookup on the geocell table).
+ * A region is a set of rings under the even-odd rule (multipolygons with holes: a point in a hole is outside, a point on any ring is on
+ * the boundary).  The bank is plain CSR; ring closure is stored (first vertex == last vertex), boxes are [min lng, min lat, max lng,
+ * max lat].  The two offset arrays exist twice: on the device for the kernels, and on the HOST, where every call checks them before
+ * anything is launched (ascending, inside the arrays, rings of at least 2 vertices: PG_EINVAL with a message naming the offender);
+ * the kernels additionally clamp every offset they read to the counts below.
+ * ------------------------------------------------------------------------------------------------ */
+typedef struct pg_region_bank {
+    const int64_t* region_off;       /* DEVICE (num_regions + 1): region g owns rings region_off[g] .. region_off[g+1] */
+    const int64_t* ring_off;         /* DEVICE (num_rings + 1): ring r owns vertices ring_off[r] .. ring_off[r+1] */
+    const double*  xy;               /* DEVICE (num_vertices, 2) fp64 [lng, lat], 16-byte aligned */
+    const double*  ring_bbox;        /* DEVICE (num_rings, 4) fp64 */
+    const double*  region_bbox;      /* DEVICE (num_regions, 4) fp64 */
+    const int64_t* region_off_host;  /* HOST copy of region_off */
+    const int64_t* ring_off_host;    /* HOST copy of ring_off */
+    int64_t num_regions;
+    int64_t num_rings;
+    int64_t num_vertices;
+} pg_region_bank;
+/* States of a (point, region) pair.  The device never guesses: INSIDE (strictly interior) and OUTSIDE are certain; AMBIGUOUS is every
+ * pair its fp64 filter cannot certify -- all points on a ring among them -- which the host settles in rational arithmetic
+ * (pigeon_amd/regions.py exact_state).  The filter is stated in csrc/regions.hip's header. */
+#define PG_REGION_OUTSIDE   0
+#define PG_REGION_INSIDE    1
+#define PG_REGION_AMBIGUOUS 2
+/* pts DEVICE (N,2) fp64 [lng, lat]; start HOST (N) int32 or NULL (= all 0), 0 <= start[i] <= num_regions; cover DEVICE (N) int32 out,
+ * state DEVICE (N) uint8 out: the lowest region index >= start[i] whose state is not OUTSIDE, and that state; -1 / 0 if there is none.
+ * Asynchronous on `stream`; with a `start` array the call copies it to the device itself and SYNCHRONISES the stream before returning.
+ * N = 0 and num_regions = 0 are no-ops (the latter fills cover with -1, state with 0). */
+int pg_region_locate(const pg_region_bank* bank, const double* pts, const int32_t* start, int64_t N, int32_t* cover, uint8_t* state,
+                     void* stream);
+/* The state of point i against region[i]: region HOST (N) int32, -1 <= region[i] < num_regions, -1 gives OUTSIDE; state DEVICE (N)
+ * uint8 out.  Copies `region` to the device and SYNCHRONISES the stream before returning. */
+int pg_region_classify(const pg_region_bank* bank, const double* pts, const int32_t* region, int64_t N, uint8_t* state, void* stream);
+/* The minimum point-to-segment distance (planar, in degrees) over all edges of all regions and the region that has it, ties to the
+ * lower index: idx DEVICE (N) int32 out (-1 when the bank has no edge), dist DEVICE (N) fp64 out (+inf then).  The fp64 operations are
+ * stated in csrc/regions.hip's header.  Asynchronous on `stream`. */
+int pg_region_nearest(const pg_region_bank* bank, const double* pts, int64_t N, int32_t* idx, double* dist, void* stream);
+/* How the three calls map points onto the device for this bank under the current knob (host arithmetic on the bank's host arrays, no
+ * GPU; the device pointers may be NULL; the same refusals):
+ *   out[0]  0 = one wave per point (banks of small rings: geocells), 1 = one workgroup of four waves per point (large rings: countries)
+ *   out[1]  threads that share a point's edges (64 / 256)
+ *   out[2]  edges of the bank's largest ring
+ *   out[3]  the largest out[2] that still gets form 0
+ * Results do not depend on the form. */
+int pg_region_plan(const pg_region_bank* bank, int32_t out[4]);
+/* Sets pg_region_plan's out[3] (0: every bank takes form 1; INT32_MAX: every bank form 0; negative restores the default, 128) so that
+ * tests reach both forms with any bank.  Process-wide. */
+int pg_tune_region_wave_edges(int max_edges);
 
 /* ------------------------------------------------------------------------------------------------
  * Building-block ops (exported so the parity tests can check every kernel in isolation through the ABI).

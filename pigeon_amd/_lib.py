@@ -32,6 +32,13 @@ class Bank(C.Structure):
                 ("num_cells", C.c_int64), ("num_protos", C.c_int64), ("num_train", C.c_int64)]
 
 
+class RegionBankStruct(C.Structure):
+    """pg_region_bank (include/pigeon_hip.h): five device arrays, the host copies of the two offset arrays, three counts."""
+    _fields_ = [("region_off", C.c_void_p), ("ring_off", C.c_void_p), ("xy", C.c_void_p), ("ring_bbox", C.c_void_p),
+                ("region_bbox", C.c_void_p), ("region_off_host", C.c_void_p), ("ring_off_host", C.c_void_p),
+                ("num_regions", C.c_int64), ("num_rings", C.c_int64), ("num_vertices", C.c_int64)]
+
+
 class PrepItem(C.Structure):
     """pg_prep_item (include/pigeon_hip.h): one image of a ragged preprocessing batch, PREP_ITEM_BYTES bytes."""
     _fields_ = [("src_off", C.c_uint64), ("in_h", C.c_int32), ("in_w", C.c_int32), ("new_h", C.c_int32), ("new_w", C.c_int32),
@@ -102,6 +109,11 @@ SIGNATURES = {
     "pg_optics_graph": (_I, [_P, _P, _P, _I, _I, _P, _P, _P, _P, _P]),
     "pg_optics_plan": (_I, [_I64, _I, C.POINTER(C.c_int32)]),
     "pg_tune_optics_lds_points": (_I, [_I]),
+    "pg_region_locate": (_I, [C.POINTER(RegionBankStruct), _P, _P, _I64, _P, _P, _P]),
+    "pg_region_classify": (_I, [C.POINTER(RegionBankStruct), _P, _P, _I64, _P, _P]),
+    "pg_region_nearest": (_I, [C.POINTER(RegionBankStruct), _P, _I64, _P, _P, _P]),
+    "pg_region_plan": (_I, [C.POINTER(RegionBankStruct), C.POINTER(C.c_int32)]),
+    "pg_tune_region_wave_edges": (_I, [_I]),
     "pg_head_forward": (_I, [_P, _I, _I, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P]),
     "pg_head_margin": (_I, [_P, _I, _I, _P, _I, _P, _P, _P, _P, _P]),
     "pg_head_certainty": (_I, [_P, _I, _I, _P, _I, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P]),

@@ -9,6 +9,9 @@ CLIP_EMBED_DIM = 1024
 GEOCELL_PATH = 'data/geocells_2203.csv'       # PIGEON
 GEOCELL_PATH_YFCC = 'data/geocells_yfcc.csv'  # PIGEOTTO
 
+# Country polygons of `Country_accuracy` (config.py:26)
+COUNTRY_PATH = 'data/geocells/countries.geojson'
+
 # Scaler of the six multi-task regression targets (config.py:39-40)
 SCALER_PATH = 'saved_models/scaler/regression.scaler'
 SCALER_PATH_YFCC = 'saved_models/scaler/regression_yfcc.scaler'

@@ -3,8 +3,9 @@ SuperGuessr + ProtoRefiner, `evaluate_model()` (training/train_eval_loop.py:35-1
 `model(**data)` -> `refiner(...)` -> collect.  Plus `PanoramaPipeline`, the data-parallel step the benchmark
 times: ViT + head on the local shard, ONE all-gather of embeddings / candidates, refinement.
 
-Out of scope here (SURVEY.md section 2 rows 14,17): TensorBoard writers, the geopandas country metric; the
-distance / geocell metrics of evaluation/metrics.py:89-181 are provided under the reference's keys.
+Out of scope here: TensorBoard writers.  The distance / geocell metrics of
+evaluation/metrics.py:89-181 are provided under the reference's keys; `Country_accuracy` (:56-88) when the country
+polygons are given (pigeon_amd/regions.py: exact point-in-region lookup on the GPU, no geopandas).
 """
 from __future__ import annotations
 
@@ -80,14 +81,16 @@ def _class_labels(labels) -> np.ndarray:
     return np.argmax(labels, axis=-1) if labels.ndim > 1 else labels          # (N, classes) one-hot / probabilities, or (N,) indices
 
 
-def compute_geoguessr_metrics(results, scaler=None) -> Dict[str, float]:
+def compute_geoguessr_metrics(results, scaler=None, countries=None) -> Dict[str, float]:
     """reference evaluation/metrics.py:138-199 on the 11-tuple evaluate_model builds (train_eval_loop.py:138-140):
     the km-error statistics, the Under_*_km fractions, the GeoGuessr score and the geocell (top-k) accuracies, under the
     reference's keys; with multi-task labels (`labels_mt` not None, :184-199) also `Climate_accuracy`, `Month_accuracy` (when there
     are month labels) and -- when a scaler is available: the `scaler` keyword, or the file config.SCALER_PATH(_YFCC) names -- the six
     `Mean_*_error` entries on the recovered regression values.  Climate labels may be class indices or the (N, 28) one-hot rows
-    the model's forward takes.  Left out: `Country_accuracy` (geopandas country polygons, absent here).
-    Host numpy on the collected predictions, as in the reference."""
+    the model's forward takes.  `Country_accuracy` (:178, find_country / country_accuracy :56-88) is added when `countries` is given:
+    a `pigeon_amd.regions.RegionBank` of the country polygons (`RegionBank.from_geojson(config.COUNTRY_PATH)`); the lookup runs on
+    the GPU (pg_region_locate / _classify / _nearest) and is exact.  Without `countries` the key is left out, as before.
+    Everything else is host numpy on the collected predictions, as in the reference."""
     predictions, cell_preds, preds_mt, preds_climate, preds_month, top5_geocells, labels, cell_labels, labels_mt, labels_climate, \
         labels_month = results
     cell_labels = np.asarray(cell_labels)
@@ -97,6 +100,9 @@ def compute_geoguessr_metrics(results, scaler=None) -> Dict[str, float]:
     eval_dict = {'Mean_km_error': np.mean(distances), 'Median_km_error': np.median(distances)}
     for km in (1, 5, 10, 25, 50, 100, 200, 750, 1000, 2500):
         eval_dict[f'Under_{km}_km'] = percentage_within_radius(distances, km)
+    if countries is not None:                                                  # :178
+        from .regions import country_accuracy
+        eval_dict['Country_accuracy'] = country_accuracy(np.asarray(predictions), np.asarray(labels), countries)
     eval_dict['Geoguessr_score'] = geoguessr_score(distances)
     eval_dict['Geocell_accuracy'] = float(np.mean(cell_labels == np.asarray(cell_preds)))      # sklearn accuracy_score
     eval_dict['Geocell_top5_accuracy'] = topk_geocell_accuracy(cell_labels, top5_geocells)
@@ -248,7 +254,7 @@ def evaluate_model(model: SuperGuessr, dataset, metrics: Optional[Callable] = No
 def evaluate(model: str, dataset, yfcc: bool, landmarks: bool, base_model=None, heading: bool = False,
              refine: bool = True, geocell_path: Optional[str] = None, proto_path: Optional[str] = None,
              dataset_path=None, bank=None, head_state: Optional[str] = None, multi_task: bool = False,
-             calibration: Optional[str] = None, embedding_rel_tol: Optional[float] = None):
+             calibration: Optional[str] = None, embedding_rel_tol: Optional[float] = None, country_path: Optional[str] = None):
     """reference evaluation/evaluate.py:10-85.
 
     `base_model`: as in the reference a STRING -- config.CLIP_MODEL for the pretrained tower, or the path of a checkpoint whose
@@ -270,9 +276,18 @@ def evaluate(model: str, dataset, yfcc: bool, landmarks: bool, base_model=None, 
     `embedding_rel_tol` (precomputed embeddings, `base_model=None`): the relative error the dataset's embeddings carry, passed to
     `SuperGuessr`.  None: the fast path's tolerance (1e-3, or what a calibration file says) -- right for files written by
     `run.py embed`; embeddings of the exact encoder or of the fp32 reference are declared with 5e-6.
+    `country_path`: the GeoJSON of country polygons behind `Country_accuracy` (reference evaluation/metrics.py:17).  None: the file
+    config.COUNTRY_PATH names if it exists, else the key is left out as before; a path given explicitly must exist.
     """
     import os
     from . import config as cfg
+    countries = None
+    if country_path is not None and not os.path.exists(country_path):
+        raise FileNotFoundError(f'evaluate: country polygons {country_path!r} do not exist')
+    if os.path.exists(country_path or cfg.COUNTRY_PATH):
+        from .regions import RegionBank
+        countries = RegionBank.from_geojson(country_path or cfg.COUNTRY_PATH)
+        print(f'Loaded {len(countries)} country polygons from {country_path or cfg.COUNTRY_PATH}')
     if isinstance(base_model, str):                                               # reference :36-40
         from .clip_embedder import HipCLIPVisionModel, load_pretrained_clip
         from .utils import load_state_dict
@@ -342,7 +357,8 @@ def evaluate(model: str, dataset, yfcc: bool, landmarks: bool, base_model=None, 
             os.makedirs(os.path.dirname(packed) or '.', exist_ok=True)
             refiner.host_bank.save(packed)
         print(refiner)
-    results = evaluate_model(full_model, dataset, compute_geoguessr_metrics, None, refiner)
+    metrics = compute_geoguessr_metrics if countries is None else (lambda r: compute_geoguessr_metrics(r, countries=countries))
+    results = evaluate_model(full_model, dataset, metrics, None, refiner)
     if write_calibration:
         if full_model.base_model is not None and full_model.certainty.calibrated:
             full_model.save_calibration(calibration, source=f'evaluate, first batch, {full_model.certainty.stats.get("samples")} samples')

@@ -310,6 +310,93 @@ def tune_optics_lds_points(max_points: int) -> None:
     check(load().pg_tune_optics_lds_points(int(max_points)), "pg_tune_optics_lds_points")
 
 
+# ----------------------------------------------------------------------------------------- point-in-region lookup
+class RegionBankHandle:
+    """pg_region_bank over numpy CSR arrays (pigeon_amd/regions.py RegionBank builds them): keeps the host offset arrays alive,
+    uploads the device copies at the first use that needs them (`device=None`: no GPU is touched; pg_region_plan reads the host side only)."""
+
+    def __init__(self, region_off, ring_off, xy, ring_bbox, region_bbox):
+        import numpy as np
+        self.region_off = np.ascontiguousarray(region_off, dtype=np.int64)
+        self.ring_off = np.ascontiguousarray(ring_off, dtype=np.int64)
+        self.host = (np.ascontiguousarray(xy, dtype=np.float64).reshape(-1, 2), np.ascontiguousarray(ring_bbox, dtype=np.float64).reshape(-1, 4),
+                     np.ascontiguousarray(region_bbox, dtype=np.float64).reshape(-1, 4))
+        self.num_regions, self.num_rings, self.num_vertices = self.region_off.size - 1, self.ring_off.size - 1, self.host[0].shape[0]
+        self.dev = None
+        self.struct = _lib.RegionBankStruct(None, None, None, None, None, self.region_off.ctypes.data, self.ring_off.ctypes.data,
+                                            self.num_regions, self.num_rings, self.num_vertices)
+
+    def on_device(self, device="cuda"):
+        if self.dev is None:
+            _lib.require_gpu()
+            self.dev = [torch.from_numpy(a).to(device) for a in (self.region_off, self.ring_off) + self.host]
+            s = self.struct
+            s.region_off, s.ring_off, s.xy, s.ring_bbox, s.region_bbox = (t.data_ptr() or None for t in self.dev)
+        return self
+
+
+def _region_points(who: str, pts: torch.Tensor) -> torch.Tensor:
+    _dev(pts, torch.float64)
+    return _shape(pts, f"{who}: pts", None, 2)
+
+
+def _host_i32(who: str, name: str, v, n: int):
+    import numpy as np
+    a = np.ascontiguousarray(v.cpu().numpy() if torch.is_tensor(v) else v)
+    if a.shape != (n,) or a.dtype.kind not in "iu":
+        raise _lib.PigeonHipError(f"{who}: {name} must be {n} integers, got shape {a.shape} of {a.dtype}")
+    if a.size and (int(a.min()) < -2**31 or int(a.max()) >= 2**31):
+        raise _lib.PigeonHipError(f"{who}: {name} does not fit 32 bits")
+    return np.ascontiguousarray(a, dtype=np.int32)
+
+
+def region_locate(bank: RegionBankHandle, pts: torch.Tensor, start=None):
+    """pg_region_locate: pts (N,2) fp64 on the device, start (N) host integers or None -> (cover (N) int32, state (N) uint8) on the
+    device: the lowest region >= start[i] that is not certainly OUTSIDE and its state (1 INSIDE, 2 AMBIGUOUS); -1 / 0 if none."""
+    _region_points("region_locate", pts)
+    n = pts.shape[0]
+    st = None if start is None else _host_i32("region_locate", "start", start, n)
+    cover = torch.empty((n,), dtype=torch.int32, device=pts.device)
+    state = torch.empty((n,), dtype=torch.uint8, device=pts.device)
+    check(load().pg_region_locate(C.byref(bank.on_device(pts.device).struct), _p(pts), None if st is None else st.ctypes.data, n, _p(cover),
+                                  _p(state), _stream()), "pg_region_locate")
+    return cover, state
+
+
+def region_classify(bank: RegionBankHandle, pts: torch.Tensor, region) -> torch.Tensor:
+    """pg_region_classify: the state (0 OUTSIDE, 1 INSIDE, 2 AMBIGUOUS) of point i against region[i] (host integers; -1: OUTSIDE)."""
+    _region_points("region_classify", pts)
+    n = pts.shape[0]
+    rg = _host_i32("region_classify", "region", region, n)
+    state = torch.empty((n,), dtype=torch.uint8, device=pts.device)
+    check(load().pg_region_classify(C.byref(bank.on_device(pts.device).struct), _p(pts), rg.ctypes.data, n, _p(state), _stream()),
+          "pg_region_classify")
+    return state
+
+
+def region_nearest(bank: RegionBankHandle, pts: torch.Tensor):
+    """pg_region_nearest: (idx (N) int32, dist (N) fp64) on the device: the region whose boundary is nearest (planar, degrees; ties to
+    the lower index) and that distance."""
+    _region_points("region_nearest", pts)
+    n = pts.shape[0]
+    idx = torch.empty((n,), dtype=torch.int32, device=pts.device)
+    dist = torch.empty((n,), dtype=torch.float64, device=pts.device)
+    check(load().pg_region_nearest(C.byref(bank.on_device(pts.device).struct), _p(pts), n, _p(idx), _p(dist), _stream()), "pg_region_nearest")
+    return idx, dist
+
+
+def region_plan(bank: RegionBankHandle) -> dict:
+    """pg_region_plan: how the three calls map points onto the device for this bank (host arithmetic, no GPU)."""
+    out = (C.c_int32 * 4)()
+    check(load().pg_region_plan(C.byref(bank.struct), out), "pg_region_plan")
+    return {"form": int(out[0]), "threads": int(out[1]), "max_ring_edges": int(out[2]), "wave_edges": int(out[3])}
+
+
+def tune_region_wave_edges(max_edges: int) -> None:
+    """pg_tune_region_wave_edges: the largest ring (edges) of a bank that is still served by one wave per point (negative = the default)."""
+    check(load().pg_tune_region_wave_edges(int(max_edges)), "pg_tune_region_wave_edges")
+
+
 # ----------------------------------------------------------------------------------------- image preprocessing
 class Preprocessor:
     """CLIP preprocessing on the GPU for one input geometry: (N,H,W,3) uint8 RGB -> (N,3,336,336) pixel_values,

@@ -70,6 +70,11 @@ argp.add_argument('--embedding-rel-tol', dest='embedding_rel_tol', type=float, d
                        "embeddings of the exact encoder or of the fp32 reference")
 
 
+argp.add_argument('--countries', default=None, metavar='FILE',
+                  help="evaluate: GeoJSON of country polygons (Polygon / MultiPolygon features) for `Country_accuracy`; default: "
+                       "config.COUNTRY_PATH if that file exists, else the key is left out")
+
+
 class _SyntheticImages(torch.utils.data.Dataset):
     def __init__(self, n, panorama):
         self.n, self.panorama = n, panorama
@@ -172,7 +177,8 @@ def _dispatch(args, comm):
                 dataset = dataset['test'] if args.test else dataset['val']
         results = evaluate(args.name, dataset, yfcc=args.yfcc, base_model=_vision_model(args), refine=True,
                            landmarks=args.landmarks, geocell_path=geocell_path, bank=bank, heading=args.heading,
-                           multi_task=args.multitask, calibration=args.calibration, embedding_rel_tol=args.embedding_rel_tol)
+                           multi_task=args.multitask, calibration=args.calibration, embedding_rel_tol=args.embedding_rel_tol,
+                           country_path=args.countries)
         if comm.is_main_process:
             print({k: (v if not hasattr(v, 'shape') or v.shape == () else tuple(v.shape)) for k, v in results.items() if k != 'exact_passes'})
             if 'geocell_certain' in results:
