@@ -36,6 +36,7 @@ extern "C" {
 #define PG_DTYPE_BF16    1
 #define PG_DTYPE_F16     2
 #define PG_DTYPE_F64     3
+#define PG_DTYPE_U8      4   /* 8-bit pixels: the byte the resize computes, before the normalisation table (pg_prep_norm_lut) */
 
 #define PG_ABI_VERSION   7   /* 2: pg_vit_cfg.precise, pg_vit_forward_precise, pg_head_margin (round 4); 3: pg_head_certainty, pg_refine_forward_ex,
                               * pg_refine_certainty, pg_tune_gemm_raster (round 5); 4: the deferred exact tier -- pg_requeue_append,
@@ -45,7 +46,8 @@ extern "C" {
                               * 7 (+ pg_aux_heads_forward, additive; + pg_fingerprint, pg_vit_fingerprint, additive;
                               *    + pg_prep_ragged_plan / _create / _destroy / _forward and pg_prep_item, additive;
                               *    + pg_haversine_blocks, pg_optics_graph, pg_optics_plan, pg_tune_optics_lds_points, additive;
-                              *    + pg_region_locate, pg_region_classify, pg_region_nearest, pg_region_plan, pg_tune_region_wave_edges, additive) */
+                              *    + pg_region_locate, pg_region_classify, pg_region_nearest, pg_region_plan, pg_tune_region_wave_edges, additive;
+                              *    + PG_DTYPE_U8 pixels and pg_prep_norm_lut, additive) */
 
 const char* pg_last_error(void);
 int pg_abi_version(void);
@@ -85,11 +87,15 @@ int pg_vit_create(pg_vit** out, int device, const pg_vit_cfg* cfg);
  * Unknown names (post_layernorm.*, position_ids) are accepted and ignored (dead on this path). */
 int pg_vit_load_weight(pg_vit* h, const char* name, const void* data, int dtype,
                        const int64_t* shape, int ndim);
-/* Checks that every required parameter was loaded and uploads fused/packed forms. */
+/* Checks that every required parameter was loaded and uploads fused/packed forms, and the handle's 3 KB device copy of the
+ * normalisation table (pg_prep_norm_lut) that PG_DTYPE_U8 pixels are looked up in. */
 int pg_vit_finalize(pg_vit* h);
 /* Bytes of DEVICE workspace pg_vit_forward needs for n_images (caller allocates, e.g. a torch uint8 tensor). */
 int pg_vit_workspace_bytes(const pg_vit* h, int n_images, size_t* bytes);
-/* pixels: DEVICE (n_images,3,336,336) contiguous NCHW, fp32 (PG_DTYPE_F32), fp16 (what pg_prep_forward writes) or bf16.
+/* pixels: DEVICE (n_images,3,336,336) contiguous NCHW, fp32 (PG_DTYPE_F32), fp16 (what pg_prep_forward writes), bf16, or the
+ * bytes pg_prep_forward writes with PG_DTYPE_U8: the im2col looks each byte up in the handle's copy of pg_prep_norm_lut, so the pass
+ * computes from bytes b exactly what it computes from the fp32 pixels table[c][b], bit for bit (an image is 338 688 bytes: every
+ * image of a 16-byte aligned batch is 16-byte aligned).  Any other code is PG_EINVAL "bad pixel dtype".
  * emb_out: DEVICE (n_images,1024) fp32 -- mean over the 577 tokens of last_hidden_state.
  * n_images = 0 is a no-op (PG_OK; the buffers of an empty batch may be NULL), n_images < 0 is PG_EINVAL -- the same holds for
  * pg_prep_forward, pg_head_forward (B) and pg_refine_forward (B). */
@@ -106,7 +112,8 @@ int pg_vit_forward_hidden(pg_vit* h, const void* pixels, int pix_dtype, int n_im
  * persistent MFMA kernels over a 3x longer K; LayerNorm, attention (fp32 MFMA), QuickGELU (expf, IEEE division) and the residual
  * stream are fp32.  Measured against the fp32 reference: embeddings to ~1e-6 relative (fast path: 2.7e-4), at ~5x the time per
  * image.  Needs cfg.precise at creation.  Workspace from pg_vit_precise_workspace_bytes (98 KB per token row, equal chunks of at most 128 images).
- * hidden_out (DEVICE (n_images,577,1024) fp32, may be NULL) receives last_hidden_state. */
+ * hidden_out (DEVICE (n_images,577,1024) fp32, may be NULL) receives last_hidden_state.  pixels / pix_dtype as pg_vit_forward: from
+ * PG_DTYPE_U8 bytes both tiers start from the identical fp32 value. */
 int pg_vit_precise_workspace_bytes(const pg_vit* h, int n_images, size_t* bytes);
 /* What pg_vit_forward_precise does with a batch of n_images (>= 1) under the current knobs.  Host arithmetic only: no launch, no device
  * work; pg_vit_forward_precise runs what this reports (one function decides both).
@@ -401,9 +408,13 @@ int pg_prep_destroy(pg_prep* h);
 /* out6 = { resized_h, resized_w, crop_top, crop_left, first_source_row, source_rows_used } */
 int pg_prep_geometry(const pg_prep* h, int32_t* out6);
 int pg_prep_workspace_bytes(const pg_prep* h, int n_images, size_t* bytes);
-/* images_u8: DEVICE (n_images, in_h, in_w, 3) uint8 RGB; out: DEVICE (n_images,3,336,336) fp32 (PG_DTYPE_F32) or fp16
- * (PG_DTYPE_F16, the fp32 value rounded to nearest even -- exactly what the encoder's im2col would do to the fp32 value).
- * Asynchronous on `stream`. */
+/* The normalisation table: out[c * 256 + v] = ((v / 255) - mean[c]) / std[c] evaluated in IEEE float32, operation by operation, as
+ * numpy does for float32 arrays -- every value a pixel can take.  HOST ONLY (no HIP call).  PG_EINVAL for a null pointer. */
+int pg_prep_norm_lut(float out[768]);
+/* images_u8: DEVICE (n_images, in_h, in_w, 3) uint8 RGB; out: DEVICE (n_images,3,336,336) fp32 (PG_DTYPE_F32), fp16
+ * (PG_DTYPE_F16, the fp32 value rounded to nearest even -- exactly what the encoder's im2col would do to the fp32 value) or uint8
+ * (PG_DTYPE_U8: the resized, clamped byte itself, planar; table[c][byte] is the fp32 output, a quarter of its size).  Same grids and
+ * workspace for all three.  Asynchronous on `stream`. */
 int pg_prep_forward(pg_prep* h, const void* images_u8, int n_images, void* out, int out_dtype, void* workspace,
                     size_t workspace_bytes, void* stream);
 
@@ -439,8 +450,8 @@ typedef struct pg_prep_ragged pg_prep_ragged;
 int pg_prep_ragged_create(pg_prep_ragged** out, int device);
 int pg_prep_ragged_destroy(pg_prep_ragged* h);
 /* packed_dev: DEVICE, packed_bytes bytes, 16-byte aligned, laid out as above -- its first n * PG_PREP_ITEM_BYTES bytes MUST be a copy
- * of items_host (the kernels read the descriptors there; the host copy is what this call checks).  out: DEVICE (n,3,336,336) fp32 or
- * fp16 as pg_prep_forward.  workspace: DEVICE, 16-byte aligned.  Before anything is launched every descriptor is checked against
+ * of items_host (the kernels read the descriptors there; the host copy is what this call checks).  out: DEVICE (n,3,336,336) fp32,
+ * fp16 or uint8 as pg_prep_forward.  workspace: DEVICE, 16-byte aligned.  Before anything is launched every descriptor is checked against
  * its own (in_h, in_w) and against packed_bytes / workspace_bytes -- geometry, range, alignment, ascending overlap-free offsets:
  * PG_EINVAL (PG_ENOMEM for a workspace too small for the temp image) with a message that names the image.  n = 0 is a no-op (buffers
  * may be NULL).  Asynchronous on `stream`: three launches whatever the sizes; the horizontal pass stages one source row in dynamic
@@ -617,7 +628,9 @@ int pg_op_layernorm(const float* x, const float* gamma, const float* beta, void*
 /* Multi-head attention over the fused QKV buffer (n_images*577, 3072) 16-bit -> out (n_images*577,1024) 16-bit.
  * Q must already carry the factor log2(e)/sqrt(64) (the GEMM epilogue applies it); softmax in fp32. */
 int pg_op_attention(int dtype, const void* qkv, void* out, int n_images, void* stream);
-/* fp32/fp16/bf16 NCHW pixels -> 16-bit patch matrix (n_images*576, 640), k = c*196+ky*14+kx, cols 588..639 zero. */
+/* fp32/fp16/bf16/uint8 NCHW pixels -> 16-bit patch matrix (n_images*576, 640), k = c*196+ky*14+kx, cols 588..639 zero.  PG_DTYPE_U8
+ * pixels (16-byte aligned) go through the normalisation table first: the same bits as from the fp32 pixels table[c][byte].
+ * out_dtype PG_DTYPE_U8 is refused by name (bytes are a pixel format only). */
 int pg_op_im2col(const void* pixels, int pix_dtype, void* out, int out_dtype, int n_images, void* stream);
 /* mean over the 577 tokens: x fp32 (n_images,577,1024) -> (n_images,1024). */
 int pg_op_token_mean(const float* x, float* out, int n_images, void* stream);
@@ -631,7 +644,7 @@ int pg_op_cast_f32(const float* x, void* y, int out_dtype, int64_t n, void* stre
  *   pg_op_attention_f32 fused QKV fp32 (n_images*577, 3072), Q NOT pre-scaled -> softmax(q k^T / 8) v, fp32 (n_images*577, 1024)
  *   pg_op_attention_x3  the same attention with the output written as the triple (n_images*577, 3072) the out-projection reads: what
  *                       pg_op_x3_split makes of pg_op_attention_f32's rows, bit for bit.  PG_ESTATE with pg_tune_exact_attention(1).
- *   pg_op_x3_im2col     fp32/fp16/bf16 NCHW pixels -> the triple of the patch matrix (n_images*576, 3*640): segment s holds its 588 values
+ *   pg_op_x3_im2col     fp32/fp16/bf16/uint8 (as pg_op_im2col) NCHW pixels -> the triple of the patch matrix (n_images*576, 3*640): segment s holds its 588 values
  *                       at columns [640 s, 640 s + 588), k = c*196+ky*14+kx, the 52 pad columns of every segment zero
  *   pg_op_sum_parts     dst[i] = (resid ? dst[i] : 0) + ((p0[i] + p1[i]) + p2[i] ...), i < n, part k at parts + k*part_elems; n and
  *                       part_elems multiples of 4, n <= part_elems, 1 <= S <= 8 */

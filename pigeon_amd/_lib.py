@@ -9,7 +9,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # PIGEON_HIP_LIB lets a developer A/B two builds of the library in one process launch (tools/); default = in-tree build
 LIB_PATH = os.environ.get("PIGEON_HIP_LIB") or os.path.join(_HERE, "libpigeon_hip.so")
 
-PG_DTYPE_F32, PG_DTYPE_BF16, PG_DTYPE_F16, PG_DTYPE_F64 = 0, 1, 2, 3
+PG_DTYPE_F32, PG_DTYPE_BF16, PG_DTYPE_F16, PG_DTYPE_F64, PG_DTYPE_U8 = 0, 1, 2, 3, 4
 EPI_QKV, EPI_GELU, EPI_RESID, EPI_PATCH, EPI_F32, EPI_RESID_STAT, EPI_QKV_LN, EPI_GELU_LN, EPI_GELU_X3 = 0, 1, 2, 3, 4, 5, 6, 7, 8
 PROF_CLASSES = ["gemm_qkv", "gemm_out", "gemm_fc1", "gemm_fc2", "gemm_patch", "attention", "layernorm",
                 "im2col", "token_mean"]
@@ -96,6 +96,7 @@ SIGNATURES = {
     "pg_prep_destroy": (_I, [_P]),
     "pg_prep_geometry": (_I, [_P, C.POINTER(C.c_int32)]),
     "pg_prep_workspace_bytes": (_I, [_P, _I, C.POINTER(_SZ)]),
+    "pg_prep_norm_lut": (_I, [C.POINTER(_F)]),
     "pg_prep_forward": (_I, [_P, _P, _I, _P, _I, _P, _SZ, _P]),
     "pg_prep_ragged_plan": (_I, [_I, C.POINTER(C.c_int32), C.POINTER(PrepItem), C.POINTER(_SZ), C.POINTER(_SZ)]),
     "pg_prep_ragged_create": (_I, [C.POINTER(_P), _I]),

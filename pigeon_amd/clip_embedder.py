@@ -93,16 +93,32 @@ class HipCLIPVisionModel(torch.nn.Module):
             self._precise = bool(on)
             self._weights_changed()
 
-    def embed_precise(self, pixel_values: Tensor, out: Optional[Tensor] = None) -> Tensor:
-        """The exact mode of `embed`: near-fp32 arithmetic (pg_vit_forward_precise), ~3x the time per image at 40+ images, more below.
-        `out` (N,1024) fp32: write there instead of a fresh tensor."""
-        self.enable_precise(True)
-        pixel_values = _to_device_pixels(pixel_values, self._dummy.device)
-        return self._encoder(pixel_values.device).forward_precise(pixel_values, out=out)
+    def _pixels(self, pixel_values: Optional[Tensor], pixel_bytes: Optional[Tensor]) -> Tensor:
+        """The (N,3,336,336) device tensor the encoder reads: float `pixel_values` as before, or `pixel_bytes` -- uint8 (B,12,336,336) /
+        (B,3,336,336), checked by name before anything moves -- as (B*4 or B, 3,336,336) uint8."""
+        if pixel_bytes is None:
+            return _to_device_pixels(pixel_values, self._dummy.device)
+        exclusive_pixel_bytes(pixel_bytes, pixel_values=pixel_values)
+        return pixel_bytes_to_device(pixel_bytes, self._dummy.device)
 
-    def embed(self, pixel_values: Tensor) -> Tensor:
-        pixel_values = _to_device_pixels(pixel_values, self._dummy.device)
-        return self._encoder(pixel_values.device).forward(pixel_values)
+    def embed_precise(self, pixel_values: Tensor = None, out: Optional[Tensor] = None, pixel_bytes: Tensor = None) -> Tensor:
+        """The exact mode of `embed`: near-fp32 arithmetic (pg_vit_forward_precise), ~3x the time per image at 40+ images, more below.
+        `out` (N,1024) fp32: write there instead of a fresh tensor.  `pixel_bytes`: as `embed`."""
+        px = self._pixels(pixel_values, pixel_bytes)
+        self.enable_precise(True)
+        return self._encoder(px.device).forward_precise(px, out=out)
+
+    def embed(self, pixel_values: Tensor = None, pixel_bytes: Tensor = None) -> Tensor:
+        """`pixel_bytes` (instead of `pixel_values`): uint8 (B,12,336,336) or (B,3,336,336), device or host -- the resized bytes in
+        front of the normalisation table (`gpu_preprocess(..., out_dtype=torch.uint8)`).  The encoder looks them up itself: the same
+        bits as from the fp32 pixel_values, a quarter of the bytes.  Returns one row per image (B*4 or B)."""
+        px = self._pixels(pixel_values, pixel_bytes)
+        return self._encoder(px.device).forward(px)
+
+    def hidden(self, pixel_values: Tensor = None, pixel_bytes: Tensor = None) -> Tensor:
+        """last_hidden_state (N,577,1024) of `pixel_values` or `pixel_bytes` (as `embed`)."""
+        px = self._pixels(pixel_values, pixel_bytes)
+        return self._encoder(px.device).forward(px, return_hidden=True)[1]
 
     def fingerprint(self) -> str:
         """32 hex digits identifying the weights the fast encoder computes with (pg_vit_fingerprint over the packed device buffers;
@@ -154,6 +170,38 @@ def _to_device_pixels(pixel_values: Tensor, device) -> Tensor:
     if pixel_values.dtype not in (torch.float32, torch.float16, torch.bfloat16):
         pixel_values = pixel_values.float()
     return pixel_values.contiguous()
+
+
+def check_pixel_bytes(pixel_bytes, name: str = "pixel_bytes") -> Tensor:
+    """The one form 8-bit pixels are accepted in, anywhere: a CONTIGUOUS uint8 tensor (B,12,336,336) or (B,3,336,336), planar (what
+    `gpu_preprocess(..., out_dtype=torch.uint8)` writes, four views side by side for a panorama).  Anything else -- HWC images, another
+    shape or dtype, a strided view -- is a ValueError that names the argument, raised before the tensor goes anywhere."""
+    if not torch.is_tensor(pixel_bytes) or pixel_bytes.dtype != torch.uint8:
+        got = pixel_bytes.dtype if torch.is_tensor(pixel_bytes) else type(pixel_bytes).__name__
+        raise ValueError(f"{name} must be a uint8 tensor (B,12,336,336) or (B,3,336,336), got {got}")
+    shape = tuple(pixel_bytes.shape)
+    if len(shape) != 4 or shape[1] not in (3, 12) or shape[2:] != (336, 336):
+        hwc = " -- HWC images are not pixel bytes: resize them with gpu_preprocess(..., out_dtype=torch.uint8)" if shape[-1:] == (3,) else ""
+        raise ValueError(f"{name} must be uint8 (B,12,336,336) or (B,3,336,336) planar, got shape {shape}{hwc}")
+    if not pixel_bytes.is_contiguous():
+        raise ValueError(f"{name} must be contiguous, got strides {tuple(pixel_bytes.stride())} for shape {shape}")
+    return pixel_bytes
+
+
+def exclusive_pixel_bytes(pixel_bytes, **others) -> None:
+    """`pixel_bytes` stands alone: a ValueError naming it and the other input it was given with."""
+    given = [k for k, v in others.items() if v is not None]
+    if pixel_bytes is not None and given:
+        raise ValueError(f"pixel_bytes cannot be given together with {' / '.join(given)}: one input per call")
+
+
+def pixel_bytes_to_device(pixel_bytes: Tensor, device) -> Tensor:
+    """Checked `pixel_bytes` -> (B*4 or B, 3,336,336) uint8 on the device (a host tensor is copied as bytes)."""
+    check_pixel_bytes(pixel_bytes)
+    if not pixel_bytes.is_cuda:
+        dev = device if (isinstance(device, torch.device) and device.type == "cuda") else torch.device("cuda")
+        pixel_bytes = pixel_bytes.to(dev)
+    return pixel_bytes.view((-1, 3, 336, 336))
 
 
 def _resize_output_size(h: int, w: int, size: int = 336):
@@ -312,7 +360,9 @@ def _gpu_preprocess(images, device="cuda", out_dtype: torch.dtype = torch.float3
     several shapes run pg_prep_ragged_forward: one packed staging buffer and, per chunk of at most RAGGED_MAX_BYTES (256 MiB) of packed
     bytes, one copy and three launches whatever the sizes.  A PINNED `PackedImages` is copied from in place: its head is overwritten
     with the descriptors and the buffer belongs to the call until `copy_event` (set on the object) has passed.  Returns the
-    (N,3,336,336) pixel_values on `device`, bit-identical to `clip_preprocess` / the reference's CLIPProcessor."""
+    (N,3,336,336) pixel_values on `device`, bit-identical to `clip_preprocess` / the reference's CLIPProcessor.
+    `out_dtype`: torch.float32, torch.float16 (the fp32 value rounded) or torch.uint8 -- the resized, cropped byte itself, planar, in
+    front of the normalisation table: what the `pixel_bytes` arguments of the encoder and the model take (a quarter of the fp32 size)."""
     dev = torch.device(device)
     if dev.index is None:
         dev = torch.device("cuda", torch.cuda.current_device())
@@ -376,7 +426,7 @@ class CLIPEmbedding(torch.nn.Module):
     def __init__(self, model_name: str, device: str = 'cuda', load_checkpoint: bool = False,
                  panorama: bool = False, state_dict: Optional[Dict[str, Tensor]] = None,
                  clip_model: Optional[HipCLIPVisionModel] = None, contract_guard: Optional[str] = None,
-                 calibration: Optional[str] = None):
+                 calibration: Optional[str] = None, pixel_bytes: Optional[bool] = None):
         """CLIP embedding model (not trainable) -- reference models/clip_embedder.py:11-40.
 
         Args follow the reference.  The reference pulls the base weights from the HuggingFace hub
@@ -396,6 +446,11 @@ class CLIPEmbedding(torch.nn.Module):
 
         `calibration` (a path): `load_calibration(path)` at the end of construction -- bias and verdict come from the file, and the
         first forward runs neither the guard's measurement nor its collectives.  Without it nothing changes.
+
+        `pixel_bytes` (default: env PIGEON_PIXEL_BYTES, else False): images given as PIL / uint8 HWC / `PackedImages` are preprocessed
+        to 8-bit pixels (`gpu_preprocess(..., out_dtype=torch.uint8)`) and the fast tier, `force_exact` and the guard's measurement all
+        encode from those bytes: both tiers start from the identical fp32 value, where the default hands the exact tier fp16-rounded
+        pixels.  Float tensors given as pixel_values are encoded as before.
         """
         super().__init__()
         self.device = device
@@ -419,6 +474,7 @@ class CLIPEmbedding(torch.nn.Module):
                         "point PIGEON_CLIP_MODEL at a directory written by save_pretrained (or have the hub id in the local HF cache), "
                         "pass state_dict=... / clip_model=..., or a checkpoint path with load_checkpoint=True.  " + str(why)) from why
         self.panorama = panorama
+        self.pixel_bytes = (os.environ.get('PIGEON_PIXEL_BYTES', '0') not in ('', '0')) if pixel_bytes is None else bool(pixel_bytes)
         self.contract_guard = (contract_guard or os.environ.get('PIGEON_EMBED_GUARD', 'exact')).lower()
         if self.contract_guard not in ('exact', 'raise', 'off'):
             raise ValueError(f"contract_guard must be 'exact', 'raise' or 'off', got {self.contract_guard!r}")
@@ -499,7 +555,7 @@ class CLIPEmbedding(torch.nn.Module):
                 # PIL image(s) / uint8 HWC arrays / a PackedImages: resize + crop + normalise on the GPU (bit-identical to the
                 # reference's host-side CLIPProcessor); 16-bit pixels when the encoder's MFMA operands are fp16
                 dev = self.device if type(self.device) == str else f'cuda:{self.device}'
-                pixel_values = gpu_preprocess(image, dev, self._pixel_dtype())
+                pixel_values = gpu_preprocess(image, dev, torch.uint8 if self.pixel_bytes else self._pixel_dtype())
             else:
                 pixel_values = image
             if type(self.device) == str:
@@ -510,9 +566,11 @@ class CLIPEmbedding(torch.nn.Module):
             if self.contract_guard != 'off' and self.guard_stats is None and pixel_values.shape[0] > 0:
                 self._check_contract(base, pixel_values)
             # last_hidden_state.mean(dim=1), fused in the library (token_mean kernel)
+            # (uint8 here is what gpu_preprocess wrote just above with `pixel_bytes`: (N,3,336,336) planar bytes)
+            as_input = (lambda px: dict(pixel_bytes=px)) if pixel_values.dtype == torch.uint8 else (lambda px: dict(pixel_values=px))
             if self.force_exact:
-                return base.embed_precise(pixel_values)
-            emb = base.embed(pixel_values)
+                return base.embed_precise(**as_input(pixel_values))
+            emb = base.embed(**as_input(pixel_values))
             bias = self.certainty.bias_on(emb.device)
             if bias is not None:
                 # the 16-bit encoder's measured systematic error taken out of every image's embedding (pigeon_amd/certainty.py `debias`)
@@ -524,6 +582,9 @@ class CLIPEmbedding(torch.nn.Module):
         measurement; `_judge` is what follows from it.
         (A first batch of fewer than 8 images measures the error but fits no bias: nothing is subtracted for the lifetime of this
         object -- hand the embed path a full first batch, as `run.py embed` does, or set PIGEON_DEBIAS=0 on both entry points.)"""
+        if pixel_values.dtype == torch.uint8:                        # `pixel_bytes`: both encoders from the same bytes
+            px = pixel_values[:max_images].contiguous()
+            return self._judge(base.embed(pixel_bytes=px), base.embed_precise(pixel_bytes=px))
         px = _to_device_pixels(pixel_values[:max_images], base._dummy.device)
         return self._judge(base.embed(px), base.embed_precise(px))
 

@@ -77,7 +77,10 @@ extern "C" int pg_op_attention(int dtype, const void* qkv, void* out, int n_imag
 }
 extern "C" int pg_op_im2col(const void* pixels, int pix_dtype, void* out, int out_dtype, int n_images, void* stream) {
     if (!pixels || !out) { pg_set_error("op_im2col: null argument"); return PG_EINVAL; }
-    return pg_im2col_launch(pixels, pix_dtype, out, out_dtype, n_images, (hipStream_t)stream);
+    if (out_dtype == PG_DTYPE_U8) { pg_set_error("op_im2col: PG_DTYPE_U8 is a pixel dtype, not an output dtype"); return PG_EINVAL; }
+    const float* lut = nullptr;
+    if (pix_dtype == PG_DTYPE_U8 && n_images > 0) { const int rc = pg_norm_lut_device(&lut); if (rc) return rc; }
+    return pg_im2col_launch(pixels, pix_dtype, out, out_dtype, n_images, (hipStream_t)stream, lut);
 }
 extern "C" int pg_op_token_mean(const float* x, float* out, int n_images, void* stream) {
     if (!x || !out) { pg_set_error("op_token_mean: null argument"); return PG_EINVAL; }
@@ -112,7 +115,9 @@ extern "C" int pg_op_attention_f32(const float* qkv, float* out, int n_images, v
 }
 extern "C" int pg_op_x3_im2col(const void* pixels, int pix_dtype, void* out3, int n_images, void* stream) {
     if (!pixels || !out3 || n_images < 0) { pg_set_error("op_x3_im2col: bad argument"); return PG_EINVAL; }
-    return pg_x3_im2col_launch(pixels, pix_dtype, out3, n_images, (hipStream_t)stream);
+    const float* lut = nullptr;
+    if (pix_dtype == PG_DTYPE_U8 && n_images > 0) { const int rc = pg_norm_lut_device(&lut); if (rc) return rc; }
+    return pg_x3_im2col_launch(pixels, pix_dtype, out3, n_images, (hipStream_t)stream, lut);
 }
 extern "C" int pg_op_sum_parts(const float* parts, int S, int64_t part_elems, float* dst, int64_t n, int resid, void* stream) {
     if (!parts || !dst) { pg_set_error("op_sum_parts: null argument"); return PG_EINVAL; }

@@ -61,6 +61,12 @@ struct PgFpBuf { const void* data; size_t bytes; uint64_t seed; };
 int pg_fingerprint_many(const PgFpBuf* bufs, int n, uint64_t* out, hipStream_t stream);
 void pg_fingerprint_host(const void* data, size_t bytes, uint64_t seed, uint64_t out[2]);
 
+// preprocess.hip: the normalisation table ((v / 255) - mean[c]) / std[c], [3][256] fp32 -- its one definition (host), and a per-device
+// copy for the entry points without a handle
+#define PG_NORM_LUT_SIZE (3 * 256)
+void pg_norm_lut_fill(float* lut);
+int pg_norm_lut_device(const float** lut);
+
 // gemm_plan.hip: every GEMM; argument checks, the plan, at most two kernel launches
 int pg_gemm_launch(int dtype, const void* A, int64_t lda, const void* W, int64_t ldw, const float* bias, void* out, int64_t ldc,
                    int M, int N, int K, int epi, float qscale, int qcols, const float* aux, int variant,
@@ -70,7 +76,8 @@ int pg_layernorm_launch(const float* x, const float* gamma, const float* beta, v
                         int64_t rows, float eps, hipStream_t s);
 int pg_preln_launch(float* x, const float* cls, const float* pos0, const float* gamma, const float* beta,
                     int64_t rows, float eps, hipStream_t s, void* x16 = nullptr, int x16_dtype = 0, float* rowstat = nullptr);
-int pg_im2col_launch(const void* pixels, int pix_dtype, void* out, int out_dtype, int n_images, hipStream_t s);
+// norm_lut: DEVICE [3][256] fp32 normalisation table, read only for PG_DTYPE_U8 pixels (may be NULL otherwise)
+int pg_im2col_launch(const void* pixels, int pix_dtype, void* out, int out_dtype, int n_images, hipStream_t s, const float* norm_lut = nullptr);
 int pg_token_mean_launch(const float* x, float* out, int n_images, hipStream_t s);
 int pg_cast_f32_launch(const float* x, void* y, int out_dtype, int64_t n, hipStream_t s);
 int pg_rowstat_cast_launch(const float* x, void* x16, int out_dtype, float* rowstat, int64_t rows, float eps, hipStream_t s);
@@ -82,7 +89,7 @@ int pg_attention_launch(int dtype, const void* qkv, void* out, int n_images, hip
 // precise.hip (exact mode)
 int pg_x3_ln_launch(const float* x, const float* gamma, const float* beta, void* y3, int64_t rows, float eps, hipStream_t s);
 int pg_x3_split_launch(const float* x, void* y3, int64_t rows, int C, int gelu, hipStream_t s);
-int pg_x3_im2col_launch(const void* pixels, int pix_dtype, void* out3, int n_images, hipStream_t s);
+int pg_x3_im2col_launch(const void* pixels, int pix_dtype, void* out3, int n_images, hipStream_t s, const float* norm_lut = nullptr);
 int pg_attention_f32_launch(const float* qkv, float* out, int n_images, hipStream_t s);
 bool pg_attention_x3out_available();
 int pg_attention_x3out_launch(const float* qkv, void* out3, int n_images, hipStream_t s);

@@ -15,7 +15,7 @@
 // runs it on split fp16 operands like the GEMMs (attention_x3_kernel).
 //
 // Kernels here (all HBM-bound streaming except attention):
-//   im2col_x3_kernel   pixels (n,3,336,336) -> patch matrix triple [576 n][3 * 640] fp16
+//   im2col_x3_kernel   pixels (n,3,336,336) -> patch matrix triple [576 n][3 * 640] fp16 (im2col_x3_u8_kernel: from 8-bit pixels)
 //   ln_x3_kernel       LayerNorm of fp32 rows -> triple [M][3 * 1024]
 //   split_x3_kernel    fp32 [M][C] (optionally through QuickGELU) -> triple [M][3 * C]
 //   sum_parts_kernel   (round 5) fixed-order sum of the K-split partial products of one GEMM (+ the fp32 residual row)
@@ -136,10 +136,49 @@ __global__ __launch_bounds__(256) void im2col_x3_kernel(const PIX* __restrict__ 
         dst[px * (3 * VIT_PATCH_KPAD) + seg * VIT_PATCH_KPAD + VIT_PATCH_K + k] = 0;
     }
 }
-int pg_x3_im2col_launch(const void* pixels, int pix_dtype, void* out3, int n_images, hipStream_t s) {
+// 8-bit pixels (PG_DTYPE_U8): as im2col_u8_kernel (rowops.hip) -- the table in LDS, a line as 84 aligned 4-byte words, each byte looked up
+// to the fp32 value the fp32 instantiation reads, then the same x3_split.
+__global__ __launch_bounds__(256) void im2col_x3_u8_kernel(const uint8_t* __restrict__ pix, uint16_t* __restrict__ out,
+                                                           const float* __restrict__ lut) {
+    __shared__ float slut[PG_NORM_LUT_SIZE];
+    for (int i = threadIdx.x; i < PG_NORM_LUT_SIZE; i += 256) slut[i] = lut[i];
+    __syncthreads();
+    const int img = blockIdx.x / 24, py = blockIdx.x % 24;
+    const uint8_t* src = pix + (int64_t)img * 3 * VIT_IMG * VIT_IMG;
+    uint16_t* dst = out + ((int64_t)img * VIT_PATCHES + py * 24) * (3 * VIT_PATCH_KPAD);
+    constexpr int WORDS = VIT_IMG / 4;
+    static_assert(VIT_IMG % 4 == 0, "a pixel line is a whole number of 4-byte words");
+    for (int idx = threadIdx.x; idx < 42 * WORDS; idx += 256) {
+        const int line = idx / WORDS, w = idx - line * WORDS;          // line = c*14 + ky
+        const int c = line / 14, ky = line - c * 14;
+        const uint32_t word = *(const uint32_t*)(src + ((int64_t)c * VIT_IMG + py * 14 + ky) * VIT_IMG + w * 4);
+        // two pixels per 4-byte store (a pair starts at an even kx <= 12: inside one patch, at an even element offset)
+#pragma unroll
+        for (int b = 0; b < 4; b += 2) {
+            const int xcol = w * 4 + b;
+            const int px = xcol / 14, kx = xcol - px * 14;
+            const X3 t0 = x3_split(slut[c * 256 + ((word >> (8 * b)) & 0xffu)]);
+            const X3 t1 = x3_split(slut[c * 256 + ((word >> (8 * b + 8)) & 0xffu)]);
+            uint16_t* d = dst + px * (3 * VIT_PATCH_KPAD) + c * 196 + ky * 14 + kx;
+            *(uint32_t*)d = (uint32_t)t0.hi | ((uint32_t)t1.hi << 16);
+            *(uint32_t*)(d + VIT_PATCH_KPAD) = (uint32_t)t0.lo | ((uint32_t)t1.lo << 16);
+            *(uint32_t*)(d + 2 * VIT_PATCH_KPAD) = (uint32_t)t0.hs | ((uint32_t)t1.hs << 16);
+        }
+    }
+    const int pad = VIT_PATCH_KPAD - VIT_PATCH_K;
+    for (int idx = threadIdx.x; idx < 24 * 3 * pad; idx += 256) {
+        const int px = idx / (3 * pad), rem = idx % (3 * pad), seg = rem / pad, k = rem % pad;
+        dst[px * (3 * VIT_PATCH_KPAD) + seg * VIT_PATCH_KPAD + VIT_PATCH_K + k] = 0;
+    }
+}
+int pg_x3_im2col_launch(const void* pixels, int pix_dtype, void* out3, int n_images, hipStream_t s, const float* norm_lut) {
     if (n_images <= 0) return PG_OK;
     dim3 grid(n_images * 24), block(256);
-    if (pix_dtype == PG_DTYPE_F32) hipLaunchKernelGGL((im2col_x3_kernel<float, 0>), grid, block, 0, s, (const float*)pixels, (uint16_t*)out3);
+    if (pix_dtype == PG_DTYPE_U8) {
+        if (!norm_lut) { pg_set_error("im2col_x3: PG_DTYPE_U8 pixels without a normalisation table"); return PG_EINVAL; }
+        if (((uintptr_t)pixels | (uintptr_t)out3) & 3) { pg_set_error("im2col_x3: PG_DTYPE_U8 pixels and their patch matrix must be 4-byte aligned"); return PG_EINVAL; }
+        hipLaunchKernelGGL(im2col_x3_u8_kernel, grid, block, 0, s, (const uint8_t*)pixels, (uint16_t*)out3, norm_lut);
+    } else if (pix_dtype == PG_DTYPE_F32) hipLaunchKernelGGL((im2col_x3_kernel<float, 0>), grid, block, 0, s, (const float*)pixels, (uint16_t*)out3);
     else if (pix_dtype == PG_DTYPE_BF16) hipLaunchKernelGGL((im2col_x3_kernel<uint16_t, 1>), grid, block, 0, s, (const uint16_t*)pixels, (uint16_t*)out3);
     else if (pix_dtype == PG_DTYPE_F16) hipLaunchKernelGGL((im2col_x3_kernel<uint16_t, 2>), grid, block, 0, s, (const uint16_t*)pixels, (uint16_t*)out3);
     else { pg_set_error("im2col_x3: unsupported pixel dtype %d", pix_dtype); return PG_EINVAL; }

@@ -14,7 +14,9 @@
 // Kernels (both HBM-bound byte streams, one block per image row):
 //   prep_h_kernel   source row (W x 3 bytes) staged in LDS; thread xo of 336 accumulates its taps for R,G,B -> uint8 temp
 //   prep_v_kernel   output row yo: thread xo accumulates the vertical taps over temp rows (coalesced 3-byte pixels),
-//                   clips, looks up the normalised value and writes the three channel planes (coalesced along x)
+//                   clips, looks up the normalised value and writes the three channel planes (coalesced along x); with out dtype
+//                   PG_DTYPE_U8 it writes the clipped byte itself and the encoder's im2col does the lookup (pg_norm_lut_fill below
+//                   is the table's one definition, exported as pg_prep_norm_lut)
 // Only the rows / columns the 336x336 crop needs are ever computed (Pillow computes the full resized image, then crops:
 // rows and columns are independent, so the cropped values are identical).
 //
@@ -28,6 +30,8 @@
 #include "pigeon_internal.h"
 
 #include <cmath>
+#include <map>
+#include <mutex>
 #include <vector>
 
 #define PREP_BITS 22              // Pillow PRECISION_BITS = 32 - 8 - 2
@@ -117,9 +121,9 @@ static PrepGeom prep_geom(int in_h, int in_w) {
     return g;
 }
 
-// ((v / 255.0f) - mean) / std in IEEE float32 (what numpy does for float32 arrays)
-static std::vector<float> make_lut() {
-    std::vector<float> lut(3 * 256);
+// ((v / 255.0f) - mean) / std in IEEE float32 (what numpy does for float32 arrays).  THE definition of the normalisation table: the
+// resize handles, the encoder handle (pg_vit_finalize) and the op-level im2col entry points all get theirs from here.
+void pg_norm_lut_fill(float* lut) {
     const float mean[3] = {0.48145466f, 0.4578275f, 0.40821073f}, stdv[3] = {0.26862954f, 0.26130258f, 0.27577711f};
     for (int c = 0; c < 3; ++c)
         for (int v = 0; v < 256; ++v) {
@@ -127,13 +131,41 @@ static std::vector<float> make_lut() {
             volatile float y = x - mean[c];
             lut[c * 256 + v] = y / stdv[c];
         }
+}
+static std::vector<float> make_lut() {
+    std::vector<float> lut(PG_NORM_LUT_SIZE);
+    pg_norm_lut_fill(lut.data());
     return lut;
+}
+extern "C" int pg_prep_norm_lut(float* out) {
+    if (!out) { pg_set_error("prep_norm_lut: null argument"); return PG_EINVAL; }
+    pg_norm_lut_fill(out);
+    return PG_OK;
 }
 
 template <typename T>
 static int upload(const std::vector<T>& v, T** dst) {
     PG_HIP(hipMalloc((void**)dst, v.size() * sizeof(T)));
     PG_HIP(hipMemcpy(*dst, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
+    return PG_OK;
+}
+
+// A device copy of the table for the entry points that have no handle (pg_op_im2col, pg_op_x3_im2col with PG_DTYPE_U8 pixels): made at
+// the first use on a device, kept for the life of the process (3 KB per device).
+int pg_norm_lut_device(const float** lut) {
+    static std::mutex mu;
+    static std::map<int, float*> per_device;
+    int dev = 0;
+    PG_HIP(hipGetDevice(&dev));
+    std::lock_guard<std::mutex> lock(mu);
+    auto it = per_device.find(dev);
+    if (it == per_device.end()) {
+        float* d = nullptr;
+        const int rc = upload(make_lut(), &d);
+        if (rc) return rc;
+        it = per_device.emplace(dev, d).first;
+    }
+    *lut = it->second;
     return PG_OK;
 }
 
@@ -220,7 +252,9 @@ __device__ __forceinline__ void prep_v_taps(const uint8_t* __restrict__ p, const
     }
     const int v0 = min(max(s0 >> PREP_BITS, 0), 255), v1 = min(max(s1 >> PREP_BITS, 0), 255), v2 = min(max(s2 >> PREP_BITS, 0), 255);
     const size_t plane = (size_t)PREP_SIZE * PREP_SIZE;
-    if constexpr (sizeof(OUT) == 4) {
+    if constexpr (sizeof(OUT) == 1) {                        // PG_DTYPE_U8: the byte itself, the lookup is the reader's (im2col)
+        o[0] = (uint8_t)v0; o[plane] = (uint8_t)v1; o[2 * plane] = (uint8_t)v2;
+    } else if constexpr (sizeof(OUT) == 4) {
         o[0] = slut[v0]; o[plane] = slut[256 + v1]; o[2 * plane] = slut[512 + v2];
     } else {
         o[0] = f32_to_f16_bits(slut[v0]); o[plane] = f32_to_f16_bits(slut[256 + v1]); o[2 * plane] = f32_to_f16_bits(slut[512 + v2]);
@@ -325,7 +359,7 @@ extern "C" int pg_prep_forward(pg_prep* h, const void* images_u8, int n_images, 
     if (n_images < 0) { pg_set_error("prep_forward: n_images = %d", n_images); return PG_EINVAL; }
     if (n_images == 0) return PG_OK;                       // an empty batch is a no-op: its (empty) buffers may be NULL
     if (!images_u8 || !out || !workspace) { pg_set_error("prep_forward: null argument"); return PG_EINVAL; }
-    if (out_dtype != PG_DTYPE_F32 && out_dtype != PG_DTYPE_F16) { pg_set_error("prep_forward: out dtype must be F32 or F16"); return PG_EINVAL; }
+    if (out_dtype != PG_DTYPE_F32 && out_dtype != PG_DTYPE_F16 && out_dtype != PG_DTYPE_U8) { pg_set_error("prep_forward: out dtype must be F32, F16 or U8"); return PG_EINVAL; }
     size_t need = 0;
     pg_prep_workspace_bytes(h, n_images, &need);
     if (workspace_bytes < need) { pg_set_error("prep_forward: workspace %zu < required %zu bytes", workspace_bytes, need); return PG_ENOMEM; }
@@ -338,6 +372,9 @@ extern "C" int pg_prep_forward(pg_prep* h, const void* images_u8, int n_images, 
     if (rc) return rc;
     if (out_dtype == PG_DTYPE_F32)
         hipLaunchKernelGGL(prep_v_kernel<float>, dim3(PREP_SIZE, n_images), dim3(384), 0, s, (const uint8_t*)workspace, (float*)out,
+                           h->bounds_v, h->kk_v, h->lut, h->ksize_v, h->nrows);
+    else if (out_dtype == PG_DTYPE_U8)
+        hipLaunchKernelGGL(prep_v_kernel<uint8_t>, dim3(PREP_SIZE, n_images), dim3(384), 0, s, (const uint8_t*)workspace, (uint8_t*)out,
                            h->bounds_v, h->kk_v, h->lut, h->ksize_v, h->nrows);
     else
         hipLaunchKernelGGL(prep_v_kernel<uint16_t>, dim3(PREP_SIZE, n_images), dim3(384), 0, s, (const uint8_t*)workspace, (uint16_t*)out,
@@ -444,7 +481,7 @@ extern "C" int pg_prep_ragged_forward(pg_prep_ragged* h, const void* packed_dev,
     if (n < 0) { pg_set_error("%s: n = %d is negative", who, n); return PG_EINVAL; }
     if (n == 0) return PG_OK;                              // an empty batch is a no-op: its (empty) buffers may be NULL
     if (!packed_dev || !items_host || !out || !workspace) { pg_set_error("%s: null argument", who); return PG_EINVAL; }
-    if (out_dtype != PG_DTYPE_F32 && out_dtype != PG_DTYPE_F16) { pg_set_error("%s: out dtype must be F32 or F16", who); return PG_EINVAL; }
+    if (out_dtype != PG_DTYPE_F32 && out_dtype != PG_DTYPE_F16 && out_dtype != PG_DTYPE_U8) { pg_set_error("%s: out dtype must be F32, F16 or U8", who); return PG_EINVAL; }
     if (n > PG_PREP_RAGGED_MAX_IMAGES) { pg_set_error("%s: n = %d, at most %d images per call", who, n, PG_PREP_RAGGED_MAX_IMAGES); return PG_EINVAL; }
     if (((uintptr_t)packed_dev & 15) || ((uintptr_t)workspace & 15)) {
         pg_set_error("%s: the packed buffer and the workspace must be 16-byte aligned", who);
@@ -516,6 +553,8 @@ extern "C" int pg_prep_ragged_forward(pg_prep_ragged* h, const void* packed_dev,
     if (rc) return rc;
     if (out_dtype == PG_DTYPE_F32)
         hipLaunchKernelGGL(prep_ragged_v_kernel<float>, dim3(PREP_SIZE, n), dim3(384), 0, s, packed, (const uint8_t*)ws, tmp_off, (float*)out, h->lut);
+    else if (out_dtype == PG_DTYPE_U8)
+        hipLaunchKernelGGL(prep_ragged_v_kernel<uint8_t>, dim3(PREP_SIZE, n), dim3(384), 0, s, packed, (const uint8_t*)ws, tmp_off, (uint8_t*)out, h->lut);
     else
         hipLaunchKernelGGL(prep_ragged_v_kernel<uint16_t>, dim3(PREP_SIZE, n), dim3(384), 0, s, packed, (const uint8_t*)ws, tmp_off, (uint16_t*)out, h->lut);
     return pg_check_launch("prep_ragged_v");

@@ -240,12 +240,54 @@ __global__ __launch_bounds__(256) void im2col_kernel(const PIX* __restrict__ pix
     }
 }
 
-int pg_im2col_launch(const void* pixels, int pix_dtype, void* out, int out_dtype, int n_images, hipStream_t s) {
+// 8-bit pixels (PG_DTYPE_U8, what pg_prep_forward writes with that type): the same block and the same output, but a line of 336 bytes is
+// read as 84 4-byte words (images are 338 688 bytes and lines 336: every word is aligned when the batch is), and each byte goes through
+// the normalisation table, staged in LDS, to the fp32 value the fp32 instantiation reads from memory -- from there the same T::bits(v).
+// (`out` is the 256-byte aligned patch buffer of the workspace / a tensor: rows of 640 elements keep every pair 4-byte aligned.)
+template <typename T>
+__global__ __launch_bounds__(256) void im2col_u8_kernel(const uint8_t* __restrict__ pix, uint16_t* __restrict__ out,
+                                                        const float* __restrict__ lut) {
+    __shared__ float slut[PG_NORM_LUT_SIZE];
+    for (int i = threadIdx.x; i < PG_NORM_LUT_SIZE; i += 256) slut[i] = lut[i];
+    __syncthreads();
+    const int img = blockIdx.x / 24, py = blockIdx.x % 24;
+    const uint8_t* src = pix + (int64_t)img * 3 * VIT_IMG * VIT_IMG;
+    uint16_t* dst = out + ((int64_t)img * VIT_PATCHES + py * 24) * VIT_PATCH_KPAD;
+    constexpr int WORDS = VIT_IMG / 4;
+    static_assert(VIT_IMG % 4 == 0, "a pixel line is a whole number of 4-byte words");
+    for (int idx = threadIdx.x; idx < 42 * WORDS; idx += 256) {
+        const int line = idx / WORDS, w = idx - line * WORDS;          // line = c*14 + ky
+        const int c = line / 14, ky = line - c * 14;
+        const uint32_t word = *(const uint32_t*)(src + ((int64_t)c * VIT_IMG + py * 14 + ky) * VIT_IMG + w * 4);
+        // two pixels per 4-byte store: a pair starts at an even column, so at an even kx <= 12 -- it never straddles two patches,
+        // and px * 640 + c * 196 + ky * 14 + kx is even
+#pragma unroll
+        for (int b = 0; b < 4; b += 2) {
+            const int xcol = w * 4 + b;
+            const int px = xcol / 14, kx = xcol - px * 14;
+            const uint32_t lo = T::bits(slut[c * 256 + ((word >> (8 * b)) & 0xffu)]);
+            const uint32_t hi = T::bits(slut[c * 256 + ((word >> (8 * b + 8)) & 0xffu)]);
+            *(uint32_t*)(dst + px * VIT_PATCH_KPAD + c * 196 + ky * 14 + kx) = lo | (hi << 16);
+        }
+    }
+    for (int idx = threadIdx.x; idx < 24 * (VIT_PATCH_KPAD - VIT_PATCH_K); idx += 256) {
+        const int px = idx / (VIT_PATCH_KPAD - VIT_PATCH_K), k = idx % (VIT_PATCH_KPAD - VIT_PATCH_K);
+        dst[px * VIT_PATCH_KPAD + VIT_PATCH_K + k] = 0;
+    }
+}
+
+int pg_im2col_launch(const void* pixels, int pix_dtype, void* out, int out_dtype, int n_images, hipStream_t s, const float* norm_lut) {
     if (n_images <= 0) return PG_OK;
     dim3 grid(n_images * 24), block(256);
+    if (out_dtype == PG_DTYPE_U8) { pg_set_error("im2col: PG_DTYPE_U8 is a pixel dtype, not an output dtype (the patch matrix is F16 or BF16)"); return PG_EINVAL; }
     if (out_dtype != PG_DTYPE_F16 && out_dtype != PG_DTYPE_BF16) { pg_set_error("im2col: bad output dtype %d", out_dtype); return PG_EINVAL; }
     const bool h = out_dtype == PG_DTYPE_F16;
-    if (pix_dtype == PG_DTYPE_F32) {
+    if (pix_dtype == PG_DTYPE_U8) {
+        if (!norm_lut) { pg_set_error("im2col: PG_DTYPE_U8 pixels without a normalisation table"); return PG_EINVAL; }
+        if (((uintptr_t)pixels | (uintptr_t)out) & 3) { pg_set_error("im2col: PG_DTYPE_U8 pixels and their patch matrix must be 4-byte aligned"); return PG_EINVAL; }
+        if (h) hipLaunchKernelGGL(im2col_u8_kernel<T_F16>, grid, block, 0, s, (const uint8_t*)pixels, (uint16_t*)out, norm_lut);
+        else hipLaunchKernelGGL(im2col_u8_kernel<T_BF16>, grid, block, 0, s, (const uint8_t*)pixels, (uint16_t*)out, norm_lut);
+    } else if (pix_dtype == PG_DTYPE_F32) {
         if (h) hipLaunchKernelGGL((im2col_kernel<float, T_F16>), grid, block, 0, s, (const float*)pixels, (uint16_t*)out);
         else hipLaunchKernelGGL((im2col_kernel<float, T_BF16>), grid, block, 0, s, (const float*)pixels, (uint16_t*)out);
     } else if (pix_dtype == PG_DTYPE_BF16) {

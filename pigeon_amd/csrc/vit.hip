@@ -2,7 +2,7 @@
 // vit_weights.hip; the exact mode: vit_precise.hip; the rest of the exported C ABI of include/pigeon_hip.h: abi.hip).
 //
 // Forward pass for a chunk of n images (M = 577 n rows), all launches asynchronous on the caller's stream:
-//   im2col            pixels (n,3,336,336) -> P (576 n, 640) bf16
+//   im2col            pixels (n,3,336,336; fp32 / fp16 / bf16, or bytes looked up in the handle's normalisation table) -> P (576 n, 640) bf16
 //   gemm<PATCH>       P x Wpatch^T (+ position)            -> X rows 1..576 of every image (fp32 residual stream)
 //   pre_layernorm     class token + position[0], LN in place on X
 //   24 x { LN1 -> Xn bf16 ; gemm<QKV> -> QKV bf16 ; attention -> O bf16 (aliases Xn) ; gemm<RESID>(O, Wo) -> X
@@ -170,7 +170,7 @@ static int vit_forward_chunk(pg_vit* h, const void* pixels, int pix_dtype, int n
     const FastWs w = fast_ws((size_t)M, h->ln_fold);
     float* X = (float*)(ws + w.X);
     uint16_t* big = (uint16_t*)(ws + w.big);                   // the im2col patches P
-    { ProfScope p(h, s, PROF_IM2COL); RC(pg_im2col_launch(pixels, pix_dtype, big, h->cfg.mma_dtype, n, s)); }
+    { ProfScope p(h, s, PROF_IM2COL); RC(pg_im2col_launch(pixels, pix_dtype, big, h->cfg.mma_dtype, n, s, h->norm_lut)); }
     RC(vit_forward_body_graphed(h, n, ws, s));
     { ProfScope p(h, s, PROF_TOKEN_MEAN); RC(pg_token_mean_launch(X, emb_out, n, s)); }
     if (hidden_out) PG_HIP(hipMemcpyAsync(hidden_out, X, (size_t)M * VIT_HIDDEN * 4, hipMemcpyDeviceToDevice, s));

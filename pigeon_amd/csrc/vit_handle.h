@@ -32,6 +32,7 @@ struct pg_vit {
     uint16_t* wpatch = nullptr;                           // [1024][640] bf16 (K zero padded)
     uint16_t* wpatch3 = nullptr;                          // exact mode: [1024][3 * 640] split-fp16 triple
     float *cls = nullptr, *pos = nullptr, *preg = nullptr, *preb = nullptr;
+    float* norm_lut = nullptr;                            // [3][256] the normalisation table PG_DTYPE_U8 pixels are looked up in (im2col)
     std::vector<LayerW> layers;
     // two half-batches on two HIP streams (env PIGEON_VIT_STREAMS=2): the tail of a persistent GEMM of one half -- a partial last
     // round with a handful of CUs busy -- is filled by the other half's next kernel instead of idling the chip
@@ -129,7 +130,8 @@ static inline int vit_forward_check(const char* who, const pg_vit* h, bool preci
     if (n_images < 0) { pg_set_error("%s: n_images = %d", who, n_images); return PG_EINVAL; }
     if (n_images == 0) return PG_OK;
     if (!pixels || !emb_out || !workspace) { pg_set_error("%s: null argument", who); return PG_EINVAL; }
-    if (pix_dtype != PG_DTYPE_F32 && pix_dtype != PG_DTYPE_BF16 && pix_dtype != PG_DTYPE_F16) { pg_set_error("%s: bad pixel dtype", who); return PG_EINVAL; }
+    if (pix_dtype != PG_DTYPE_F32 && pix_dtype != PG_DTYPE_BF16 && pix_dtype != PG_DTYPE_F16 && pix_dtype != PG_DTYPE_U8) { pg_set_error("%s: bad pixel dtype", who); return PG_EINVAL; }
+    if (pix_dtype == PG_DTYPE_U8 && ((uintptr_t)pixels & 15) != 0) { pg_set_error("%s: PG_DTYPE_U8 pixels must be 16-byte aligned", who); return PG_EINVAL; }
     if (workspace_bytes < needb) { pg_set_error("%s: workspace %zu < required %zu bytes", who, workspace_bytes, needb); return PG_ENOMEM; }
     if (((uintptr_t)workspace & 255) != 0) { pg_set_error("%s: workspace must be 256-byte aligned", who); return PG_EINVAL; }
     return PG_OK;
@@ -138,7 +140,7 @@ static inline int vit_forward_check(const char* who, const pg_vit* h, bool preci
 // Where the images from `first` on start in the caller's pixel, embedding and (may be NULL) hidden-state buffers.
 struct ChunkIO { const void* pixels; float *emb, *hidden; };
 static inline ChunkIO chunk_io(const void* pixels, int pix_dtype, float* emb_out, float* hidden_out, int first) {
-    const size_t img_bytes = (size_t)3 * VIT_IMG * VIT_IMG * (pix_dtype == PG_DTYPE_F32 ? 4 : 2);
+    const size_t img_bytes = (size_t)3 * VIT_IMG * VIT_IMG * (pix_dtype == PG_DTYPE_F32 ? 4 : pix_dtype == PG_DTYPE_U8 ? 1 : 2);
     return {(const char*)pixels + (size_t)first * img_bytes, emb_out + (size_t)first * VIT_HIDDEN,
             hidden_out ? hidden_out + (size_t)first * VIT_TOKENS * VIT_HIDDEN : nullptr};
 }

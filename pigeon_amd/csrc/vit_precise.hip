@@ -121,7 +121,7 @@ static int vit_precise_chunk(pg_vit* h, const void* pixels, int pix_dtype, int n
     auto gemm = [&](const uint16_t* A3, const uint16_t* W3, const float* bias, float* dst, bool resid, int N, int K, int S) -> int {
         return precise_gemm(A3, 3 * K, W3, 3 * K, bias, PP, dst, resid, (int)M, N, np * K, S, s);
     };
-    RC(pg_x3_im2col_launch(pixels, pix_dtype, G3, n, s));
+    RC(pg_x3_im2col_launch(pixels, pix_dtype, G3, n, s, h->norm_lut));
     RC(pg_gemm_launch(dt, G3, 3 * VIT_PATCH_KPAD, h->wpatch3, 3 * VIT_PATCH_KPAD, nullptr, X, D, n * VIT_PATCHES, D, np * VIT_PATCH_KPAD,
                       EPI_PATCH, 1.f, 0, h->pos, V, s));
     RC(pg_preln_launch(X, h->cls, h->pos, h->preg, h->preb, M, eps, s));

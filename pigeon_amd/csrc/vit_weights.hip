@@ -191,6 +191,11 @@ extern "C" int pg_vit_finalize(pg_vit* h) {
     RC(put(h, "embeddings.position_embedding.weight", VIT_TOKENS, D, &h->pos));
     RC(put(h, "pre_layrnorm.weight", 1, D, &h->preg));
     RC(put(h, "pre_layrnorm.bias", 1, D, &h->preb));
+    {   // the table 8-bit pixels (PG_DTYPE_U8) are looked up in: not a parameter, not in the fingerprint
+        float lut[PG_NORM_LUT_SIZE];
+        pg_norm_lut_fill(lut);
+        RC(upload(h, lut, (size_t)PG_NORM_LUT_SIZE, &h->norm_lut));
+    }
     for (int l = 0; l < h->cfg.layers; ++l) {
         LayerW& L = h->layers[l];
         const std::string pre = "encoder.layers." + std::to_string(l) + ".";

@@ -180,18 +180,20 @@ class DeferredExact:
 
     # ------------------------------------------------------------------------------------------------ one step
     @torch.no_grad()
-    def submit(self, pixel_values=None, embedding=None, index=None, meta=None) -> List[dict]:
+    def submit(self, pixel_values=None, embedding=None, index=None, meta=None, pixel_bytes=None) -> List[dict]:
         """Queue one step.  Returns the results that became final (possibly none, possibly several), oldest first; each is a dict of
         the gathered batch's tensors (rank-major; copies, valid for as long as the caller keeps them): embedding, index, preds_geocell,
         preds_LLH, topk_indices, topk_values [, refined_LLH, refined_geocell], certain (bool), cause, exact (bool: re-encoded rows),
-        plus `step`, `meta` (what the caller passed), `state` (this rank's rows in the form `SuperGuessr.package` takes)."""
+        plus `step`, `meta` (what the caller passed), `state` (this rank's rows in the form `SuperGuessr.package` takes).
+        `pixel_bytes` (instead of pixel_values / embedding): uint8 (B,12,336,336) or (B,3,336,336) 8-bit pixels; the queue then carries
+        byte rows (a quarter of the fp32 allocation) and the exact pass encodes from them."""
         model, comm, ops = self.model, self.comm, self.ops
         marks = [] if self.marks is not None else None
         settled = []
         if self.dev is None:
             self.dev = model.cell_layer.weight.device
         self._mark(marks)
-        st = model.encode_head(pixel_values, embedding)
+        st = model.encode_head(pixel_values, embedding) if pixel_bytes is None else model.encode_head(pixel_values, embedding, pixel_bytes=pixel_bytes)
         b = int(st['tol'].shape[0])
         px = st.get('pixel_values')
         if b == 0:
@@ -258,7 +260,7 @@ class DeferredExact:
             px_rows = px.reshape((b, -1)).contiguous()            # (a strided view handed in by the caller: one copy; else free)
             if self.q_pixels is None or self.px_shape != (tuple(px_rows.shape[1:]), px_rows.dtype):
                 if self.q_pixels is not None:
-                    # another pixel dtype / geometry (e.g. fp16 pixels from the GPU preprocessing after fp32 tensors): settle what is
+                    # another pixel dtype / geometry (e.g. fp16 pixels from the GPU preprocessing after fp32 tensors, or bytes after floats): settle what is
                     # queued in the old one, then start a new queue (every rank sees the same change in the same step)
                     settled = settled + self.flush()
                     self.counters.zero_()

@@ -125,7 +125,7 @@ def compute_geoguessr_metrics(results, scaler=None, countries=None) -> Dict[str,
 
 @torch.no_grad()
 def certain_forward(model: SuperGuessr, refiner: Optional[ProtoRefiner], pixel_values=None, embedding=None, labels=None,
-                    labels_clf=None, labels_multi_task=None, labels_climate=None, labels_month=None, **_unused):
+                    labels_clf=None, labels_multi_task=None, labels_climate=None, labels_month=None, pixel_bytes=None, **_unused):
     """`model(**data)` followed by `refiner(...)` with the reference's discrete outputs (a z ~ 4 statistical statement for the samples called certain, pigeon_amd/certainty.py): one fast pass, the tolerance of every
     discrete decision downstream of the embedding -- the top-1 cell (pg_head_certainty) and, with a refiner, the winning candidate,
     the candidate-set boundary, the nearest prototype and the farthest member (pg_refine_certainty) -- and ONE exact pass
@@ -137,8 +137,12 @@ def certain_forward(model: SuperGuessr, refiner: Optional[ProtoRefiner], pixel_v
     reference's; cause (B,) int32: why a sample was not certain after the fast pass; reencoded (n,) int64; head_tol, refine_tol,
     refine_code (B,) or None; boundary_checked; refined_LLH (B,2) f32 / refined_geocell (B,) i64: the refinement's result -- the
     caller need not run the refiner again; multi-task models: aux_tol (B,) f32 the tolerance of the climate and month argmaxes,
-    aux_code (B,) i32 which class sets it -- `head_tol` is already the minimum over the geocell, climate and month decisions)."""
-    res = model.engine(refiner).submit(pixel_values, embedding)[0]
+    aux_code (B,) i32 which class sets it -- `head_tol` is already the minimum over the geocell, climate and month decisions).
+    `pixel_bytes` (instead of pixel_values / embedding): uint8 (B,12,336,336) or (B,3,336,336) 8-bit pixels (`SuperGuessr.encode_head`);
+    every output and every `info` entry equals what the fp32 pixels `table[bytes]` give."""
+    if pixel_bytes is not None:
+        model._check_pixel_bytes(pixel_bytes, pixel_values, embedding)
+    res = model.engine(refiner).submit(pixel_values, embedding, pixel_bytes=pixel_bytes)[0]
     out = as_model_output(model, res, labels, labels_clf, labels_multi_task, labels_climate, labels_month)
     st = res['state']
     info = dict(certain=st['certain'], cause=st['cause'], head_tol=st['tol'], refine_tol=st.get('refine_tol'),
@@ -151,12 +155,69 @@ def certain_forward(model: SuperGuessr, refiner: Optional[ProtoRefiner], pixel_v
     return out, info
 
 
+IMAGE_KEYS = ('image', 'image_2', 'image_3', 'image_4')
+
+
+class ImageEvalDataset:
+    """The reference's `EvalDataset` (dataset_creation/benchmark/eval_dataset.py) for `evaluate_model`: wraps anything indexable whose
+    items hold a raw `image` column, or the four views `image`, `image_2`, `image_3`, `image_4` (PIL images or uint8 (H,W,3) arrays
+    of any sizes).  Where the reference's workers run the CLIP processor per item and ship 12 x 336 x 336 floats, a worker here only
+    decodes and packs (`packing.pack_images`: the raw views in one uint8 buffer) and passes every other column (`labels`,
+    `labels_clf`, ...) through; `collate` joins a batch's items into ONE `PackedImages`, and the process that owns the GPU resizes
+    the whole mixed-size batch to 8-bit pixels in one ragged call (`preprocess`) and submits them as `pixel_bytes`.  String keys are
+    column reads of the wrapped dataset (`dataset['labels']`, as `evaluate_model` collects the labels for the metrics)."""
+
+    def __init__(self, dataset):
+        self.dataset = dataset
+
+    def __len__(self) -> int:
+        return len(self.dataset)
+
+    def __getitem__(self, idx):
+        if isinstance(idx, str):
+            return self.dataset[idx]
+        from .packing import pack_images
+        item = self.dataset[idx]
+        if 'image' not in item:
+            raise KeyError("ImageEvalDataset: items need an 'image' column (or 'image', 'image_2', 'image_3', 'image_4')")
+        views = [item[k] for k in (IMAGE_KEYS if 'image_2' in item else IMAGE_KEYS[:1])]
+        out = {k: v for k, v in item.items() if 'image' not in k}              # (the reference drops every image column the same way)
+        out['images'] = pack_images([v.numpy() if torch.is_tensor(v) else v for v in views])
+        return out
+
+    @staticmethod
+    def collate(batch):
+        """collate_fn: a list of items -> {'images': one PackedImages of the batch's views in item order, 'views': views per item,
+        every other key: torch's default collation}."""
+        from torch.utils.data import default_collate
+        from .packing import concat_packed
+        views = {len(b['images']) for b in batch}
+        if len(views) != 1:
+            raise ValueError(f'ImageEvalDataset: items of one batch hold {sorted(views)} views; every item must have the same number')
+        out = default_collate([{k: v for k, v in b.items() if k != 'images'} for b in batch])
+        out['images'] = concat_packed([b['images'] for b in batch])
+        out['views'] = views.pop()
+        return out
+
+    @staticmethod
+    def preprocess(data: dict, device) -> dict:
+        """Main process: the batch's `PackedImages` -> `pixel_bytes` (B, 3 * views, 336, 336) uint8 on the device, by the ragged
+        GPU preprocessing; the other keys as they are."""
+        from .clip_embedder import gpu_preprocess
+        data = dict(data)
+        packed, views = data.pop('images'), int(data.pop('views'))
+        px = gpu_preprocess(packed, device, torch.uint8)
+        data['pixel_bytes'] = px.reshape((len(packed) // views, 3 * views, 336, 336))
+        return data
+
+
 def evaluate_model(model: SuperGuessr, dataset, metrics: Optional[Callable] = None, train_args=None,
                    refiner: Optional[ProtoRefiner] = None, yfcc: bool = False, writer=None, step: int = 0,
                    batch_size: Optional[int] = None, num_workers: int = 0):
     """reference training/train_eval_loop.py:35-161 (eval loop :77-112).
 
-    dataset items are dicts of forward() keyword arguments (pixel_values | embedding, labels, labels_clf, ...).
+    dataset items are dicts of forward() keyword arguments (pixel_values | pixel_bytes | embedding, labels, labels_clf, ...), or
+    -- an `ImageEvalDataset` -- raw images of any sizes, which are resized to `pixel_bytes` here, a batch at a time on the GPU.
     Returns the dict of concatenated numpy results; if `metrics` is given it is called with the same 11-tuple
     the reference builds (:138-140) and its dict is merged in.
     """
@@ -164,7 +225,9 @@ def evaluate_model(model: SuperGuessr, dataset, metrics: Optional[Callable] = No
     logger.warning('Starting evaluation ...')
     if batch_size is None:
         batch_size = getattr(train_args, 'per_device_eval_batch_size', EVAL_BATCH_SIZE_PER_GPU)
-    eval_data = DataLoader(dataset, batch_size, shuffle=False, pin_memory=False, num_workers=num_workers)
+    from_images = isinstance(dataset, ImageEvalDataset)
+    eval_data = DataLoader(dataset, batch_size, shuffle=False, pin_memory=False, num_workers=num_workers,
+                           collate_fn=ImageEvalDataset.collate if from_images else None)
     model.eval()
     if refiner is not None:
         refiner.eval()
@@ -210,9 +273,11 @@ def evaluate_model(model: SuperGuessr, dataset, metrics: Optional[Callable] = No
 
     with torch.no_grad():
         for data in eval_data:
+            if from_images:
+                data = ImageEvalDataset.preprocess(data, model.cell_layer.weight.device)
             # :80 `model(**data)` and :98 `refiner(...)`, with what the refiner will consume checked as well
             keep = dict({k: data.get(k) for k in LABEL_KEYS}, n_keys=len(data))
-            collect(engine.submit(data.get('pixel_values'), data.get('embedding'), meta=keep))
+            collect(engine.submit(data.get('pixel_values'), data.get('embedding'), meta=keep, pixel_bytes=data.get('pixel_bytes')))
         collect(engine.flush())
     dropped = engine.check_nothing_dropped()
     if dropped:
@@ -420,14 +485,15 @@ class PanoramaPipeline:
         return done
 
     @torch.no_grad()
-    def submit(self, pixel_values: torch.Tensor, index: Optional[torch.Tensor] = None, meta=None):
-        return self._note(self.engine.submit(pixel_values, index=index, meta=meta))
+    def submit(self, pixel_values: torch.Tensor = None, index: Optional[torch.Tensor] = None, meta=None, pixel_bytes: torch.Tensor = None):
+        return self._note(self.engine.submit(pixel_values, index=index, meta=meta, pixel_bytes=pixel_bytes))
 
     @torch.no_grad()
     def flush(self):
         return self._note(self.engine.flush())
 
     @torch.no_grad()
-    def step(self, pixel_values: torch.Tensor, index: Optional[torch.Tensor] = None):
-        done = self.submit(pixel_values, index) + self.flush()
+    def step(self, pixel_values: torch.Tensor = None, index: Optional[torch.Tensor] = None, pixel_bytes: torch.Tensor = None):
+        """`pixel_bytes` (instead of pixel_values): uint8 (B,12,336,336) / (B,3,336,336) 8-bit pixels, a quarter of the resident batch."""
+        done = self.submit(pixel_values, index, pixel_bytes=pixel_bytes) + self.flush()
         return done[-1]

@@ -23,6 +23,10 @@ def _stream():
 
 _T16 = {torch.float16: _lib.PG_DTYPE_F16, torch.bfloat16: _lib.PG_DTYPE_BF16}
 _PIXDT = {torch.float32: _lib.PG_DTYPE_F32, torch.float16: _lib.PG_DTYPE_F16, torch.bfloat16: _lib.PG_DTYPE_BF16}
+# what the encoder and the im2col read, what the resize writes: the float formats plus the 8-bit pixel (the byte in front of the
+# normalisation table, PG_DTYPE_U8)
+_PIXIN = {**_PIXDT, torch.uint8: _lib.PG_DTYPE_U8}
+_PREP_OUT = {torch.float32: _lib.PG_DTYPE_F32, torch.float16: _lib.PG_DTYPE_F16, torch.uint8: _lib.PG_DTYPE_U8}
 _PG2T = {_lib.PG_DTYPE_F16: torch.float16, _lib.PG_DTYPE_BF16: torch.bfloat16, _lib.PG_DTYPE_F32: torch.float32}
 
 
@@ -158,8 +162,9 @@ def attention(qkv: torch.Tensor, n_images: int) -> torch.Tensor:
 
 def im2col(pixels: torch.Tensor, out_dtype: torch.dtype = torch.float16) -> torch.Tensor:
     _dev(pixels)
+    _shape(pixels, "pixels", None, 3, 336, 336)
     n = pixels.shape[0]
-    dt = _PIXDT[pixels.dtype]
+    dt = _PIXIN[pixels.dtype]
     out = torch.empty((n * PATCHES, KPAD), dtype=out_dtype, device=pixels.device)
     check(load().pg_op_im2col(_p(pixels), dt, _p(out), _dt16(out), n, _stream()), "pg_op_im2col")
     return out
@@ -398,6 +403,22 @@ def tune_region_wave_edges(max_edges: int) -> None:
 
 
 # ----------------------------------------------------------------------------------------- image preprocessing
+def norm_lut() -> torch.Tensor:
+    """pg_prep_norm_lut: the (3, 256) fp32 normalisation table ((v / 255) - mean[c]) / std[c], every value a pixel can take.  A host
+    tensor from a host call (no GPU needed); `norm_lut()[c][bytes]` is the fp32 pixel of a byte of channel c."""
+    out = (C.c_float * 768)()
+    check(load().pg_prep_norm_lut(out), "pg_prep_norm_lut")
+    return torch.tensor(list(out), dtype=torch.float32).view(3, 256)
+
+
+def bytes_to_pixels(pixel_bytes: torch.Tensor) -> torch.Tensor:
+    """(..., 3, 336, 336) uint8 -> fp32 pixel values through the table: what the encoder computes from, for tests and tools (the
+    product path never materialises it)."""
+    lut = norm_lut().to(pixel_bytes.device)
+    idx = pixel_bytes.long() + (torch.arange(3, device=pixel_bytes.device) * 256).view(3, 1, 1)
+    return lut.view(-1)[idx]
+
+
 class Preprocessor:
     """CLIP preprocessing on the GPU for one input geometry: (N,H,W,3) uint8 RGB -> (N,3,336,336) pixel_values,
     bit-exact with `CLIPProcessor(images=pil)` (Pillow fixed-point bicubic + numpy float32 normalisation)."""
@@ -416,15 +437,15 @@ class Preprocessor:
         _dev(images_u8, torch.uint8)
         if images_u8.dim() != 4 or tuple(images_u8.shape[1:]) != (self.in_h, self.in_w, 3):
             raise _lib.PigeonHipError(f"images must be (N,{self.in_h},{self.in_w},3) uint8, got {tuple(images_u8.shape)}")
-        if out_dtype not in (torch.float32, torch.float16):
-            raise _lib.PigeonHipError("preprocess output dtype must be float32 or float16")
+        if out_dtype not in _PREP_OUT:
+            raise _lib.PigeonHipError("preprocess output dtype must be float32 or float16 (or uint8: the resized bytes)")
         n = images_u8.shape[0]
         need = C.c_size_t()
         check(load().pg_prep_workspace_bytes(self._h, n, C.byref(need)), "pg_prep_workspace_bytes")
         if self._ws is None or self._ws.numel() < need.value or self._ws.device != images_u8.device:
             self._ws = torch.empty(need.value, dtype=torch.uint8, device=images_u8.device)
         out = torch.empty((n, 3, 336, 336), dtype=out_dtype, device=images_u8.device)
-        check(load().pg_prep_forward(self._h, _p(images_u8), n, _p(out), _PIXDT[out_dtype], _p(self._ws), self._ws.numel(),
+        check(load().pg_prep_forward(self._h, _p(images_u8), n, _p(out), _PREP_OUT[out_dtype], _p(self._ws), self._ws.numel(),
                                      _stream()), "pg_prep_forward")
         return out
 
@@ -493,8 +514,8 @@ class RaggedPreprocessor:
             raise _lib.PigeonHipError(f"packed buffer must be 1-D uint8 of {plan.packed_bytes} bytes, got {tuple(packed_u8.shape)}")
         if packed_u8.device.index != self.device:
             raise _lib.PigeonHipError(f"packed buffer is on {packed_u8.device}, the preprocessor on cuda:{self.device}")
-        if out_dtype not in (torch.float32, torch.float16):
-            raise _lib.PigeonHipError("preprocess output dtype must be float32 or float16")
+        if out_dtype not in _PREP_OUT:
+            raise _lib.PigeonHipError("preprocess output dtype must be float32 or float16 (or uint8: the resized bytes)")
         out = torch.empty((plan.n, 3, 336, 336), dtype=out_dtype, device=packed_u8.device)
         if plan.n == 0:
             return out
@@ -502,7 +523,7 @@ class RaggedPreprocessor:
             self._ws = torch.empty(plan.workspace_bytes, dtype=torch.uint8, device=packed_u8.device)
         if not header_written:
             packed_u8[:plan.header_bytes].copy_(torch.from_numpy(plan.header().copy()))
-        check(load().pg_prep_ragged_forward(self._h, _p(packed_u8), plan.packed_bytes, plan.items, plan.n, _p(out), _PIXDT[out_dtype],
+        check(load().pg_prep_ragged_forward(self._h, _p(packed_u8), plan.packed_bytes, plan.items, plan.n, _p(out), _PREP_OUT[out_dtype],
                                             _p(self._ws), self._ws.numel(), _stream()), "pg_prep_ragged_forward")
         return out
 
@@ -572,18 +593,19 @@ class VitEncoder:
         return self._ws
 
     def forward(self, pixels: torch.Tensor, return_hidden: bool = False):
-        """pixels (N,3,336,336) fp32/bf16 on the device -> (N,1024) fp32 [, (N,577,1024) fp32]."""
+        """pixels (N,3,336,336) fp32/fp16/bf16, or uint8 (the bytes Preprocessor writes with out_dtype=torch.uint8: looked up in the
+        normalisation table by the im2col), on the device -> (N,1024) fp32 [, (N,577,1024) fp32]."""
         _dev(pixels)
         if pixels.dim() != 4 or tuple(pixels.shape[1:]) != (3, 336, 336):
             raise _lib.PigeonHipError(f"pixels must be (N,3,336,336), got {tuple(pixels.shape)}")
-        if pixels.dtype not in _PIXDT:
-            raise _lib.PigeonHipError("pixels must be fp32, fp16 or bf16")
+        if pixels.dtype not in _PIXIN:
+            raise _lib.PigeonHipError("pixels must be fp32, fp16 or bf16, or uint8 bytes")
         n = pixels.shape[0]
         ws = self._workspace(n)
         off = (-ws.data_ptr()) % 256
         emb = torch.empty((n, HIDDEN), dtype=torch.float32, device=pixels.device)
         hid = torch.empty((n, TOKENS, HIDDEN), dtype=torch.float32, device=pixels.device) if return_hidden else None
-        dt = _PIXDT[pixels.dtype]
+        dt = _PIXIN[pixels.dtype]
         check(load().pg_vit_forward_hidden(self._h, _p(pixels), dt, n, _p(emb), _p(hid),
                                            C.c_void_p(ws.data_ptr() + off), ws.numel() - off, _stream()),
               "pg_vit_forward")
@@ -599,8 +621,8 @@ class VitEncoder:
         _dev(pixels)
         if pixels.dim() != 4 or tuple(pixels.shape[1:]) != (3, 336, 336):
             raise _lib.PigeonHipError(f"pixels must be (N,3,336,336), got {tuple(pixels.shape)}")
-        if pixels.dtype not in _PIXDT:
-            raise _lib.PigeonHipError("pixels must be fp32, fp16 or bf16")
+        if pixels.dtype not in _PIXIN:
+            raise _lib.PigeonHipError("pixels must be fp32, fp16 or bf16, or uint8 bytes")
         n = pixels.shape[0]
         need = C.c_size_t()
         check(load().pg_vit_precise_workspace_bytes(self._h, n, C.byref(need)), "pg_vit_precise_workspace_bytes")
@@ -613,7 +635,7 @@ class VitEncoder:
             _dev(out, torch.float32); _shape(out, "out", n, HIDDEN)
         emb = out if out is not None else torch.empty((n, HIDDEN), dtype=torch.float32, device=pixels.device)
         hid = torch.empty((n, TOKENS, HIDDEN), dtype=torch.float32, device=pixels.device) if return_hidden else None
-        check(load().pg_vit_forward_precise(self._h, _p(pixels), _PIXDT[pixels.dtype], n, _p(emb), _p(hid),
+        check(load().pg_vit_forward_precise(self._h, _p(pixels), _PIXIN[pixels.dtype], n, _p(emb), _p(hid),
                                             C.c_void_p(ws.data_ptr() + off), ws.numel() - off, _stream()), "pg_vit_forward_precise")
         return (emb, hid) if return_hidden else emb
 
@@ -1069,7 +1091,7 @@ def x3_im2col(pixels: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch
     _dev(out, torch.float16)
     if out.numel() < n * PATCHES * 3 * KPAD:
         raise _lib.PigeonHipError("x3_im2col: output too small")
-    check(load().pg_op_x3_im2col(_p(pixels), _PIXDT[pixels.dtype], _p(out), n, _stream()), "pg_op_x3_im2col")
+    check(load().pg_op_x3_im2col(_p(pixels), _PIXIN[pixels.dtype], _p(out), n, _stream()), "pg_op_x3_im2col")
     return out
 
 

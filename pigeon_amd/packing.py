@@ -104,3 +104,14 @@ def pack_images(images) -> PackedImages:
     buf = np.zeros(total, dtype=np.uint8)
     pack_into(arrs, offs, buf)
     return PackedImages(torch.from_numpy(buf), torch.tensor(sizes, dtype=torch.int32).reshape(-1, 2))
+
+
+def concat_packed(parts: Sequence[PackedImages]) -> PackedImages:
+    """Several PackedImages (e.g. what DataLoader workers packed per item) -> ONE holding all their images in order: the images are
+    copied to their places in a new buffer laid out for the whole list (the descriptor region grows with the count, so the parts'
+    buffers cannot simply be joined)."""
+    sizes = [s for p in parts for s in p.size_list()]
+    offs, total = packed_layout(sizes)
+    buf = np.zeros(total, dtype=np.uint8)
+    pack_into([p.image(i) for p in parts for i in range(len(p))], offs, buf)
+    return PackedImages(torch.from_numpy(buf), torch.tensor(sizes, dtype=torch.int32).reshape(-1, 2))

@@ -23,7 +23,7 @@ from torch.nn.parameter import Parameter
 from . import hip_ops
 from .certainty import SAFETY, CalibrationError, Certainty, require_fingerprint
 from .geo_utils import haversine_matrix, smooth_labels
-from .clip_embedder import HipCLIPVisionModel
+from .clip_embedder import HipCLIPVisionModel, check_pixel_bytes, exclusive_pixel_bytes
 from .config import CLIP_EMBED_DIM, GEOCELL_PATH, GEOCELL_PATH_YFCC
 from .utils import ModelOutput, TopK, resolve_name
 
@@ -246,6 +246,25 @@ class SuperGuessr(nn.Module):
             self._hip_base.to(self.cell_layer.weight.device)
         return self._hip_base
 
+    def _embed(self, px: Tensor, exact: bool = False, out: Tensor = None) -> Tensor:
+        """(N,3,336,336) device pixels, float or uint8 bytes (what `encode_head` made of `pixel_bytes`), through the fast or exact encoder."""
+        enc = self._encoder()
+        kw = {'pixel_bytes': px} if px.dtype == torch.uint8 else {'pixel_values': px}
+        return enc.embed_precise(out=out, **kw) if exact else enc.embed(**kw)
+
+    def _check_pixel_bytes(self, pixel_bytes, pixel_values=None, embedding=None) -> None:
+        """`pixel_bytes` by name, before anything else happens: alone, uint8 (B,12,336,336) [panorama] or (B,3,336,336), contiguous."""
+        if pixel_bytes is None:
+            return
+        exclusive_pixel_bytes(pixel_bytes, pixel_values=pixel_values, embedding=embedding)
+        check_pixel_bytes(pixel_bytes)
+        if self.base_model is None:
+            raise ValueError('pixel_bytes needs a base model: this SuperGuessr takes embeddings')
+        views = 12 if self.panorama else 3
+        if pixel_bytes.shape[1] != views:
+            raise ValueError(f'pixel_bytes must be (B,{views},336,336) for a {"panorama" if self.panorama else "single-image"} model, '
+                             f'got shape {tuple(pixel_bytes.shape)}')
+
     def _assert_requirements(self, pixel_values=None, embedding=None, heading=None):
         if self.base_model is not None:
             assert pixel_values is not None, 'Parameter "pixel_values" must be supplied if model has a base model.'
@@ -322,14 +341,19 @@ class SuperGuessr(nn.Module):
         return o
 
     @torch.no_grad()
-    def encode_head(self, pixel_values: Tensor = None, embedding: Tensor = None) -> dict:
+    def encode_head(self, pixel_values: Tensor = None, embedding: Tensor = None, pixel_bytes: Tensor = None) -> dict:
         """Fast pass: ViT + token mean (:395-398), head, tolerance of the top-1.  No re-encode.  Returns the step's STATE: a dict
         with `embedding` (as ModelOutput carries it), `head_in`, the head outputs over k + extra candidates (`topk_values`,
         `topk_indices`, `logits`, `preds_geocell`, `preds_LLH`), `tol`, `certain`, `exact` (rows on the exact tier: none yet) and
         `pixel_values` (the reshaped device pixels, or None).  `package` turns it into the reference's outputs; pigeon_amd.deferred.DeferredExact
-        settles the rows that are not certain."""
+        settles the rows that are not certain.  `pixel_bytes` (uint8 (B,12,336,336) / (B,3,336,336), instead of the other two): the
+        8-bit pixels in front of the normalisation table; the state's `pixel_values` then holds those bytes, and the exact tier
+        re-encodes from them."""
+        self._check_pixel_bytes(pixel_bytes, pixel_values, embedding)
         dev = self.cell_layer.weight.device
         px = None
+        if pixel_bytes is not None:
+            pixel_values = pixel_bytes
         if self.panorama and pixel_values is not None:                          # :386-388
             num_samples = pixel_values.size(0)
             pixel_values = pixel_values.reshape((num_samples * 4, 3, 336, 336))
@@ -337,11 +361,13 @@ class SuperGuessr(nn.Module):
             if pixel_values.dim() > 4:
                 pixel_values = pixel_values.squeeze(1)                          # :392-393
             px = pixel_values.to(dev)
+            if pixel_bytes is None and px.dtype == torch.uint8:
+                px = px.float()                          # a uint8 tensor under the name pixel_values is numbers, as it always was: bytes come as pixel_bytes
             if self.exact_top1 and self.margin_autocalibrate and not self.certainty.calibrated:
                 self._autocalibrate(px)
             # a tower on which the calibration measured the 16-bit path OUTSIDE the embedding contract: every sample through the exact encoder
             exact_tier = bool(self.certainty.force_exact and self.exact_top1)
-            embedding = self._encoder().embed_precise(px) if exact_tier else self._encoder().embed(px)   # :395-398 (ViT + token mean)
+            embedding = self._embed(px, exact=exact_tier)                       # :395-398 (ViT + token mean)
             bias = None if exact_tier else self.certainty.bias_on(dev)
             if bias is not None:
                 # the 16-bit encoder's measured systematic error, taken out of every image's embedding (pigeon_amd/certainty.py `debias`):
@@ -374,11 +400,11 @@ class SuperGuessr(nn.Module):
         n = sum(int(t.shape[0]) for t in pixel_rows)
         dev = self.cell_layer.weight.device
         emb = torch.empty((n * P, CLIP_EMBED_DIM), dtype=torch.float32, device=dev)
-        enc, off = self._encoder(), 0
+        off = 0
         for t in pixel_rows:
             m = int(t.shape[0])
             if m:
-                enc.embed_precise(t.reshape((m * P, 3, 336, 336)), out=emb[off * P:(off + m) * P])
+                self._embed(t.reshape((m * P, 3, 336, 336)), exact=True, out=emb[off * P:(off + m) * P])
             off += m
         if self.panorama:
             emb = emb.reshape((n, P, CLIP_EMBED_DIM))
@@ -464,21 +490,23 @@ class SuperGuessr(nn.Module):
 
     def forward(self, pixel_values: Tensor = None, embedding: Tensor = None, heading: Tensor = None,
                 labels: Tensor = None, labels_clf: Tensor = None, labels_multi_task: Tensor = None,
-                labels_climate: Tensor = None, labels_month: Tensor = None, index: Tensor = None):
+                labels_climate: Tensor = None, labels_month: Tensor = None, index: Tensor = None, pixel_bytes: Tensor = None):
         """Inference branch of reference models/super_guessr.py:350-483.
 
         pixel_values (B,12,336,336) [panorama] or (B,3,336,336); or embedding (B,4,1024)/(B,1024).
         Returns ModelOutput (or, with serving=True in eval mode, the (pred_LLH, topk, embedding) tuple -- multi-task:
         (pred_LLH, topk, preds_mt, embedding) --, :462-466).  `heading` is ignored: the only configuration that accepts
         heading=True is the one in which the reference ignores it too (:273-274).
+        `pixel_bytes` (instead of pixel_values / embedding): uint8 (B,12,336,336) or (B,3,336,336), see `encode_head`.
         """
-        self._assert_requirements(pixel_values, embedding, heading)
+        self._check_pixel_bytes(pixel_bytes, pixel_values, embedding)
+        self._assert_requirements(pixel_values if pixel_bytes is None else pixel_bytes, embedding, heading)
         if not self.cell_layer.weight.is_cuda:
             raise RuntimeError('pigeon_amd.SuperGuessr runs on the GPU only: call .to("cuda") first (no CPU fallback)')
         with torch.no_grad():
             # fast pass, tolerance of the top-1 against every cell, exact re-encode of the samples that are not certain
             # (pigeon_amd.deferred, settled before this call returns: one host synchronisation)
-            res = self.engine(None).submit(pixel_values, embedding)[0]
+            res = self.engine(None).submit(pixel_values, embedding, pixel_bytes=pixel_bytes)[0]
             return self.package(dict(res['state']), labels, labels_clf, labels_multi_task, labels_climate, labels_month)
 
     def engine(self, refiner=None, **kw):
@@ -502,6 +530,9 @@ class SuperGuessr(nn.Module):
             return
         self._cal_buffer.append(px.detach().clone())
         if sum(t.shape[0] for t in self._cal_buffer) >= 16 * P:
+            if len({t.dtype == torch.uint8 for t in self._cal_buffer}) > 1:    # bytes and floats collected together: all as fp32 pixels
+                self._cal_buffer = [hip_ops.bytes_to_pixels(t) if t.dtype == torch.uint8 else t.float() for t in self._cal_buffer]
+                px = self._cal_buffer[-1]
             buf, self._cal_buffer = torch.cat([t.to(px.dtype) for t in self._cal_buffer]), []
             self._calibrate(buf)
 
@@ -510,8 +541,7 @@ class SuperGuessr(nn.Module):
         P = self._panels()
         n = min(max_samples, px.shape[0] // P)
         px = px[:n * P]
-        enc = self._encoder()
-        fast_i, exact_i = enc.embed(px), enc.embed_precise(px)
+        fast_i, exact_i = self._embed(px), self._embed(px, exact=True)
         st = self.certainty.calibrate(fast_i.reshape((-1, P, CLIP_EMBED_DIM)).mean(dim=1), exact_i.reshape((-1, P, CLIP_EMBED_DIM)).mean(dim=1),
                                       fast_images=fast_i, exact_images=exact_i)
         if self.certainty.force_exact:
@@ -530,6 +560,8 @@ class SuperGuessr(nn.Module):
             raise ValueError('calibrate_certainty needs pixel_values and a base model')
         dev = self.cell_layer.weight.device
         px = pixel_values.reshape((-1, 3, 336, 336)).to(dev)
+        if px.dtype == torch.uint8:
+            px = px.float()                              # (pixel_values: numbers, as in `encode_head`)
         return self._calibrate(px, max_samples)['fast_vs_exact_rms']
 
     # ------------------------------------------------------------------------------------------ calibration as a file

@@ -55,7 +55,10 @@ argp.add_argument('--no-exact-top1', dest='exact_top1', action='store_false',
                   help="the 16-bit path alone (PIGEON_EXACT_TOP1=0): embeddings within 1e-3, discrete outputs not guaranteed")
 argp.add_argument('--raw-images', dest='raw_images', action='store_true', default=False,
                   help="embed: items hold one image of any size each (PIL / uint8 array); the DataLoader workers decode and pack, "
-                       "the resize + crop + normalise runs on the GPU for the whole mixed-size batch at once (pg_prep_ragged_forward)")
+                       "the resize + crop + normalise runs on the GPU for the whole mixed-size batch at once (pg_prep_ragged_forward).  "
+                       "evaluate: items hold raw `image` (or `image`, `image_2`, `image_3`, `image_4`) columns of any sizes "
+                       "(the reference's EvalDataset); they are packed by the workers, resized on the GPU to 8-bit pixels and "
+                       "evaluated from those bytes (pigeon_amd.evaluate.ImageEvalDataset)")
 argp.add_argument('--calibration', default=None, metavar='FILE',
                   help="encoder calibration file (bias vector, certainty tolerance, exact-encoder verdict; keyed by the weight "
                        "fingerprint).  If FILE exists it is loaded before the first batch -- every rank loads the same one, nothing is "
@@ -91,6 +94,24 @@ class _SyntheticImages(torch.utils.data.Dataset):
             return {'pixel_values': torch.randn((12, 336, 336), generator=g), 'labels': torch.zeros(2, dtype=torch.float64),
                     'labels_clf': torch.tensor(0)}
         return {'image': torch.randn((3, 336, 336), generator=g), 'index': i}
+
+
+class _SyntheticRawPanoramas(_SyntheticImages):
+    """N seeded four-view items of raw uint8 images of mixed sizes, as a dataset with `image` ... `image_4` columns holds them."""
+    SIZES = ((336, 336), (400, 640), (512, 384), (337, 500))
+
+    def __init__(self, n):
+        super().__init__(n, panorama=True)
+
+    def __getitem__(self, i):
+        if isinstance(i, str):
+            return super().__getitem__(i)
+        g = torch.Generator().manual_seed(4321 + i)
+        item = {'labels': torch.zeros(2, dtype=torch.float64), 'labels_clf': torch.tensor(0)}
+        for v, key in enumerate(('image', 'image_2', 'image_3', 'image_4')):
+            h, w = self.SIZES[(i + v) % len(self.SIZES)]
+            item[key] = torch.randint(0, 256, (h, w, 3), generator=g, dtype=torch.uint8).numpy()
+        return item
 
 
 def _vision_model(args):
@@ -169,12 +190,15 @@ def _dispatch(args, comm):
             geocell_path = os.path.join(tmp, 'geocells.csv')
             synthetic.write_geocell_csv(geocell_path, synthetic.make_geocells(args.geocells, seed=0))
             bank = synthetic.make_bank(args.geocells, 20, seed=2, exact_means=False)
-            dataset = _SyntheticImages(args.synthetic, panorama=True)
+            dataset = _SyntheticRawPanoramas(args.synthetic) if args.raw_images else _SyntheticImages(args.synthetic, panorama=True)
         else:
             from datasets import DatasetDict
             dataset = DatasetDict.load_from_disk(args.load[0])
             if not args.yfcc:
                 dataset = dataset['test'] if args.test else dataset['val']
+        if args.raw_images:
+            from pigeon_amd.evaluate import ImageEvalDataset
+            dataset = ImageEvalDataset(dataset)
         results = evaluate(args.name, dataset, yfcc=args.yfcc, base_model=_vision_model(args), refine=True,
                            landmarks=args.landmarks, geocell_path=geocell_path, bank=bank, heading=args.heading,
                            multi_task=args.multitask, calibration=args.calibration, embedding_rel_tol=args.embedding_rel_tol,
