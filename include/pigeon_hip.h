@@ -47,7 +47,7 @@ extern "C" {
                               *    + pg_prep_ragged_plan / _create / _destroy / _forward and pg_prep_item, additive;
                               *    + pg_haversine_blocks, pg_optics_graph, pg_optics_plan, pg_tune_optics_lds_points, additive;
                               *    + pg_region_locate, pg_region_classify, pg_region_nearest, pg_region_plan, pg_tune_region_wave_edges, additive;
-                              *    + PG_DTYPE_U8 pixels and pg_prep_norm_lut, additive) */
+                              *    + PG_DTYPE_U8 pixels and pg_prep_norm_lut, additive; + pg_vit_param_read, additive) */
 
 const char* pg_last_error(void);
 int pg_abi_version(void);
@@ -83,8 +83,13 @@ int pg_vit_create(pg_vit** out, int device, const pg_vit_cfg* cfg);
 /* Copy one parameter into the handle.  `name` is the state-dict key of transformers' CLIPVisionModel, either
  * layout: 4.23.1 "vision_model.embeddings.patch_embedding.weight" or 5.x "embeddings.patch_embedding.weight"
  * (reference loads by name: models/utils.py:24-45, models/super_guessr.py:222-238).  `data` is a HOST pointer
- * to contiguous fp32 (PG_DTYPE_F32); the library converts GEMM weights to bf16 and keeps its own device copy.
- * Unknown names (post_layernorm.*, position_ids) are accepted and ignored (dead on this path). */
+ * to contiguous fp32 (PG_DTYPE_F32), anything else is PG_EINVAL; pg_vit_finalize converts GEMM weights to the handle's 16-bit operand
+ * format (cfg.mma_dtype: fp16, saturating, or bf16; round to nearest even) and keeps its own device copy.  `shape` / `ndim` must be the
+ * parameter's transformers shape -- (1024,3,14,14) patch weight, (577,1024) position embedding, (4096,1024) fc1, (1024,4096) fc2,
+ * (1024,1024) projections, (N) vectors: a known name with any other shape (a transposed fc1, say, which has the right element count)
+ * is PG_EINVAL with a message naming both shapes.  ndim outside 1..8 or an extent < 1 is PG_EINVAL before `data` is read.  A name
+ * loaded twice keeps the last value.  Names this path does not read (post_layernorm.*, position_ids, layers past cfg.layers) are
+ * accepted and ignored.  PG_ESTATE after pg_vit_finalize. */
 int pg_vit_load_weight(pg_vit* h, const char* name, const void* data, int dtype,
                        const int64_t* shape, int ndim);
 /* Checks that every required parameter was loaded and uploads fused/packed forms, and the handle's 3 KB device copy of the
@@ -153,6 +158,14 @@ int pg_vit_mma_dtype(const pg_vit* h);
  * synchronous copy back (~0.6 GB read for ViT-L).  Any change of a weight that changes a stored bit changes the result. */
 int pg_fingerprint(const void* data, size_t bytes, uint64_t seed, uint64_t out[2], void* stream);
 int pg_vit_fingerprint(const pg_vit* h, uint64_t out[2]);
+/* TEST / DEBUG entry, not for the hot path: copies one parameter buffer of a finalized handle (PG_ESTATE before) to HOST `host_dst`,
+ * synchronously, on the handle's device (the caller's current device is restored).  (group, slot) is pg_vit_fingerprint's numbering
+ * (csrc/vit_weights.hip: group 0 slots 0..4 the embeddings, group l + 1 slots 0..13 encoder layer l), continued by the buffers the
+ * fingerprint leaves out: group 0 slot 5 the patch weight's split-fp16 triple, 6 the normalisation table; group l + 1 slots 14..19 the
+ * QKV, out_proj, fc1 and fc2 triples and the raw QKV and fc1 biases.  *bytes receives the buffer's size; host_dst == NULL only
+ * queries it.  A buffer this handle does not have (the column sums without the LayerNorm fold, the exact tier's slots without
+ * cfg.precise) is PG_OK with *bytes = 0; any other (group, slot) is PG_EINVAL; dst_bytes < *bytes is PG_EINVAL and copies nothing. */
+int pg_vit_param_read(const pg_vit* h, int group, int slot, void* host_dst, size_t dst_bytes, size_t* bytes);
 
 /* Per-kernel-class timing (HIP events on `stream`), for bench.py's roofline object.
  * pg_vit_profile_enable(h,1) makes subsequent forwards bracket every launch with events; a value >= 2 is a class mask

@@ -70,6 +70,7 @@ SIGNATURES = {
     "pg_vit_mma_dtype": (_I, [_P]),
     "pg_fingerprint": (_I, [_P, _SZ, C.c_uint64, C.POINTER(C.c_uint64), _P]),
     "pg_vit_fingerprint": (_I, [_P, C.POINTER(C.c_uint64)]),
+    "pg_vit_param_read": (_I, [_P, _I, _I, _P, _SZ, C.POINTER(_SZ)]),
     "pg_vit_profile_enable": (_I, [_P, _I]),
     "pg_vit_profile_read": (_I, [_P, C.POINTER(_I64), C.POINTER(_D)]),
     "pg_vit_profile_reset": (_I, [_P]),

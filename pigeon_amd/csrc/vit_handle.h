@@ -9,7 +9,7 @@
 #include <vector>
 
 struct LayerW {
-    uint16_t *wqkv = nullptr, *wo = nullptr, *w1 = nullptr, *w2 = nullptr;     // bf16 [N][K]
+    uint16_t *wqkv = nullptr, *wo = nullptr, *w1 = nullptr, *w2 = nullptr;     // 16-bit (cfg.mma_dtype: fp16 or bf16) [N][K]
     float *bqkv = nullptr, *bo = nullptr, *b1 = nullptr, *b2 = nullptr;
     float *ln1g = nullptr, *ln1b = nullptr, *ln2g = nullptr, *ln2b = nullptr;
     // LayerNorm folded into the following GEMM (cfg ln_fold): wqkv / w1 then hold gamma-scaled weights, bqkv / b1 hold
@@ -28,8 +28,8 @@ struct pg_vit {
     bool ln_fold = true;                                   // LayerNorm folded into the GEMMs (env PIGEON_LN_FOLD=0: separate kernels)
     std::map<std::string, std::vector<float>> host;      // staged fp32 parameters until finalize
     std::vector<void*> allocs;
-    std::map<const void*, size_t> alloc_bytes;             // byte size of every uploaded parameter buffer (pg_vit_fingerprint reads them whole)
-    uint16_t* wpatch = nullptr;                           // [1024][640] bf16 (K zero padded)
+    std::map<const void*, size_t> alloc_bytes;             // byte size of every uploaded parameter buffer (pg_vit_fingerprint / pg_vit_param_read)
+    uint16_t* wpatch = nullptr;                           // [1024][640] 16-bit, cfg.mma_dtype (K zero padded)
     uint16_t* wpatch3 = nullptr;                          // exact mode: [1024][3 * 640] split-fp16 triple
     float *cls = nullptr, *pos = nullptr, *preg = nullptr, *preb = nullptr;
     float* norm_lut = nullptr;                            // [3][256] the normalisation table PG_DTYPE_U8 pixels are looked up in (im2col)

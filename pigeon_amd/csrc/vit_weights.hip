@@ -4,6 +4,7 @@
 #include "vit_handle.h"
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 #include <type_traits>
 #ifndef PG_DEFAULT_VIT_STREAMS
 #define PG_DEFAULT_VIT_STREAMS 1
@@ -70,13 +71,65 @@ extern "C" int pg_vit_create(pg_vit** out, int device, const pg_vit_cfg* cfg) {
     return PG_OK;
 }
 
+// The shape transformers' CLIPVisionModel gives the parameter `key` (canonical name) where this path reads it: its extents to want[4],
+// their number returned; 0 for a name finalize never asks for (post_layernorm.*, position_ids, a layer past cfg.layers).
+static int param_shape(const pg_vit* h, const std::string& key, int64_t want[4]) {
+    const int64_t D = VIT_HIDDEN, F = VIT_MLP;
+    auto set = [&](std::initializer_list<int64_t> e) { int i = 0; for (int64_t v : e) want[i++] = v; return (int)e.size(); };
+    if (key == "embeddings.patch_embedding.weight") return set({D, 3, 14, 14});
+    if (key == "embeddings.position_embedding.weight") return set({VIT_TOKENS, D});
+    if (key == "embeddings.class_embedding" || key == "pre_layrnorm.weight" || key == "pre_layrnorm.bias") return set({D});
+    const std::string pre = "encoder.layers.";
+    if (key.compare(0, pre.size(), pre) != 0) return 0;
+    size_t dot = key.find('.', pre.size());
+    if (dot == std::string::npos || dot == pre.size() || dot - pre.size() > 6) return 0;
+    int l = 0;
+    for (size_t i = pre.size(); i < dot; ++i) { if (key[i] < '0' || key[i] > '9') return 0; l = l * 10 + (key[i] - '0'); }
+    if (l >= h->cfg.layers || key.substr(pre.size(), dot - pre.size()) != std::to_string(l)) return 0;
+    const std::string s = key.substr(dot + 1);
+    for (const char* p : {"self_attn.q_proj", "self_attn.k_proj", "self_attn.v_proj", "self_attn.out_proj"}) {
+        if (s == std::string(p) + ".weight") return set({D, D});
+        if (s == std::string(p) + ".bias") return set({D});
+    }
+    for (const char* p : {"layer_norm1", "layer_norm2"})
+        if (s == std::string(p) + ".weight" || s == std::string(p) + ".bias") return set({D});
+    if (s == "mlp.fc1.weight") return set({F, D});
+    if (s == "mlp.fc1.bias") return set({F});
+    if (s == "mlp.fc2.weight") return set({D, F});
+    if (s == "mlp.fc2.bias") return set({D});
+    return 0;
+}
+static std::string shape_str(const int64_t* s, int n) {    // "(4096, 1024) of 4194304 elements"; every extent is >= 1
+    std::string o = "(";
+    uint64_t count = 1;
+    bool over = false;
+    for (int i = 0; i < n; ++i) {
+        o += std::to_string((long long)s[i]) + (i + 1 < n ? ", " : ")");
+        if (count > UINT64_MAX / (uint64_t)s[i]) over = true; else count *= (uint64_t)s[i];
+    }
+    return o + (over ? " of more than 2^64 elements" : " of " + std::to_string((unsigned long long)count) + " elements");
+}
+
 extern "C" int pg_vit_load_weight(pg_vit* h, const char* name, const void* data, int dtype, const int64_t* shape, int ndim) {
     if (!h || !name || !data || !shape) { pg_set_error("vit_load_weight: null argument"); return PG_EINVAL; }
     if (dtype != PG_DTYPE_F32) { pg_set_error("vit_load_weight: only fp32 host data is accepted"); return PG_EINVAL; }
     if (h->finalized) { pg_set_error("vit_load_weight: handle already finalized"); return PG_ESTATE; }
+    const std::string key = canon(name);
+    if (ndim < 1 || ndim > 8) { pg_set_error("vit_load_weight: parameter %s has ndim = %d (1..8)", key.c_str(), ndim); return PG_EINVAL; }
+    for (int i = 0; i < ndim; ++i)
+        if (shape[i] < 1) { pg_set_error("vit_load_weight: parameter %s has extent %lld in dimension %d", key.c_str(), (long long)shape[i], i); return PG_EINVAL; }
+    int64_t want[4];
+    const int wn = param_shape(h, key, want);
+    if (wn == 0) return PG_OK;                               // not read on this path (post_layernorm.*, layers past cfg.layers): ignored
+    bool same = wn == ndim;
+    for (int i = 0; same && i < wn; ++i) same = shape[i] == want[i];
+    if (!same) {
+        pg_set_error("vit_load_weight: parameter %s has shape %s, expected %s", key.c_str(), shape_str(shape, ndim).c_str(),
+                     shape_str(want, wn).c_str());
+        return PG_EINVAL;
+    }
     int64_t n = 1;
-    for (int i = 0; i < ndim; ++i) n *= shape[i];
-    std::string key = canon(name);
+    for (int i = 0; i < wn; ++i) n *= want[i];
     const float* f = (const float*)data;
     h->host[key] = std::vector<float>(f, f + n);
     return PG_OK;
@@ -178,7 +231,7 @@ extern "C" int pg_vit_finalize(pg_vit* h) {
     const size_t D = VIT_HIDDEN, F = VIT_MLP;
     const int dt = h->cfg.mma_dtype;
     const std::vector<float>* p;
-    // patch embedding [1024,3,14,14] -> bf16 [1024][640], zero padded along K
+    // patch embedding [1024,3,14,14] -> 16-bit (cfg.mma_dtype) [1024][640], zero padded along K
     RC(need(h, "embeddings.patch_embedding.weight", D * VIT_PATCH_K, &p));
     {
         std::vector<uint16_t> w(D * VIT_PATCH_KPAD, 0);
@@ -273,6 +326,25 @@ extern "C" int pg_vit_mma_dtype(const pg_vit* h) { return h ? h->cfg.mma_dtype :
 //   result: the digest (same function, seed 0) of that table's bytes.
 // The exact tier's split-weight copies and raw biases (cfg.precise) are NOT in it: they are a function of the same fp32 weights, and
 // a handle built without `precise` gives the same value.
+
+// The parameter buffer (group, slot) of a finalized handle in the numbering above -- ONE table for the fingerprint and for
+// pg_vit_param_read; nullptr where this handle has none.  The buffers the fingerprint leaves out continue the numbering: group 0:
+// 5 the patch triple, 6 the normalisation table; group l + 1: 14..19 the QKV, out_proj, fc1, fc2 triples, the raw QKV and fc1 biases.
+enum { VIT_FP_EMBED_SLOTS = 5, VIT_EMBED_SLOTS = 7, VIT_FP_LAYER_SLOTS = 14, VIT_LAYER_SLOTS = 20 };
+static const void* vit_param(const pg_vit* h, int group, int slot, bool* known) {
+    if (known) *known = false;
+    if (group < 0 || group > h->cfg.layers || slot < 0 || slot >= (group ? VIT_LAYER_SLOTS : VIT_EMBED_SLOTS)) return nullptr;
+    if (known) *known = true;
+    if (group == 0) {
+        const void* p[VIT_EMBED_SLOTS] = {h->wpatch, h->cls, h->pos, h->preg, h->preb, h->wpatch3, h->norm_lut};
+        return p[slot];
+    }
+    const LayerW& L = h->layers[group - 1];
+    const void* p[VIT_LAYER_SLOTS] = {L.wqkv, L.bqkv, L.sqkv, L.wo, L.bo, L.w1, L.b1, L.s1, L.w2, L.b2, L.ln1g, L.ln1b, L.ln2g, L.ln2b,
+                                      L.wqkv3, L.wo3, L.w13, L.w23, L.bqkv_raw, L.b1_raw};
+    return p[slot];
+}
+
 extern "C" int pg_vit_fingerprint(const pg_vit* h, uint64_t out[2]) {
     if (!h || !out) { pg_set_error("vit_fingerprint: null argument"); return PG_EINVAL; }
     if (!h->finalized) { pg_set_error("vit_fingerprint: handle not finalized"); return PG_ESTATE; }
@@ -284,12 +356,8 @@ extern "C" int pg_vit_fingerprint(const pg_vit* h, uint64_t out[2]) {
         if (it == h->alloc_bytes.end()) { ++missing; return; }
         bufs.push_back({p, it->second, ((uint64_t)group << 8) | (uint64_t)slot});
     };
-    add(h->wpatch, 0, 0); add(h->cls, 0, 1); add(h->pos, 0, 2); add(h->preg, 0, 3); add(h->preb, 0, 4);
-    for (int l = 0; l < h->cfg.layers; ++l) {
-        const LayerW& L = h->layers[l];
-        const void* p[14] = {L.wqkv, L.bqkv, L.sqkv, L.wo, L.bo, L.w1, L.b1, L.s1, L.w2, L.b2, L.ln1g, L.ln1b, L.ln2g, L.ln2b};
-        for (int s = 0; s < 14; ++s) add(p[s], l + 1, s);
-    }
+    for (int g = 0; g <= h->cfg.layers; ++g)
+        for (int s = 0; s < (g ? VIT_FP_LAYER_SLOTS : VIT_FP_EMBED_SLOTS); ++s) add(vit_param(h, g, s, nullptr), g, s);
     if (missing) { pg_set_error("vit_fingerprint: %d parameter buffers without a recorded size", missing); return PG_ESTATE; }
     int cur = 0;
     PG_HIP(hipGetDevice(&cur));
@@ -305,5 +373,29 @@ extern "C" int pg_vit_fingerprint(const pg_vit* h, uint64_t out[2]) {
         table.push_back(dig[2 * i]); table.push_back(dig[2 * i + 1]);
     }
     pg_fingerprint_host(table.data(), table.size() * sizeof(uint64_t), 0, out);
+    return PG_OK;
+}
+
+extern "C" int pg_vit_param_read(const pg_vit* h, int group, int slot, void* host_dst, size_t dst_bytes, size_t* bytes) {
+    if (!h || !bytes) { pg_set_error("vit_param_read: null argument"); return PG_EINVAL; }
+    *bytes = 0;
+    if (!h->finalized) { pg_set_error("vit_param_read: handle not finalized"); return PG_ESTATE; }
+    bool known = false;
+    const void* p = vit_param(h, group, slot, &known);
+    if (!known) { pg_set_error("vit_param_read: no buffer (group %d, slot %d) on a handle of %d layers", group, slot, h->cfg.layers); return PG_EINVAL; }
+    if (!p) return PG_OK;                                      // (the column sums without ln_fold, the exact tier's slots without cfg.precise)
+    auto it = h->alloc_bytes.find(p);
+    if (it == h->alloc_bytes.end()) { pg_set_error("vit_param_read: buffer (group %d, slot %d) without a recorded size", group, slot); return PG_ESTATE; }
+    *bytes = it->second;
+    if (!host_dst) return PG_OK;                               // size query
+    if (dst_bytes < it->second) {
+        pg_set_error("vit_param_read: destination of %zu bytes, buffer (group %d, slot %d) has %zu", dst_bytes, group, slot, it->second);
+        return PG_EINVAL;
+    }
+    int cur = 0; PG_HIP(hipGetDevice(&cur));
+    PG_HIP(hipSetDevice(h->device));                         // the weights live on the handle's device, whatever is current
+    const hipError_t e = hipMemcpy(host_dst, p, it->second, hipMemcpyDeviceToHost);
+    (void)hipSetDevice(cur);                                 // ... and the caller's current device is put back
+    if (e != hipSuccess) { pg_set_error("vit_param_read: %s", hipGetErrorString(e)); return PG_EHIP; }
     return PG_OK;
 }

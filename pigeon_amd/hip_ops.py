@@ -543,7 +543,7 @@ class RaggedPreprocessor:
 
 # ----------------------------------------------------------------------------------------- ViT encoder handle
 class VitEncoder:
-    """Owns a pg_vit handle: bf16-packed weights resident in HBM, forward = ViT-L/14-336 + token mean.
+    """Owns a pg_vit handle: 16-bit-packed weights (fp16 or bf16) resident in HBM, forward = ViT-L/14-336 + token mean.
 
     state_dict keys may be in either transformers layout (vision_model.* or flat); values are CPU or device
     tensors of any float dtype (converted to fp32 on the host, then packed by the library).
@@ -646,6 +646,17 @@ class VitEncoder:
         out = (C.c_uint64 * 2)()
         check(load().pg_vit_fingerprint(self._h, out), "pg_vit_fingerprint")
         return int(out[0]), int(out[1])
+
+    def param(self, group: int, slot: int, dtype: torch.dtype = torch.uint8) -> torch.Tensor:
+        """pg_vit_param_read (test / debug, not for the hot path): the device buffer (group, slot) of pg_vit_fingerprint's numbering,
+        continued by the exact tier's buffers and the normalisation table (include/pigeon_hip.h), as a flat CPU tensor of `dtype`
+        (the bytes reinterpreted; empty where this handle has no such buffer).  Synchronous."""
+        n = C.c_size_t()
+        check(load().pg_vit_param_read(self._h, group, slot, None, 0, C.byref(n)), "pg_vit_param_read")
+        out = torch.empty(n.value, dtype=torch.uint8)
+        if n.value:
+            check(load().pg_vit_param_read(self._h, group, slot, C.c_void_p(out.data_ptr()), n.value, C.byref(n)), "pg_vit_param_read")
+        return out.view(dtype)
 
     def graph(self, on: Optional[bool] = None):
         """Switch the encoder's hipGraph replay on / off (None: query only) -> (replays, captures) since creation."""
@@ -923,10 +934,11 @@ def x3_layernorm(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps: 
 
 
 def x3_pack_weight(W: torch.Tensor) -> torch.Tensor:
-    """Host-side mirror of the library's weight triple (vit.hip pack_x3), for the building-block tests: W fp32 (N,K) ->
-    fp16 (N,3K) = [Wh | Wh | (W - Wh) 2^8]."""
-    Wh = W.to(torch.float16)
-    Wl = ((W - Wh.float()) * 256.0).to(torch.float16)
+    """Host-side mirror of the library's weight triple (vit_weights.hip pack_x3), for the building-block tests: W fp32 (N,K) ->
+    fp16 (N,3K) = [Wh | Wh | (W - Wh) 2^8], both conversions saturating at +-65504 as the library's (tests/test_gpu_weights.py holds
+    the two equal bit for bit)."""
+    Wh = W.clamp(-65504.0, 65504.0).to(torch.float16)
+    Wl = ((W - Wh.float()) * 256.0).clamp(-65504.0, 65504.0).to(torch.float16)
     return torch.cat([Wh, Wh, Wl], dim=1).contiguous()
 
 
