@@ -47,7 +47,8 @@ extern "C" {
                               *    + pg_prep_ragged_plan / _create / _destroy / _forward and pg_prep_item, additive;
                               *    + pg_haversine_blocks, pg_optics_graph, pg_optics_plan, pg_tune_optics_lds_points, additive;
                               *    + pg_region_locate, pg_region_classify, pg_region_nearest, pg_region_plan, pg_tune_region_wave_edges, additive;
-                              *    + PG_DTYPE_U8 pixels and pg_prep_norm_lut, additive; + pg_vit_param_read, additive) */
+                              *    + PG_DTYPE_U8 pixels and pg_prep_norm_lut, additive; + pg_vit_param_read, additive;
+                              *    + pg_refine_certainty_bank, additive) */
 
 const char* pg_last_error(void);
 int pg_abi_version(void);
@@ -361,6 +362,22 @@ int pg_refine_certainty(const pg_bank* bank, const float* q, int B, int P, const
                         int topk, int n_eval, const float* scratch12, const float* W, int C, const float* beta,
                         const float* wstats, float temperature, const int32_t* refined, const int32_t* choice,
                         float* tol, int32_t* code, void* stream);
+
+/* pg_refine_certainty for a bank whose rows carry an error of their own (a bank built from embeddings of the 16-bit encoder;
+ * derivation: csrc/certainty.hip "Bank error").  Every bank row p is taken to be off by |p| r_p, r_p of relative RMS
+ * norm eps_b in an unknown direction, independent from row to row, the systematic part removed (a bank that was not debiased declares
+ * its whole error).  bank_sigma = kappa * eps_b, ONE scalar for all rows (finite, >= 0; else PG_EINVAL): the z-score the host compares
+ * tolerances with, times the bank's relative error.  Per decision, with num = m - |e| g.beta, A = |e| |g| / 32 and
+ * Bk = bank_sigma sqrt(bsum) / 32, bsum = sum of w^2 |row|^2 over the bank rows that enter it (candidate-score pairs: the nearest
+ * prototype of both candidates, w = 1 / T, empty cells nothing; nearest prototype / farthest member: the pick and the alternative,
+ * w = 1; set-boundary margins: none), the tolerance is sqrt((num - Bk)(num + Bk)) / A, 0 where num <= Bk (no query accuracy settles
+ * it), and pg_refine_certainty's own expression where bank_sigma or bsum is 0 -- bank_sigma = 0 gives pg_refine_certainty's tol and
+ * code bit for bit.  tol keeps its meaning (the largest relative query error, in standard deviations, every decision survives), so one
+ * value serves the fast and the exact tier's threshold; code as above.  The row norms come from the rows the pass streams anyway. */
+int pg_refine_certainty_bank(const pg_bank* bank, const float* q, int B, int P, const int64_t* cand, const float* cand_prob, int k,
+                             int topk, int n_eval, const float* scratch12, const float* W, int C, const float* beta,
+                             const float* wstats, float temperature, const int32_t* refined, const int32_t* choice,
+                             float* tol, int32_t* code, float bank_sigma, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * The deferred exact tier (round 6; csrc/requeue.hip).  The reference's discrete outputs are fp32 end to end

@@ -493,6 +493,9 @@ class CLIPEmbedding(torch.nn.Module):
             self.clip_model = self.clip_model.cuda(self.device)
         self.eval()
         self.calibration_header = None           # header of the calibration file in force (None: none loaded)
+        # `exact`: every image through the exact encoder (pg_vit_forward_precise) by the route `force_exact` takes, chosen by the caller
+        # (`run.py embed --exact`: embeddings a prototype bank is built from) instead of by the guard -- which then measures nothing
+        self.exact = False
         if calibration is not None:
             self.load_calibration(calibration)
 
@@ -548,6 +551,26 @@ class CLIPEmbedding(torch.nn.Module):
         self.certainty, self.guard_stats, self.calibration_header = c, st, header
         return header
 
+    def embedding_meta(self, source: str = '') -> dict:
+        """What the embeddings this module returns NOW are: the sidecar `run.py embed` writes next to its `.npy` files
+        (`embedding_meta.json`), from which a bank built on them declares its error (`HostBank.embedding_rel_tol`,
+        `run.py evaluate --bank-rel-tol`).  `embedding_rel_tol`: the exact tier's floor for the exact encoder, else the value a
+        `SuperGuessr` judges caller-supplied embeddings at -- 1.1 x the per-image residual the guard measured (or a loaded
+        calibration file records), 1e-3 where nothing was measured.  It is a declaration derived from the calibration's sample, not a
+        measurement of the written files."""
+        c, st, base = self.certainty, self.guard_stats, self.clip_model.base_model
+        exact = bool(self.exact or c.force_exact)
+        tol = c.rel_tol_exact
+        if not exact:
+            resid = None
+            if st is not None:
+                resid = st.get('residual_rms') if (c.bias is not None or st.get('image_rel_err') is None) else st.get('image_rel_err')
+            tol = SAFETY * float(resid) if resid is not None and float(resid) > 0.0 else c.rel_tol
+        meta = dict(base.encoder_config(), encoder='exact' if exact else 'fast', embedding_rel_tol=float(tol),
+                    debias=bool(not exact and c.bias is not None), fingerprint=base.fingerprint(),
+                    source=source or 'CLIPEmbedding')
+        return meta
+
     def _get_embedding(self, image) -> Tensor:
         """reference models/clip_embedder.py:42-66"""
         with torch.no_grad():
@@ -563,6 +586,8 @@ class CLIPEmbedding(torch.nn.Module):
             else:
                 pixel_values = pixel_values.cuda(self.device)
             base = self.clip_model.base_model
+            if self.exact:                                           # no guard measurement, no collectives, no bias
+                return base.embed_precise(pixel_bytes=pixel_values) if pixel_values.dtype == torch.uint8 else base.embed_precise(pixel_values)
             if self.contract_guard != 'off' and self.guard_stats is None and pixel_values.shape[0] > 0:
                 self._check_contract(base, pixel_values)
             # last_hidden_state.mean(dim=1), fused in the library (token_mean kernel)

@@ -20,6 +20,20 @@
 // decisions, and the host calls the row certain when tolerance > kappa * eps (pigeon_amd/certainty.py: eps and beta are measured per
 // set of weights against the exact encoder, kappa is a z-score).  Uncertain rows are re-encoded by pg_vit_forward_precise.
 //
+// Bank error (pg_refine_certainty_bank).  The above takes the prototype bank as exact.  A bank written by the 16-bit encoder is not: let
+// every bank row p carry an independent error |p| r_p, r_p of relative RMS norm eps_b in an unknown direction (the query's model; the
+// systematic part is assumed removed, as pg_embedding_debias does -- a bank that was not debiased declares its whole error as eps_b).
+// A distance |e - p| then moves by -u . delta_p, standard deviation eps_b |p| / 32, and a decision survives when
+//   num > kappa sqrt(eps^2 A^2 + eps_b^2 B^2),   num = m - |e| grad.beta,  A = |e| |grad| / 32,  B = sqrt(bsum) / 32,
+// bsum = the sum of w^2 |row|^2 over the bank rows that enter the decision: the nearest prototype of each of the two candidates with
+// w = 1 / T for a candidate-score pair (an empty cell adds nothing), the picked and the alternative row with w = 1 for the nearest
+// prototype / farthest member, nothing for the set-boundary margins (differences of log-probabilities).  The host hands in ONE scalar
+// sigma = kappa eps_b; with Bk = sigma B the largest query eps, in the units above, is
+//   sqrt((num - Bk) (num + Bk)) / A     (0 when num <= Bk: no query accuracy can settle it; tol_of itself when sigma or bsum is 0)
+// which does not depend on the tier whose threshold it is later compared with.  ONE eps_b for every row: a prototype (a mean of
+// `count` members) is NOT credited with eps_b / sqrt(count) -- nobody has measured whether the residual is independent across the images
+// of one cluster.
+//
 // Two kernels, one block (4 waves) per row; a wave evaluates one decision at a time: the gradient is a linear combination of at most
 // four 4 KB rows (head weights, prototypes, training rows) and e, 16 columns per lane, reduced with shuffles.  ~100 decisions x
 // <= 16 KB per row: a few hundred MB per 128-row batch from L2 / HBM, the cost of one refinement pass (tens of microseconds).
@@ -36,6 +50,28 @@ namespace {
 __device__ __forceinline__ void axpy16r(f32x4 (&g)[4], const f32x4 (&v)[4], float coef) {
 #pragma unroll
     for (int i = 0; i < 4; ++i) g[i] += coef * v[i];
+}
+// axpy16 that also returns |row|^2 (no row: 0, nothing added).  The row is loaded even where coef == 0: its norm still counts.
+__device__ __forceinline__ float axpy16n(f32x4 (&g)[4], const float* __restrict__ row, float coef, int lane) {
+    if (!row) return 0.f;
+    f32x4 v[4];
+    ld16(row, lane, v);
+    if (coef != 0.f) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) g[i] += coef * v[i];
+    }
+    return dot16(v, v);
+}
+// tol_of with a bank term (header: "Bank error"); sigma = kappa eps_b, bsum = sum of w^2 |row|^2
+__device__ __forceinline__ float tol_bank(float m, float g2, float gb, float en, float sigma, float bsum) {
+    if (sigma == 0.f || bsum == 0.f) return tol_of(m, g2, gb, en);
+    if (!(m == m) || !(g2 == g2) || !(gb == gb) || !(en == en) || !(bsum == bsum)) return 0.f;
+    const float num = m - en * gb;
+    const float bk = sigma * sqrtf(bsum) * (1.0f / 32.0f);
+    if (!(num > bk)) return 0.f;
+    if (!(g2 > 0.f)) return INFINITY;
+    const float t = sqrtf((num - bk) * (num + bk)) / (en * sqrtf(g2) * (1.0f / 32.0f));
+    return (t == t) ? t : 0.f;
 }
 __device__ __forceinline__ MinTol block_min(MinTol v, float* red_t, int* red_c) {
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -110,13 +146,16 @@ __global__ __launch_bounds__(256) void head_certainty_kernel(const float* __rest
 // prototype of the cell;  4000 / 4001 farthest member against every other member of the cluster;
 // -9 the winning product underflows in fp32 (or an empty cell wins a set that is not all empty);  -8 refined / choice out of range;
 // 0 nothing can change it
+// BANK: the bank rows carry an error too (bank_sigma = kappa eps_b >= 0; header: "Bank error").  Without it bank_sigma is not read and
+// the arithmetic is pg_refine_certainty's of old.
+template <bool BANK>
 __global__ __launch_bounds__(256) void refine_certainty_kernel(pg_bank bank, const float* __restrict__ q, int P,
                                                                const int64_t* __restrict__ cand, const float* __restrict__ cand_prob,
                                                                int k, int topk, int n_eval, const float* __restrict__ scratch12,
                                                                const float* __restrict__ W, int C, const float* __restrict__ beta,
                                                                const float* __restrict__ wstats, float temperature,
                                                                const int32_t* __restrict__ refined, const int32_t* __restrict__ choice,
-                                                               float* __restrict__ tol, int32_t* __restrict__ code) {
+                                                               float* __restrict__ tol, int32_t* __restrict__ code, float bank_sigma) {
     __shared__ float L[CT_MAX_EVAL], S[CT_MAX_EVAL];
     __shared__ float red_t[4];
     __shared__ int red_c[4];
@@ -167,10 +206,20 @@ __global__ __launch_bounds__(256) void refine_certainty_kernel(pg_bank bank, con
         zero16(g);
         axpy16(g, wrow(cd[a]), 1.f, lane);
         axpy16(g, wrow(cd[j]), -1.f, lane);
-        axpy16(g, pa >= 0 ? bank.proto_emb + (int64_t)pa * CT_DIM : nullptr, ia, lane);
-        axpy16(g, pj >= 0 ? bank.proto_emb + (int64_t)pj * CT_DIM : nullptr, -ij, lane);
-        axpy16r(g, ev, ij - ia);
-        return tol_of(S[a] - S[j], dot16(g, g), dot16(g, bv), en);
+        const float* rowa = pa >= 0 ? bank.proto_emb + (int64_t)pa * CT_DIM : nullptr;
+        const float* rowj = pj >= 0 ? bank.proto_emb + (int64_t)pj * CT_DIM : nullptr;
+        if constexpr (BANK) {
+            // both nearest prototypes move s by their own error / T (the same cell listed twice is counted twice: the safe side)
+            const float na = axpy16n(g, rowa, ia, lane);
+            const float nj = axpy16n(g, rowj, -ij, lane);
+            axpy16r(g, ev, ij - ia);
+            return tol_bank(S[a] - S[j], dot16(g, g), dot16(g, bv), en, bank_sigma, (na + nj) * (invT * invT));
+        } else {
+            axpy16(g, rowa, ia, lane);
+            axpy16(g, rowj, -ij, lane);
+            axpy16r(g, ev, ij - ia);
+            return tol_of(S[a] - S[j], dot16(g, g), dot16(g, bv), en);
+        }
     };
     // every alternative to an argmin (sign +1: nearest prototype) / argmax (sign -1: farthest member) over rows [lo, hi) of `base`
     // (through `index` if given): the pick `win` against row j has margin m = sign (d_j - d_win) and gradient sign (u_j - u_win), u =
@@ -180,6 +229,8 @@ __global__ __launch_bounds__(256) void refine_certainty_kernel(pg_bank bank, con
                                  MinTol& acc) {
         f32x4 w[4];
         ld16(base + win * CT_DIM, lane, w);
+        float nw = 0.f;
+        if constexpr (BANK) nw = dot16(w, w);                 // |row|^2 of the pick, before the subtraction
 #pragma unroll
         for (int i = 0; i < 4; ++i) w[i] = ev[i] - w[i];
         const float dw = sqrtf(dot16(w, w));
@@ -190,13 +241,16 @@ __global__ __launch_bounds__(256) void refine_certainty_kernel(pg_bank bank, con
             if (row == win) continue;
             f32x4 l[4];
             ld16(base + row * CT_DIM, lane, l);
+            float nl = 0.f;
+            if constexpr (BANK) nl = dot16(l, l);
 #pragma unroll
             for (int i = 0; i < 4; ++i) l[i] = ev[i] - l[i];
             const float dl = sqrtf(dot16(l, l));
             const float il = dl > 0.f ? 1.0f / dl : 0.f;
             const float g2 = (dl > 0.f ? 1.f : 0.f) + (dw > 0.f ? 1.f : 0.f) - 2.f * dot16(l, w) * il * iw;
             const float gb = sign * (dot16(l, bv) * il - wb);
-            acc.take(tol_of(sign * (dl - dw), fmaxf(g2, 0.f), gb, en), cd_);
+            if constexpr (BANK) acc.take(tol_bank(sign * (dl - dw), fmaxf(g2, 0.f), gb, en, bank_sigma, nw + nl), cd_);
+            else acc.take(tol_of(sign * (dl - dw), fmaxf(g2, 0.f), gb, en), cd_);
         }
     };
 
@@ -292,21 +346,47 @@ extern "C" int pg_head_certainty(const float* logits, int B, int C, const float*
     return pg_check_launch("head_certainty");
 }
 
+namespace {
+int refine_certainty_launch(const char* name, bool with_bank, float bank_sigma, const pg_bank* bank, const float* q, int B, int P,
+                            const int64_t* cand, const float* cand_prob, int k, int topk, int n_eval, const float* scratch12,
+                            const float* W, int C, const float* beta, const float* wstats, float temperature, const int32_t* refined,
+                            const int32_t* choice, float* tol, int32_t* code, void* stream) {
+    if (B < 0) { pg_set_error("%s: B = %d", name, B); return PG_EINVAL; }
+    if (with_bank && !(bank_sigma >= 0.f && bank_sigma <= FLT_MAX)) {
+        pg_set_error("%s: bank_sigma = %g (kappa x the bank's relative error: must be finite and >= 0)", name, (double)bank_sigma);
+        return PG_EINVAL;
+    }
+    if (B == 0) return PG_OK;
+    if (!bank || !q || !cand || !scratch12 || !W || !wstats || !refined || !choice || !tol || !code) {
+        pg_set_error("%s: null pointer argument", name); return PG_EINVAL;
+    }
+    if (topk < 1 || topk > 64 || n_eval < topk || n_eval > k || n_eval > CT_MAX_EVAL || P < 1 || C < 1 || !(temperature > 0.f)) {
+        pg_set_error("%s: need 1 <= topk <= 64, topk <= n_eval <= min(k, %d), P >= 1, C >= 1, T > 0 (topk=%d n_eval=%d k=%d)",
+                     name, CT_MAX_EVAL, topk, n_eval, k);
+        return PG_EINVAL;
+    }
+    if (with_bank)
+        hipLaunchKernelGGL(refine_certainty_kernel<true>, dim3(B), dim3(256), 0, (hipStream_t)stream, *bank, q, P, cand, cand_prob, k, topk,
+                           n_eval, scratch12, W, C, beta, wstats, temperature, refined, choice, tol, code, bank_sigma);
+    else
+        hipLaunchKernelGGL(refine_certainty_kernel<false>, dim3(B), dim3(256), 0, (hipStream_t)stream, *bank, q, P, cand, cand_prob, k, topk,
+                           n_eval, scratch12, W, C, beta, wstats, temperature, refined, choice, tol, code, 0.f);
+    return pg_check_launch(name);
+}
+}  // namespace
+
 extern "C" int pg_refine_certainty(const pg_bank* bank, const float* q, int B, int P, const int64_t* cand, const float* cand_prob, int k,
                                    int topk, int n_eval, const float* scratch12, const float* W, int C, const float* beta,
                                    const float* wstats, float temperature, const int32_t* refined, const int32_t* choice, float* tol,
                                    int32_t* code, void* stream) {
-    if (B < 0) { pg_set_error("refine_certainty: B = %d", B); return PG_EINVAL; }
-    if (B == 0) return PG_OK;
-    if (!bank || !q || !cand || !scratch12 || !W || !wstats || !refined || !choice || !tol || !code) {
-        pg_set_error("refine_certainty: null pointer argument"); return PG_EINVAL;
-    }
-    if (topk < 1 || topk > 64 || n_eval < topk || n_eval > k || n_eval > CT_MAX_EVAL || P < 1 || C < 1 || !(temperature > 0.f)) {
-        pg_set_error("refine_certainty: need 1 <= topk <= 64, topk <= n_eval <= min(k, %d), P >= 1, C >= 1, T > 0 (topk=%d n_eval=%d k=%d)",
-                     CT_MAX_EVAL, topk, n_eval, k);
-        return PG_EINVAL;
-    }
-    hipLaunchKernelGGL(refine_certainty_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, *bank, q, P, cand, cand_prob, k, topk, n_eval,
-                       scratch12, W, C, beta, wstats, temperature, refined, choice, tol, code);
-    return pg_check_launch("refine_certainty");
+    return refine_certainty_launch("refine_certainty", false, 0.f, bank, q, B, P, cand, cand_prob, k, topk, n_eval, scratch12, W, C, beta,
+                                   wstats, temperature, refined, choice, tol, code, stream);
+}
+
+extern "C" int pg_refine_certainty_bank(const pg_bank* bank, const float* q, int B, int P, const int64_t* cand, const float* cand_prob,
+                                        int k, int topk, int n_eval, const float* scratch12, const float* W, int C, const float* beta,
+                                        const float* wstats, float temperature, const int32_t* refined, const int32_t* choice,
+                                        float* tol, int32_t* code, float bank_sigma, void* stream) {
+    return refine_certainty_launch("refine_certainty_bank", true, bank_sigma, bank, q, B, P, cand, cand_prob, k, topk, n_eval, scratch12,
+                                   W, C, beta, wstats, temperature, refined, choice, tol, code, stream);
 }

@@ -178,6 +178,16 @@ class DeferredExact:
             import time
             m.append(time.perf_counter())
 
+    def _bank_kw(self) -> dict:
+        """`kappa` for `forward_certain`, only for a refiner whose bank declares an error (any other refiner keeps the old call).
+        Such a bank makes more rows uncertain, never more than all: the queue takes at most B rows per step whatever the cause (its
+        sizing, `_alloc_queue`, assumes no less), and a re-encoded row is judged again but never queued again.  A row whose refiner
+        tolerance is 0 because of the bank is re-encoded once for nothing -- the exact embedding cannot settle it -- and is handed
+        out uncertain with its cause code."""
+        if getattr(self.refiner, 'bank_rel_tol', 0.0) > 0:
+            return {'kappa': self.model.certainty.kappa}
+        return {}
+
     # ------------------------------------------------------------------------------------------------ one step
     @torch.no_grad()
     def submit(self, pixel_values=None, embedding=None, index=None, meta=None, pixel_bytes=None) -> List[dict]:
@@ -249,7 +259,7 @@ class DeferredExact:
             # THE refinement of this rank's slice (pg_refine_forward_ex = pg_refine_forward + the records the certainty pass reads)
             new['refined_LLH'], new['refined_geocell'], rtol, rcode, self.boundary_checked = self.refiner.forward_certain(
                 ring['embedding'][own], ring['preds_LLH'][own], ring['topk_indices'][own], ring['topk_values'][own], W_head,
-                st['wstats'], st.get('drift'))
+                st['wstats'], st.get('drift'), **self._bank_kw())
             new.update(refine_tol=rtol, refine_code=rcode)
             for k in self.local_refiner:
                 self.local[k][lbase:lbase + b].copy_(new[k])
@@ -400,7 +410,8 @@ class DeferredExact:
         new = dict(sx)                                            # the patched columns' new rows
         if self.refiner is not None:
             new['refined_LLH'], new['refined_geocell'], rtol, rcode, _ = self.refiner.forward_certain(
-                sx['embedding'], sx['preds_LLH'], sx['topk_indices'], sx['topk_values'], model.cell_layer.weight.data, model.wstats(True), None)
+                sx['embedding'], sx['preds_LLH'], sx['topk_indices'], sx['topk_values'], model.cell_layer.weight.data, model.wstats(True), None,
+                **self._bank_kw())
             new.update(refine_tol=rtol, refine_code=rcode)
         certain_x, _, _ = ops.requeue_append(sx['tol'], rtol, rcode, thr_x, False)
         new.update(certain=certain_x.view(torch.bool), exact=self._true_cap[:n_pad])

@@ -127,18 +127,27 @@ def compute_embeddings(name: str, model: Any, data: Iterable, accelerator: Commu
 def embed_images(loaded_model: Any, dataset, accelerator: Optional[Communicator] = None,
                  batch_size: int = EMBED_BATCH_SIZE_PER_GPU, num_workers: int = 8,
                  out_dir: str = 'data/landmark_embeddings', raw_images: bool = False,
-                 max_packed_bytes: int = MAX_PACKED_BYTES):
+                 max_packed_bytes: int = MAX_PACKED_BYTES, exact: bool = False):
     """reference preprocessing/embed.py:45-83: wrap every split in EmbedDataset, one DataLoader per split
     (bs 512 per GPU, shuffle False), shard batches over ranks, embed train/val/test with a barrier between.
 
     raw_images=True (one image of any size per item): the workers decode and PACK (RawImageDataset, collate_packed) and the model
     resizes on the GPU -- uint8 pixels of the source size cross the bus instead of 1.35 MB of fp32 per image, and no worker runs
     Pillow's resize.  The batches are dealt to the ranks by the same rule, applied to the sample indices before anything is
-    loaded, so every rank decodes its own batches only.  What is written is the same."""
+    loaded, so every rank decodes its own batches only.  What is written is the same.
+
+    exact=True: every image goes through the exact encoder (`CLIPEmbedding.exact`: pg_vit_forward_precise, about 3x the time per
+    image; no guard measurement, no collectives for one) -- the embeddings to build a prototype bank from when its certainty is to
+    be judged at the exact tier's floor.  Either way rank 0 writes `embedding_meta.json` next to the `.npy` files when the model
+    can say what its embeddings are (`CLIPEmbedding.embedding_meta`: encoder, embedding_rel_tol, debias, fingerprint, mma_dtype)."""
     from torch.utils.data import DataLoader
     accelerator = accelerator or Communicator()
     results = {}
     loaded_model.eval()
+    if exact:
+        if not hasattr(loaded_model, 'exact'):
+            raise TypeError(f'embed_images(exact=True): {type(loaded_model).__name__} has no exact encoder route (`exact` attribute)')
+        loaded_model.exact = True
     for split_name in ('train', 'val', 'test'):
         if split_name not in dataset:
             continue
@@ -156,4 +165,25 @@ def embed_images(loaded_model: Any, dataset, accelerator: Optional[Communicator]
             model = loaded_model
         results[split_name] = compute_embeddings(split_name, model, sharded, accelerator, out_dir)
         accelerator.wait_for_everyone()
+    if accelerator.is_local_main_process and callable(getattr(loaded_model, 'embedding_meta', None)):
+        import json
+        os.makedirs(out_dir, exist_ok=True)
+        with open(os.path.join(out_dir, META_NAME), 'w') as f:       # as of the END of the run: after the guard's measurement
+            json.dump(loaded_model.embedding_meta(source=f'embed_images, splits {sorted(results)}'), f, indent=1, sort_keys=True)
     return results
+
+
+META_NAME = 'embedding_meta.json'
+
+
+def load_embedding_meta(path: str) -> dict:
+    """Read a sidecar `embed_images` wrote (the file, or the directory that holds it).  ValueError when it is not one."""
+    import json
+    if os.path.isdir(path):
+        path = os.path.join(path, META_NAME)
+    with open(path) as f:
+        meta = json.load(f)
+    need = ('encoder', 'embedding_rel_tol', 'debias', 'fingerprint', 'mma_dtype')
+    if not isinstance(meta, dict) or any(k not in meta for k in need):
+        raise ValueError(f'{path!r} is not an embedding sidecar (needs {", ".join(need)})')
+    return meta

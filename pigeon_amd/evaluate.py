@@ -319,7 +319,8 @@ def evaluate_model(model: SuperGuessr, dataset, metrics: Optional[Callable] = No
 def evaluate(model: str, dataset, yfcc: bool, landmarks: bool, base_model=None, heading: bool = False,
              refine: bool = True, geocell_path: Optional[str] = None, proto_path: Optional[str] = None,
              dataset_path=None, bank=None, head_state: Optional[str] = None, multi_task: bool = False,
-             calibration: Optional[str] = None, embedding_rel_tol: Optional[float] = None, country_path: Optional[str] = None):
+             calibration: Optional[str] = None, embedding_rel_tol: Optional[float] = None, country_path: Optional[str] = None,
+             bank_rel_tol=None):
     """reference evaluation/evaluate.py:10-85.
 
     `base_model`: as in the reference a STRING -- config.CLIP_MODEL for the pretrained tower, or the path of a checkpoint whose
@@ -341,6 +342,10 @@ def evaluate(model: str, dataset, yfcc: bool, landmarks: bool, base_model=None, 
     `embedding_rel_tol` (precomputed embeddings, `base_model=None`): the relative error the dataset's embeddings carry, passed to
     `SuperGuessr`.  None: the fast path's tolerance (1e-3, or what a calibration file says) -- right for files written by
     `run.py embed`; embeddings of the exact encoder or of the fp32 reference are declared with 5e-6.
+    `bank_rel_tol`: the relative error the prototype bank's rows carry (`ProtoRefiner(bank_rel_tol=...)`): a number, or the path
+    of the sidecar `run.py embed` wrote next to the embeddings the bank was built from (`embedding_meta.json`; its
+    `embedding_rel_tol` is taken, and a sidecar written with other weights than the loaded tower's ends the run, both fingerprints
+    named).  None: what the bank itself records, else exact.
     `country_path`: the GeoJSON of country polygons behind `Country_accuracy` (reference evaluation/metrics.py:17).  None: the file
     config.COUNTRY_PATH names if it exists, else the key is left out as before; a path given explicitly must exist.
     """
@@ -396,6 +401,7 @@ def evaluate(model: str, dataset, yfcc: bool, landmarks: bool, base_model=None, 
         else:
             write_calibration = int(os.environ.get('RANK', '0')) == 0
     refiner = None
+    bank_tol = _resolve_bank_rel_tol(bank_rel_tol, full_model)
     if refine:
         proto_model_path = cfg.PROTO_MODEL_YFCC_PATH if yfcc else cfg.PROTO_MODEL_PATH
         proto_path = proto_path or (cfg.PROTO_PATH_YFCC if yfcc else cfg.PROTO_PATH)
@@ -411,17 +417,20 @@ def evaluate(model: str, dataset, yfcc: bool, landmarks: bool, base_model=None, 
             except FileNotFoundError:
                 pass
         if bank is not None:
-            refiner = ProtoRefiner(40, False, 100000, bank=bank, temperature=0.6)
+            refiner = ProtoRefiner(40, False, 100000, bank=bank, temperature=0.6, bank_rel_tol=bank_tol)
         elif os.path.exists(packed):                                              # cached bank, packed CSR form
-            refiner = ProtoRefiner(40, False, 100000, bank=packed, temperature=0.6, verbose=False)
+            refiner = ProtoRefiner(40, False, 100000, bank=packed, temperature=0.6, verbose=False, bank_rel_tol=bank_tol)
         elif protos is not None:                                                  # cached prototypes (:76-80)
             refiner = ProtoRefiner(40, False, 100000, proto_path=proto_path, dataset_path=dataset_path,
-                                   protos=protos, temperature=0.6, verbose=False)
+                                   protos=protos, temperature=0.6, verbose=False, bank_rel_tol=bank_tol)
         else:                                                                     # first build (:72-75)
-            refiner = ProtoRefiner(20, False, 10000, proto_path=proto_path, dataset_path=dataset_path, temperature=1)
+            refiner = ProtoRefiner(20, False, 10000, proto_path=proto_path, dataset_path=dataset_path, temperature=1,
+                                   bank_rel_tol=bank_tol)
             os.makedirs(os.path.dirname(packed) or '.', exist_ok=True)
             refiner.host_bank.save(packed)
         print(refiner)
+        if refiner.bank_rel_tol > 0:
+            print(f'Prototype bank declared at a relative error of {refiner.bank_rel_tol:.3g}: the refiner\'s certainty accounts for it')
     metrics = compute_geoguessr_metrics if countries is None else (lambda r: compute_geoguessr_metrics(r, countries=countries))
     results = evaluate_model(full_model, dataset, metrics, None, refiner)
     if write_calibration:
@@ -432,6 +441,24 @@ def evaluate(model: str, dataset, yfcc: bool, landmarks: bool, base_model=None, 
             print(f'No calibration written to {calibration}: nothing was measured in this run (no encoder, the exact tier off, '
                   'or fewer than 8 samples)')
     return results
+
+
+def _resolve_bank_rel_tol(value, model: SuperGuessr) -> Optional[float]:
+    """`evaluate(bank_rel_tol=...)`: None, a number (also as a string), or the path of an `embedding_meta.json` sidecar, which must
+    have been written with the weights of `model`'s tower (no tower -- precomputed embeddings: nothing to compare with)."""
+    if value is None:
+        return None
+    try:
+        return float(value)
+    except (TypeError, ValueError):
+        pass
+    from .certainty import require_fingerprint
+    from .embed import load_embedding_meta
+    meta = load_embedding_meta(str(value))
+    if model.base_model is not None:
+        header = dict({'layers': '?', 'ln_fold': '?', 'source': ''}, **meta)
+        require_fingerprint(str(value), header, model._encoder().fingerprint())
+    return float(meta['embedding_rel_tol'])
 
 
 class PanoramaPipeline:

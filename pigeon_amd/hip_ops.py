@@ -1040,8 +1040,13 @@ def refine_forward_ex(bank: DeviceBank, q: torch.Tensor, init_llh: torch.Tensor,
 
 def refine_certainty(bank: DeviceBank, q: torch.Tensor, cand: torch.Tensor, cand_prob: Optional[torch.Tensor], topk: int,
                      scratch12: torch.Tensor, W: torch.Tensor, drift: Optional[torch.Tensor], wstats: torch.Tensor,
-                     temperature: float, refined: torch.Tensor, choice: torch.Tensor):
-    """pg_refine_certainty over the records refine_forward_ex left.  Returns (tol (B,) f32, code (B,) i32)."""
+                     temperature: float, refined: torch.Tensor, choice: torch.Tensor, bank_sigma: float = 0.0):
+    """pg_refine_certainty over the records refine_forward_ex left.  Returns (tol (B,) f32, code (B,) i32).
+    bank_sigma = kappa x the relative error the bank's rows carry (0: an exact bank, pg_refine_certainty as before; > 0:
+    pg_refine_certainty_bank, same meaning of tol and code)."""
+    bank_sigma = float(bank_sigma)
+    if not (0.0 <= bank_sigma < float("inf")):
+        raise _lib.PigeonHipError(f"refine_certainty: bank_sigma = {bank_sigma!r} (must be finite and >= 0)")
     _dev(q, torch.float32); _dev(cand, torch.int64); _dev(scratch12, torch.float32); _dev(W, torch.float32)
     _dev(wstats, torch.float32); _dev(refined, torch.int32); _dev(choice, torch.int32)
     B = q.shape[0]
@@ -1057,9 +1062,12 @@ def refine_certainty(bank: DeviceBank, q: torch.Tensor, cand: torch.Tensor, cand
         _dev(drift, torch.float32); _shape(drift, "drift", HIDDEN)
     tol = torch.empty((B,), dtype=torch.float32, device=q.device)
     code = torch.empty((B,), dtype=torch.int32, device=q.device)
-    check(load().pg_refine_certainty(C.byref(bank.struct), _p(q), B, P, _p(cand), _p(cand_prob), k, int(topk), int(n_eval), _p(scratch12),
-                                     _p(W), W.shape[0], _p(drift), _p(wstats), float(temperature), _p(refined), _p(choice), _p(tol),
-                                     _p(code), _stream()), "pg_refine_certainty")
+    args = (C.byref(bank.struct), _p(q), B, P, _p(cand), _p(cand_prob), k, int(topk), int(n_eval), _p(scratch12), _p(W), W.shape[0],
+            _p(drift), _p(wstats), float(temperature), _p(refined), _p(choice), _p(tol), _p(code))
+    if bank_sigma == 0.0:
+        check(load().pg_refine_certainty(*args, _stream()), "pg_refine_certainty")
+    else:
+        check(load().pg_refine_certainty_bank(*args, bank_sigma, _stream()), "pg_refine_certainty_bank")
     return tol, code
 
 

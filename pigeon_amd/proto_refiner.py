@@ -25,9 +25,12 @@ class HostBank:
     FIELDS = ("proto_emb", "cell_off", "proto_lnglat", "proto_count", "member_off", "member_idx",
               "train_emb", "train_lnglat")
 
-    def __init__(self, **kw):
+    def __init__(self, embedding_rel_tol=None, **kw):
+        """`embedding_rel_tol` (optional scalar): the relative error the bank's rows carry, as the encoder that wrote the training
+        embeddings declares it (`run.py embed` sidecar `embedding_meta.json`).  None: nothing declared -- the bank is taken as exact."""
         for f in self.FIELDS:
             setattr(self, f, kw[f])
+        self.embedding_rel_tol = check_rel_tol(embedding_rel_tol, 'HostBank: embedding_rel_tol')
 
     @property
     def num_cells(self):
@@ -36,12 +39,24 @@ class HostBank:
     def save(self, path: str):
         """Packed binary bank (one .npz): loads in seconds where the reference's 64-process Arrow build
         (proto_refiner.py:257-313) takes minutes."""
-        np.savez(path, **{f: getattr(self, f) for f in self.FIELDS})
+        extra = {} if self.embedding_rel_tol is None else {'embedding_rel_tol': np.float64(self.embedding_rel_tol)}
+        np.savez(path, **{f: getattr(self, f) for f in self.FIELDS}, **extra)
 
     @classmethod
     def load(cls, path: str) -> "HostBank":
         z = np.load(path)
-        return cls(**{f: z[f] for f in cls.FIELDS})
+        tol = float(z['embedding_rel_tol']) if 'embedding_rel_tol' in z.files else None     # (a file from before the field: None)
+        return cls(embedding_rel_tol=tol, **{f: z[f] for f in cls.FIELDS})
+
+
+def check_rel_tol(v, what: str):
+    """None, or a finite float >= 0 (ValueError otherwise): a declared relative embedding error."""
+    if v is None:
+        return None
+    v = float(v)
+    if not (0.0 <= v < float('inf')):
+        raise ValueError(f'{what} = {v!r}: a relative error must be finite and >= 0')
+    return v
 
 
 def _load_indices(index_json, verbose=False):
@@ -95,11 +110,12 @@ def _segmented_mean_gpu(train_emb, member_off, member_idx, device="cuda"):
     return out.cpu().numpy()
 
 
-def build_bank(proto_path: str, dataset_path, verbose: bool = False) -> HostBank:
+def build_bank(proto_path: str, dataset_path, verbose: bool = False, embedding_rel_tol=None) -> HostBank:
     """CSV + training embeddings -> CSR bank, reproducing the reference's prototype construction:
     rows of one geocell in CSV order (`proto_df.loc[cell]`, :299), a cell whose FIRST row has no indices is
     empty (:307-308), prototype embedding = fp32 mean of the member embeddings (:359-378), lng/lat/count
-    columns become float32/int under the torch format (:312)."""
+    columns become float32/int under the torch format (:312).  `embedding_rel_tol`: what the training embeddings' writer
+    declared (`HostBank`); it is recorded as given -- a prototype, the mean of its members, is not credited with less."""
     import pandas as pd
     train_emb, train_lnglat = _training_arrays(dataset_path)
     df = pd.read_csv(proto_path)
@@ -135,10 +151,10 @@ def build_bank(proto_path: str, dataset_path, verbose: bool = False) -> HostBank
     proto_emb = _segmented_mean_gpu(train_emb, member_off, member_idx) if P else np.zeros((0, train_emb.shape[1]), np.float32)
     return HostBank(proto_emb=proto_emb, cell_off=cell_off, proto_lnglat=np.stack([lng, lat], axis=1),
                     proto_count=cnt, member_off=member_off, member_idx=member_idx,
-                    train_emb=train_emb, train_lnglat=train_lnglat)
+                    train_emb=train_emb, train_lnglat=train_lnglat, embedding_rel_tol=embedding_rel_tol)
 
 
-def bank_from_protos(protos: List, dataset_path) -> HostBank:
+def bank_from_protos(protos: List, dataset_path, embedding_rel_tol=None) -> HostBank:
     """Convert the reference's own `refiner.protos` (list of per-cell HF Datasets or None, the object
     evaluation/evaluate.py:66-75 pickles and reloads) into the CSR bank."""
     train_emb, train_lnglat = _training_arrays(dataset_path)
@@ -159,7 +175,7 @@ def bank_from_protos(protos: List, dataset_path) -> HostBank:
                     proto_lnglat=np.concatenate(lnglat) if lnglat else np.zeros((0, 2), np.float32),
                     proto_count=np.concatenate(cnt) if cnt else np.zeros((0,), np.int32), member_off=member_off,
                     member_idx=np.fromiter((i for l in idxs for i in l), dtype=np.int64, count=int(member_off[-1])),
-                    train_emb=train_emb, train_lnglat=train_lnglat)
+                    train_emb=train_emb, train_lnglat=train_lnglat, embedding_rel_tol=embedding_rel_tol)
 
 
 def load_refiner_cache(path: str):
@@ -252,10 +268,14 @@ class ProtoRefiner(nn.Module):
     def __init__(self, topk: int = 5, hedge: bool = False, max_refinement: int = 1000,
                  temperature: float = 1.6, proto_path: str = PROTO_PATH,
                  dataset_path: str = DATASET_PATH, protos: List = None,
-                 verbose: bool = False, bank=None, device: str = 'cuda'):
+                 verbose: bool = False, bank=None, device: str = 'cuda', bank_rel_tol=None):
         """Arguments as the reference.  Extra: `bank` (HostBank / SyntheticBank / path to a packed .npz) supplies
-        the CSR bank directly; `protos` accepts the reference's pickled list of per-cell datasets."""
+        the CSR bank directly; `protos` accepts the reference's pickled list of per-cell datasets.
+        `bank_rel_tol`: the relative error of the bank's rows that `forward_certain` accounts for (error model: csrc/certainty.hip
+        "Bank error").  None: what the bank records (`HostBank.embedding_rel_tol`), else 0.0 -- an exact bank, the behaviour without
+        the keyword.  An explicit number wins; a negative or non-finite one is a ValueError."""
         super(ProtoRefiner, self).__init__()
+        bank_rel_tol = check_rel_tol(bank_rel_tol, 'ProtoRefiner: bank_rel_tol')
         if hedge:
             raise NotImplementedError('hedge=True is out of scope: disabled in the final model (models/README.md:11)')
         self.topk = topk
@@ -271,6 +291,8 @@ class ProtoRefiner(nn.Module):
             host = build_bank(proto_path, dataset_path, verbose)
             print('Initialization of ProtoRefiner complete.')
         self.host_bank = host
+        recorded = getattr(host, 'embedding_rel_tol', None)
+        self.bank_rel_tol = bank_rel_tol if bank_rel_tol is not None else (0.0 if recorded is None else float(recorded))
         self.num_geocells = host.cell_off.shape[0] - 1
         self.protos = host                     # attribute name kept (evaluate.py:66-75 reads `ref.protos`)
         self.temperature = Parameter(torch.tensor(temperature), requires_grad=False)
@@ -329,13 +351,15 @@ class ProtoRefiner(nn.Module):
 
     @torch.no_grad()
     def forward_certain(self, embedding: Tensor, initial_preds: Tensor, candidate_cells: Tensor, candidate_probs: Tensor,
-                        head_weight: Tensor, wstats: Tensor, drift: Tensor = None):
+                        head_weight: Tensor, wstats: Tensor, drift: Tensor = None, kappa: float = None):
         """`forward` plus the TOLERANCE of its discrete outputs against an embedding error (round 5; error model:
         pigeon_amd/certainty.py, kernels: pg_refine_forward_ex + pg_refine_certainty).  `candidate_cells` / `candidate_probs` may hold
         more than `topk` candidates (SuperGuessr computes `num_candidates + 4`): up to 4 of those beyond `topk` are evaluated too --
         never selected -- so that the pass can tell whether a cell just outside the set could get in and win; with none beyond
         `topk` that question stays open (`boundary_checked` False).  `head_weight` (C,1024) is the geocell head's weight matrix: the
         candidates' probabilities move with the embedding through it.
+        `kappa`: the z-score the caller compares `tol` with (`Certainty.kappa`); needed when `bank_rel_tol` > 0 -- the bank's error
+        enters as bank_sigma = kappa * bank_rel_tol (pg_refine_certainty_bank) -- and ignored for an exact bank.
         Returns (preds_LLH (B,2) f32, preds_geocell (B,) i64, tol (B,) f32, code (B,) i32, boundary_checked)."""
         assert self.topk <= candidate_cells.size(1)
         dev = embedding.device
@@ -350,6 +374,13 @@ class ProtoRefiner(nn.Module):
         T = self._temperature_value()
         llh, cell, choice, refined, scratch = hip_ops.refine_forward_ex(bank, q, init, cand, probs, self.topk, n_eval, T,
                                                                        float(self.max_refinement))
-        tol, code = hip_ops.refine_certainty(bank, q, cand, probs, self.topk, scratch, head_weight, drift, wstats, T, refined, choice)
+        bank_sigma = 0.0
+        if self.bank_rel_tol > 0:
+            if kappa is None:
+                raise ValueError(f'ProtoRefiner.forward_certain: bank_rel_tol = {self.bank_rel_tol:g} needs `kappa` (the z-score the '
+                                 f'tolerances are compared with)')
+            bank_sigma = float(kappa) * self.bank_rel_tol
+        tol, code = hip_ops.refine_certainty(bank, q, cand, probs, self.topk, scratch, head_weight, drift, wstats, T, refined, choice,
+                                             bank_sigma=bank_sigma)
         self.last_scratch = scratch[:, :self.topk, :4]
         return llh, cell, tol, code, n_eval > self.topk

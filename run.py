@@ -14,6 +14,7 @@ replaced by seeded synthetic fixtures:  `--synthetic N` embeds / evaluates N syn
   python run.py evaluate saved_models/head_mt.model -m -l data/hf_eval -b saved_models/StreetviewCLIP.model   (a multi-task checkpoint)
   torchrun --nproc-per-node 8 --master-addr 127.0.0.1 run.py embed random --synthetic 4096
   python run.py embed random --synthetic 64 --calibration cal.npz                  # first run writes cal.npz, later runs load it
+  python run.py embed saved_models/StreetviewCLIP.model -l data/hf_dataset --exact  # the exact encoder: embeddings for a prototype bank
 """
 import argparse
 import logging
@@ -71,6 +72,16 @@ argp.add_argument('--embedding-rel-tol', dest='embedding_rel_tol', type=float, d
                   help="evaluate on precomputed embeddings: the relative error they carry, against which their certainty is judged.  "
                        "Default: the 16-bit path's tolerance (1e-3, or what --calibration says), as `embed` writes them; 5e-6 declares "
                        "embeddings of the exact encoder or of the fp32 reference")
+
+
+argp.add_argument('--exact', action='store_true', default=False,
+                  help="embed: every image through the exact encoder (pg_vit_forward_precise, about 3x the time per image): the "
+                       "embeddings to build a prototype bank from.  The sidecar embedding_meta.json written next to the .npy files "
+                       "then says encoder 'exact' and the exact tier's tolerance")
+argp.add_argument('--bank-rel-tol', dest='bank_rel_tol', default=None, metavar='TOL|FILE',
+                  help="evaluate: the relative error the prototype bank's embeddings carry -- a number, or the embedding_meta.json "
+                       "that `embed` wrote next to the embeddings the bank was built from (a file written with other weights than "
+                       "the loaded tower's ends the run).  Default: what the bank records, else exact")
 
 
 argp.add_argument('--countries', default=None, metavar='FILE',
@@ -169,7 +180,7 @@ def _dispatch(args, comm):
             from datasets import DatasetDict
             dataset = DatasetDict.load_from_disk(args.load[0])
         embed_images(embedder, dataset, comm, out_dir=args.out_dir, num_workers=0 if args.synthetic else 8,
-                     raw_images=args.raw_images)
+                     raw_images=args.raw_images, exact=args.exact)
         if args.calibration and not have_cal and comm.is_main_process:
             if embedder.guard_stats is not None:
                 embedder.save_calibration(args.calibration, source=f'run.py embed, first batch, {embedder.guard_stats["images"]} images')
@@ -202,7 +213,7 @@ def _dispatch(args, comm):
         results = evaluate(args.name, dataset, yfcc=args.yfcc, base_model=_vision_model(args), refine=True,
                            landmarks=args.landmarks, geocell_path=geocell_path, bank=bank, heading=args.heading,
                            multi_task=args.multitask, calibration=args.calibration, embedding_rel_tol=args.embedding_rel_tol,
-                           country_path=args.countries)
+                           country_path=args.countries, bank_rel_tol=args.bank_rel_tol)
         if comm.is_main_process:
             print({k: (v if not hasattr(v, 'shape') or v.shape == () else tuple(v.shape)) for k, v in results.items() if k != 'exact_passes'})
             if 'geocell_certain' in results:
