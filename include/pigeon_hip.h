@@ -48,7 +48,9 @@ extern "C" {
                               *    + pg_haversine_blocks, pg_optics_graph, pg_optics_plan, pg_tune_optics_lds_points, additive;
                               *    + pg_region_locate, pg_region_classify, pg_region_nearest, pg_region_plan, pg_tune_region_wave_edges, additive;
                               *    + PG_DTYPE_U8 pixels and pg_prep_norm_lut, additive; + pg_vit_param_read, additive;
-                              *    + pg_refine_certainty_bank, additive) */
+                              *    + pg_refine_certainty_bank, additive;
+                              *    + pg_jpeg_probe, pg_jpeg_reason, pg_jpeg_plan, pg_jpeg_entropy_decode, pg_jpeg_forward, pg_jpeg_info and
+                              *      pg_jpeg_item, additive) */
 
 const char* pg_last_error(void);
 int pg_abi_version(void);
@@ -488,6 +490,90 @@ int pg_prep_ragged_destroy(pg_prep_ragged* h);
  * LDS, widest in_w x 3 + 32 bytes (48 KiB + 32 at in_w = 16384). */
 int pg_prep_ragged_forward(pg_prep_ragged* h, const void* packed_dev, size_t packed_bytes, const pg_prep_item* items_host, int n,
                            void* out, int out_dtype, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Baseline JPEG decoding in front of the ragged resize: files go in as bytes, the host parses the headers and undoes the Huffman
+ * coding (pg_jpeg_entropy_decode, serial per file, a thread per file), the GPU dequantises, applies libjpeg's accurate integer inverse
+ * DCT, expands the chroma as libjpeg-turbo's "fancy" upsampling does and converts to RGB (pg_jpeg_forward, two launches), writing
+ * straight into the packed buffer pg_prep_ragged_forward reads.  The pixels are the ones Pillow (libjpeg-turbo) produces for
+ * `Image.open(f).convert('RGB')`, bit for bit.
+ *
+ * Supported: SOF0 / SOF1 with 8-bit samples and Huffman coding, one interleaved scan, 1 component (grey: R = G = B = Y) or 3
+ * components libjpeg reads as YCbCr (a JFIF marker, or an Adobe marker with transform 1, or neither and component ids other than
+ * 'R','G','B'), luma sampling 1x1, 2x1 or 2x2 with both chroma components 1x1, sizes 1..16384.  Anything else is REFUSED by
+ * pg_jpeg_probe with a reason -- not an error: the caller decodes such a file elsewhere and copies its pixels to its place.
+ * ------------------------------------------------------------------------------------------------ */
+#define PG_JPEG_R_OK            0
+#define PG_JPEG_R_NOT_JPEG      1
+#define PG_JPEG_R_PROGRESSIVE   2
+#define PG_JPEG_R_LOSSLESS      3
+#define PG_JPEG_R_HIERARCHICAL  4
+#define PG_JPEG_R_ARITHMETIC    5
+#define PG_JPEG_R_PRECISION     6    /* 12-bit samples */
+#define PG_JPEG_R_COMPONENTS    7    /* 2 or 4 components (CMYK / YCCK) */
+#define PG_JPEG_R_COLORSPACE    8    /* Adobe transform 0 or 2, component ids 'R','G','B' */
+#define PG_JPEG_R_SAMPLING      9    /* 4:4:0, 4:1:1, chroma not 1x1 */
+#define PG_JPEG_R_MULTISCAN     10
+#define PG_JPEG_R_DNL           11
+#define PG_JPEG_R_SIZE          12   /* height or width 0 or above 16384 */
+#define PG_JPEG_R_MALFORMED     13   /* the header is damaged or ends before SOS */
+typedef struct pg_jpeg_info {
+    int32_t reason;                   /* PG_JPEG_R_* */
+    int32_t height, width;            /* as far as the header got, else 0 */
+    int32_t ncomp;                    /* 1 or 3 where reason is PG_JPEG_R_OK */
+    int32_t hs, vs;                   /* luma sampling: 1x1, 2x1 or 2x2 (1x1 for grey) */
+    int32_t reserved[2];              /* zero */
+} pg_jpeg_info;
+/* One image of a batch (plain data, PG_JPEG_ITEM_BYTES bytes).  ncomp = 0 marks an image whose pixels the caller supplies itself (a
+ * refused file): it has a place in the packed buffer and nothing else.
+ *
+ *   coefficient buffer  [ n descriptors, rounded up to 128 bytes | blocks of image 0 | blocks of image 1 | ... ]   per image and
+ *                       component the blocks of the component's padded block grid (whole MCUs: bw x bh blocks) in RASTER order, each
+ *                       64 int16 in natural (de-zigzagged) order, a row of 8 = one row of the block; components in order, images in
+ *                       order, no gaps.  The descriptors travel in the buffer's head, so one copy carries both.
+ *   workspace           per image and component one 8-bit plane of (bh * 8) rows of (bw * 8) bytes, each at a multiple of 256.
+ *   packed buffer       the one of pg_prep_ragged_forward: rgb_off is the image's pg_prep_item.src_off. */
+#define PG_JPEG_ITEM_BYTES 640
+typedef struct pg_jpeg_item {
+    uint64_t rgb_off;                 /* byte offset of the image's (height, width, 3) RGB in the packed buffer (multiple of 16) */
+    uint64_t coef_off[3];             /* byte offset of each component's blocks in the coefficient buffer (multiples of 128) */
+    uint64_t plane_off[3];            /* byte offset of each component's plane in the workspace (multiples of 256) */
+    int32_t height, width;
+    int32_t ncomp;                    /* 1, 3, or 0: pixels supplied by the caller */
+    int32_t hs, vs;                   /* luma sampling */
+    int32_t bw[3], bh[3];             /* block grid per component */
+    int32_t qsel[3];                  /* which of qt[] each component is dequantised with (filled by pg_jpeg_entropy_decode) */
+    int32_t reserved[4];              /* zero */
+    uint16_t qt[4][64];               /* quantisation tables, natural order (filled by pg_jpeg_entropy_decode) */
+} pg_jpeg_item;
+/* HOST ONLY.  Reads the markers of `data` up to SOS and fills *info.  Always PG_OK for non-null arguments: a refusal is a value of
+ * info->reason.  pg_jpeg_reason: a static string for a reason code. */
+int pg_jpeg_probe(const void* data, size_t nbytes, pg_jpeg_info* info);
+const char* pg_jpeg_reason(int reason);
+/* HOST ONLY.  The layout of a batch: infos[i] with reason PG_JPEG_R_OK is decoded on the GPU, any other reason makes image i one the
+ * caller supplies (ncomp = 0; its height and width must be set by the caller).  Fills items_out[n], prep_items_out[n] and the four
+ * sizes; prep_items_out, *packed_bytes and *prep_workspace_bytes are exactly what pg_prep_ragged_plan gives for the same (height,
+ * width) list.  PG_EINVAL naming the image for a size outside 1..16384 or a sampling the decoder does not have. */
+int pg_jpeg_plan(int n, const pg_jpeg_info* infos, pg_jpeg_item* items_out, pg_prep_item* prep_items_out, size_t* coef_bytes,
+                 size_t* workspace_bytes, size_t* packed_bytes, size_t* prep_workspace_bytes);
+/* HOST ONLY.  Entropy-decodes the files of the batch whose items have ncomp != 0 into the HOST coefficient buffer `coef` (coef_bytes
+ * bytes, 16-byte aligned, laid out by pg_jpeg_plan; the regions are zeroed first) and fills each item's qsel / qt; finally copies the
+ * n descriptors into the buffer's head.  data[i] / nbytes[i]: file i (ignored where ncomp = 0).  Files are independent: `threads`
+ * (clamped to 1..16) workers take them in turn.  A Huffman code that does not exist, a marker or the end of the data inside an MCU,
+ * a coefficient index past 63, a wrong RSTn or a missing EOI is PG_EINVAL with a message naming the image, whose index goes to
+ * *bad_index (may be NULL; the lowest such index).  No read leaves [data[i], data[i] + nbytes[i]) and no write leaves the image's
+ * coefficient region, whatever the bytes are. */
+int pg_jpeg_entropy_decode(int n, const void* const* data, const size_t* nbytes, pg_jpeg_item* items, void* coef, size_t coef_bytes,
+                           int threads, int* bad_index);
+/* coef_dev: DEVICE copy of the coefficient buffer (16-byte aligned; its head MUST hold items_host).  Writes the RGB of every image with
+ * ncomp != 0 to [rgb_off, rgb_off + height * width * 3) of packed_dev and nothing else behind the descriptors; copies prep_items_host
+ * (n * PG_PREP_ITEM_BYTES bytes) into the head of packed_dev, which can then go to pg_prep_ragged_forward as it is.  Before anything is
+ * launched every descriptor is checked against its own size and sampling and against the three buffer sizes -- grids, ascending
+ * overlap-free offsets, alignment, rgb_off == prep_items_host[i].src_off: PG_EINVAL naming the image.  The arithmetic is 32-bit with
+ * wrap-around, so any coefficient values give defined pixels and none can move an address.  n = 0 is a no-op.  Asynchronous on
+ * `stream`: one copy and two launches. */
+int pg_jpeg_forward(const void* coef_dev, size_t coef_bytes, const pg_jpeg_item* items_host, const pg_prep_item* prep_items_host, int n,
+                    void* packed_dev, size_t packed_bytes, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * The one collective of the path: all-gather over RCCL (xGMI inside a node).

@@ -51,6 +51,25 @@ PREP_ITEM_BYTES = 80
 assert C.sizeof(PrepItem) == PREP_ITEM_BYTES
 
 
+class JpegInfo(C.Structure):
+    """pg_jpeg_info (include/pigeon_hip.h): what pg_jpeg_probe reads from a file's header; reason 0 = decoded on the GPU."""
+    _fields_ = [("reason", C.c_int32), ("height", C.c_int32), ("width", C.c_int32), ("ncomp", C.c_int32), ("hs", C.c_int32),
+                ("vs", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+
+class JpegItem(C.Structure):
+    """pg_jpeg_item (include/pigeon_hip.h): one image of a JPEG batch, JPEG_ITEM_BYTES bytes."""
+    _fields_ = [("rgb_off", C.c_uint64), ("coef_off", C.c_uint64 * 3), ("plane_off", C.c_uint64 * 3), ("height", C.c_int32),
+                ("width", C.c_int32), ("ncomp", C.c_int32), ("hs", C.c_int32), ("vs", C.c_int32), ("bw", C.c_int32 * 3),
+                ("bh", C.c_int32 * 3), ("qsel", C.c_int32 * 3), ("reserved", C.c_int32 * 4), ("qt", (C.c_uint16 * 64) * 4)]
+
+
+JPEG_ITEM_BYTES = 640
+assert C.sizeof(JpegItem) == JPEG_ITEM_BYTES and C.sizeof(JpegInfo) == 32
+JPEG_REASONS = ("ok", "not_jpeg", "progressive", "lossless", "hierarchical", "arithmetic", "precision", "components", "colorspace",
+                "sampling", "multiscan", "dnl", "size", "malformed")          # PG_JPEG_R_*: index = code
+
+
 # name -> (restype, argtypes); must list EVERY symbol declared in include/pigeon_hip.h (tests check this)
 _P, _I, _I64, _F, _D, _SZ = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_double, C.c_size_t
 SIGNATURES = {
@@ -103,6 +122,12 @@ SIGNATURES = {
     "pg_prep_ragged_create": (_I, [C.POINTER(_P), _I]),
     "pg_prep_ragged_destroy": (_I, [_P]),
     "pg_prep_ragged_forward": (_I, [_P, _P, _SZ, C.POINTER(PrepItem), _I, _P, _I, _P, _SZ, _P]),
+    "pg_jpeg_probe": (_I, [_P, _SZ, C.POINTER(JpegInfo)]),
+    "pg_jpeg_reason": (C.c_char_p, [_I]),
+    "pg_jpeg_plan": (_I, [_I, C.POINTER(JpegInfo), C.POINTER(JpegItem), C.POINTER(PrepItem), C.POINTER(_SZ), C.POINTER(_SZ), C.POINTER(_SZ),
+                          C.POINTER(_SZ)]),
+    "pg_jpeg_entropy_decode": (_I, [_I, C.POINTER(_P), C.POINTER(_SZ), C.POINTER(JpegItem), _P, _SZ, _I, C.POINTER(_I)]),
+    "pg_jpeg_forward": (_I, [_P, _SZ, C.POINTER(JpegItem), C.POINTER(PrepItem), _I, _P, _SZ, _P, _SZ, _P]),
     "pg_proto_build": (_I, [_P, _I, _I64, _P, _P, _I64, _P, _P]),
     "pg_haversine_matrix": (_I, [_P, _I, _P, _I, _I, _P, _P]),
     "pg_haversine_pairs": (_I, [_P, _P, _I, _I64, _P, _P]),

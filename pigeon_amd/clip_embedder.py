@@ -19,6 +19,7 @@ from torch import Tensor
 from . import hip_ops, synthetic
 from .certainty import SAFETY, CalibrationError, Certainty, combine_ranks, outside_contract, require_fingerprint
 from .config import CLIP_MODEL, OPENAI_CLIP_MEAN, OPENAI_CLIP_STD
+from .jpeg import EncodedImages, decode_chunks, decode_images  # noqa: F401  (re-exported)
 from .packing import PackedImages, as_rgb_array, check_rgb_u8, chunk_by_bytes, pack_images, pack_into, packed_layout  # noqa: F401  (re-exported)
 from .utils import load_state_dict
 
@@ -348,6 +349,15 @@ def _gpu_preprocess_packed(packed: PackedImages, dev, out_dtype) -> Tensor:
     return _ragged_forward(stage, plan, dev, out_dtype, staged=True)
 
 
+def _gpu_preprocess_encoded(encoded: EncodedImages, dev, out_dtype) -> Tensor:
+    """Files as bytes: decoded on the GPU into the packed buffer (pigeon_amd/jpeg.py), resized from there -- no host round trip."""
+    outs = []
+    for dec in decode_chunks(encoded, dev, RAGGED_MAX_BYTES):
+        with torch.cuda.device(dev):
+            outs.append(_ragged_preprocessor(dev.index).forward(dec.packed, dec.plan, out_dtype, header_written=True))
+    return outs[0] if len(outs) == 1 else torch.cat(outs, dim=0)
+
+
 def gpu_preprocess(images, device="cuda", out_dtype: torch.dtype = torch.float32) -> Tensor:
     """See `_gpu_preprocess`.  Callers from several threads are served one after the other: the pinned staging buffers are shared."""
     with _PREP_LOCK:
@@ -356,7 +366,7 @@ def gpu_preprocess(images, device="cuda", out_dtype: torch.dtype = torch.float32
 
 def _gpu_preprocess(images, device="cuda", out_dtype: torch.dtype = torch.float32) -> Tensor:
     """CLIP preprocessing on the GPU: `images` is a uint8 RGB tensor / ndarray (N,H,W,3) or (H,W,3), a list of PIL images / arrays,
-    or a `PackedImages`.  Tensors and lists of ONE shape run pg_prep_forward (a handle per geometry); a `PackedImages` and a list of
+    a `PackedImages`, or an `EncodedImages` (files as bytes: decoded on the GPU, Pillow's pixels bit for bit, then resized in place).  Tensors and lists of ONE shape run pg_prep_forward (a handle per geometry); a `PackedImages` and a list of
     several shapes run pg_prep_ragged_forward: one packed staging buffer and, per chunk of at most RAGGED_MAX_BYTES (256 MiB) of packed
     bytes, one copy and three launches whatever the sizes.  A PINNED `PackedImages` is copied from in place: its head is overwritten
     with the descriptors and the buffer belongs to the call until `copy_event` (set on the object) has passed.  Returns the
@@ -368,6 +378,8 @@ def _gpu_preprocess(images, device="cuda", out_dtype: torch.dtype = torch.float3
         dev = torch.device("cuda", torch.cuda.current_device())
     if isinstance(images, PackedImages):
         return _gpu_preprocess_packed(images, dev, out_dtype)
+    if isinstance(images, EncodedImages):
+        return _gpu_preprocess_encoded(images, dev, out_dtype)
     if hasattr(images, "convert"):                                 # one PIL image, as `processor(images=img)` accepts it
         images = [images]
     if torch.is_tensor(images) or isinstance(images, np.ndarray):

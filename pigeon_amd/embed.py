@@ -44,14 +44,19 @@ class EmbedDataset:
 
 class RawImageDataset:
     """The raw flavour of EmbedDataset: yields (uint8 (H,W,3) RGB array, index).  Decoding and `convert('RGB')` run here, in the
-    DataLoader worker; nothing is resized -- that happens on the GPU (pg_prep_ragged_forward), for the whole batch at once."""
+    DataLoader worker; nothing is resized -- that happens on the GPU (pg_prep_ragged_forward), for the whole batch at once.
+    encoded=True: yields (file bytes, index) instead -- the item's `image` is bytes, a path or the dict of a HF `Image(decode=False)`
+    column; the worker only reads, and the decode runs on the GPU as well (pg_jpeg_forward)."""
 
-    def __init__(self, dataset):
-        self.dataset = dataset
+    def __init__(self, dataset, encoded: bool = False):
+        self.dataset, self.encoded = dataset, encoded
 
     def __getitem__(self, idx):
         from .packing import as_rgb_array, check_rgb_u8
         data = self.dataset[idx]
+        if self.encoded:                                           # the file's bytes as they are: the GPU decodes (pigeon_amd/jpeg.py)
+            from .jpeg import image_bytes
+            return image_bytes(data['image']), data['index']
         a = as_rgb_array(data['image'])
         check_rgb_u8(a)
         return a, data['index']
@@ -63,11 +68,14 @@ class RawImageDataset:
 MAX_PACKED_BYTES = 256 << 20
 
 
-def collate_packed(batch, max_packed_bytes: int = MAX_PACKED_BYTES):
+def collate_packed(batch, max_packed_bytes: int = MAX_PACKED_BYTES, encoded: bool = False):
     """collate_fn for RawImageDataset: [(array, index), ...] -> ([PackedImages, ...], index tensor).  The batch is cut, in order,
     into chunks of at most `max_packed_bytes` packed bytes each (an image above the budget travels alone), which bounds the
     staging buffer and the GPU workspace whatever the photo sizes; the chunks' images, concatenated, are the batch's."""
     from .packing import chunk_by_bytes, pack_images
+    if encoded:                                                    # one EncodedImages: gpu_preprocess cuts it by the decoded sizes itself
+        from .jpeg import EncodedImages
+        return [EncodedImages([f for f, _ in batch])], torch.as_tensor([int(i) for _, i in batch], dtype=torch.int64)
     arrs = [a for a, _ in batch]
     chunks = [pack_images(arrs[lo:hi]) for lo, hi in chunk_by_bytes([a.shape[:2] for a in arrs], max_packed_bytes)]
     return chunks, torch.as_tensor([int(i) for _, i in batch], dtype=torch.int64)
@@ -127,7 +135,7 @@ def compute_embeddings(name: str, model: Any, data: Iterable, accelerator: Commu
 def embed_images(loaded_model: Any, dataset, accelerator: Optional[Communicator] = None,
                  batch_size: int = EMBED_BATCH_SIZE_PER_GPU, num_workers: int = 8,
                  out_dir: str = 'data/landmark_embeddings', raw_images: bool = False,
-                 max_packed_bytes: int = MAX_PACKED_BYTES, exact: bool = False):
+                 max_packed_bytes: int = MAX_PACKED_BYTES, exact: bool = False, encoded: bool = False):
     """reference preprocessing/embed.py:45-83: wrap every split in EmbedDataset, one DataLoader per split
     (bs 512 per GPU, shuffle False), shard batches over ranks, embed train/val/test with a barrier between.
 
@@ -135,6 +143,10 @@ def embed_images(loaded_model: Any, dataset, accelerator: Optional[Communicator]
     resizes on the GPU -- uint8 pixels of the source size cross the bus instead of 1.35 MB of fp32 per image, and no worker runs
     Pillow's resize.  The batches are dealt to the ranks by the same rule, applied to the sample indices before anything is
     loaded, so every rank decodes its own batches only.  What is written is the same.
+
+    encoded=True (with raw_images): the workers only READ -- items carry the file's bytes (`RawImageDataset(encoded=True)`), about a
+    tenth of the decoded pixels through the workers' pipes -- and baseline JPEGs are decoded on the GPU into the buffer the resize
+    reads (pigeon_amd/jpeg.py; other files by Pillow in the main process).  What is written is the same.
 
     exact=True: every image goes through the exact encoder (`CLIPEmbedding.exact`: pg_vit_forward_precise, about 3x the time per
     image; no guard measurement, no collectives for one) -- the embeddings to build a prototype bank from when its certainty is to
@@ -148,6 +160,8 @@ def embed_images(loaded_model: Any, dataset, accelerator: Optional[Communicator]
         if not hasattr(loaded_model, 'exact'):
             raise TypeError(f'embed_images(exact=True): {type(loaded_model).__name__} has no exact encoder route (`exact` attribute)')
         loaded_model.exact = True
+    if encoded and not raw_images:
+        raise ValueError('embed_images(encoded=True) is a mode of raw_images=True')
     for split_name in ('train', 'val', 'test'):
         if split_name not in dataset:
             continue
@@ -156,8 +170,8 @@ def embed_images(loaded_model: Any, dataset, accelerator: Optional[Communicator]
             n = len(dataset[split_name])
             mine = list(shard_batches([list(range(i, min(i + batch_size, n))) for i in range(0, n, batch_size)],
                                       accelerator.rank, accelerator.world_size))
-            sharded = DataLoader(RawImageDataset(dataset[split_name]), batch_sampler=mine, num_workers=num_workers,
-                                 collate_fn=partial(collate_packed, max_packed_bytes=max_packed_bytes))
+            sharded = DataLoader(RawImageDataset(dataset[split_name], encoded=encoded), batch_sampler=mine, num_workers=num_workers,
+                                 collate_fn=partial(collate_packed, max_packed_bytes=max_packed_bytes, encoded=encoded))
             model = _ChunkedModel(loaded_model)
         else:
             loader = DataLoader(EmbedDataset(dataset[split_name]), batch_size, shuffle=False, num_workers=num_workers)

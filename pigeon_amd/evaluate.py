@@ -165,10 +165,12 @@ class ImageEvalDataset:
     decodes and packs (`packing.pack_images`: the raw views in one uint8 buffer) and passes every other column (`labels`,
     `labels_clf`, ...) through; `collate` joins a batch's items into ONE `PackedImages`, and the process that owns the GPU resizes
     the whole mixed-size batch to 8-bit pixels in one ragged call (`preprocess`) and submits them as `pixel_bytes`.  String keys are
-    column reads of the wrapped dataset (`dataset['labels']`, as `evaluate_model` collects the labels for the metrics)."""
+    column reads of the wrapped dataset (`dataset['labels']`, as `evaluate_model` collects the labels for the metrics).
+    encoded=True: the image columns hold files (bytes, paths, or the dicts of HF `Image(decode=False)` columns); a worker ships the
+    bytes as an `EncodedImages` and the decode runs on the GPU too (`gpu_preprocess(EncodedImages)`, pigeon_amd/jpeg.py)."""
 
-    def __init__(self, dataset):
-        self.dataset = dataset
+    def __init__(self, dataset, encoded: bool = False):
+        self.dataset, self.encoded = dataset, encoded
 
     def __len__(self) -> int:
         return len(self.dataset)
@@ -182,6 +184,10 @@ class ImageEvalDataset:
             raise KeyError("ImageEvalDataset: items need an 'image' column (or 'image', 'image_2', 'image_3', 'image_4')")
         views = [item[k] for k in (IMAGE_KEYS if 'image_2' in item else IMAGE_KEYS[:1])]
         out = {k: v for k, v in item.items() if 'image' not in k}              # (the reference drops every image column the same way)
+        if self.encoded:                                           # the files' bytes as they are: the worker does nothing but read
+            from .jpeg import EncodedImages, image_bytes
+            out['images'] = EncodedImages([image_bytes(v) for v in views])
+            return out
         out['images'] = pack_images([v.numpy() if torch.is_tensor(v) else v for v in views])
         return out
 
@@ -195,7 +201,9 @@ class ImageEvalDataset:
         if len(views) != 1:
             raise ValueError(f'ImageEvalDataset: items of one batch hold {sorted(views)} views; every item must have the same number')
         out = default_collate([{k: v for k, v in b.items() if k != 'images'} for b in batch])
-        out['images'] = concat_packed([b['images'] for b in batch])
+        from .jpeg import EncodedImages
+        parts = [b['images'] for b in batch]
+        out['images'] = EncodedImages.concat(parts) if isinstance(parts[0], EncodedImages) else concat_packed(parts)
         out['views'] = views.pop()
         return out
 

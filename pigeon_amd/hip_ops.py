@@ -541,6 +541,113 @@ class RaggedPreprocessor:
             pass
 
 
+# ----------------------------------------------------------------------------------------- JPEG decoding
+class JpegEntropyError(ValueError):
+    """A supported file whose scan is damaged; `index` is the image's place in the batch."""
+
+    def __init__(self, index: int, message: str):
+        super().__init__(message)
+        self.index = int(index)
+
+
+def default_jpeg_threads() -> int:
+    """Workers of the host stage: the CPUs this process may run on, 16 at the most (never the machine's count)."""
+    import os
+    return max(1, min(16, len(os.sched_getaffinity(0))))
+
+
+def jpeg_probe(data) -> "_lib.JpegInfo":
+    """pg_jpeg_probe: the header of one file (bytes).  `.reason` 0 = decoded on the GPU, else why not (`jpeg_reason`).  Host only."""
+    if not isinstance(data, (bytes, bytearray, memoryview)):
+        raise _lib.PigeonHipError(f"jpeg_probe expects bytes, got {type(data).__name__}")
+    data = bytes(data)
+    info = _lib.JpegInfo()
+    check(load().pg_jpeg_probe(data if data else b"\0", len(data), C.byref(info)), "pg_jpeg_probe")
+    return info
+
+
+def jpeg_reason(code: int) -> str:
+    """Short name of a PG_JPEG_R_* code ("progressive", "components", ...); the library's sentence is `jpeg_reason_text`."""
+    return _lib.JPEG_REASONS[code] if 0 <= int(code) < len(_lib.JPEG_REASONS) else f"reason_{int(code)}"
+
+
+def jpeg_reason_text(code: int) -> str:
+    return load().pg_jpeg_reason(int(code)).decode()
+
+
+class JpegPlan:
+    """What pg_jpeg_plan makes of a list of probed headers: one pg_jpeg_item per image (`items`), the ragged resize's plan for the same
+    sizes (`prep`, a RaggedPlan: same integers as `ragged_plan`) and the sizes of the coefficient buffer and the plane workspace."""
+
+    def __init__(self, infos, items, prep: "RaggedPlan", coef_bytes: int, workspace_bytes: int):
+        self.infos, self.items, self.prep = infos, items, prep
+        self.n = len(items)
+        self.coef_bytes, self.workspace_bytes = int(coef_bytes), int(workspace_bytes)
+        self.header_bytes = self.n * _lib.JPEG_ITEM_BYTES
+
+    def header(self):
+        import numpy as np
+        return np.frombuffer(self.items, dtype=np.uint8, count=self.header_bytes) if self.n else np.zeros(0, dtype=np.uint8)
+
+
+def jpeg_plan(infos) -> JpegPlan:
+    """pg_jpeg_plan.  `infos`: a list of _lib.JpegInfo; one with reason != 0 is an image the caller supplies the pixels of (its height
+    and width must be set).  Host only."""
+    n = len(infos)
+    arr = (_lib.JpegInfo * n)(*infos)
+    items, prep_items = (_lib.JpegItem * n)(), (_lib.PrepItem * n)()
+    coef, ws, packed, prep_ws = C.c_size_t(), C.c_size_t(), C.c_size_t(), C.c_size_t()
+    check(load().pg_jpeg_plan(n, arr, items, prep_items, C.byref(coef), C.byref(ws), C.byref(packed), C.byref(prep_ws)), "pg_jpeg_plan")
+    prep = RaggedPlan([(int(i.height), int(i.width)) for i in infos], prep_items, packed.value, prep_ws.value)
+    return JpegPlan(list(infos), items, prep, coef.value, ws.value)
+
+
+def jpeg_entropy_decode(files, plan: JpegPlan, coef: torch.Tensor, threads: Optional[int] = None) -> None:
+    """pg_jpeg_entropy_decode: the files' coefficients (and the descriptors, in the head) into the HOST uint8 tensor `coef` of
+    plan.coef_bytes bytes; fills the plan's items with the quantisation tables.  ctypes releases the GIL for the call.  Raises
+    JpegEntropyError (a ValueError) carrying the index of the first damaged file.  Host only."""
+    if not torch.is_tensor(coef) or coef.is_cuda or coef.dtype != torch.uint8 or coef.dim() != 1 or not coef.is_contiguous() \
+            or coef.numel() != plan.coef_bytes:
+        raise _lib.PigeonHipError(f"coefficient buffer must be a contiguous 1-D uint8 host tensor of {plan.coef_bytes} bytes")
+    if len(files) != plan.n:
+        raise _lib.PigeonHipError(f"{len(files)} files for a plan of {plan.n} images")
+    if plan.n == 0:
+        return
+    keep = [bytes(f) if plan.items[i].ncomp else b"" for i, f in enumerate(files)]
+    ptrs = (C.c_void_p * plan.n)(*[C.cast(C.c_char_p(b), C.c_void_p) for b in keep])
+    sizes = (C.c_size_t * plan.n)(*[len(b) for b in keep])
+    bad = C.c_int(-1)
+    rc = load().pg_jpeg_entropy_decode(plan.n, ptrs, sizes, plan.items, C.c_void_p(coef.data_ptr()), plan.coef_bytes,
+                                       int(default_jpeg_threads() if threads is None else threads), C.byref(bad))
+    if rc != 0 and bad.value >= 0:
+        raise JpegEntropyError(bad.value, load().pg_last_error().decode())
+    check(rc, "pg_jpeg_entropy_decode")
+
+
+def jpeg_forward(coef_dev: torch.Tensor, plan: JpegPlan, packed_dev: torch.Tensor, workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """pg_jpeg_forward: coefficients on the device -> RGB at every decoded image's place in `packed_dev` (1-D uint8 of
+    plan.prep.packed_bytes bytes) and the resize's descriptors in its head.  The head of `coef_dev` is (re)written from the plan's
+    items, which are what the call checks.  Returns packed_dev."""
+    _dev(coef_dev, torch.uint8)
+    _dev(packed_dev, torch.uint8)
+    if coef_dev.dim() != 1 or coef_dev.numel() != plan.coef_bytes:
+        raise _lib.PigeonHipError(f"coefficient buffer must be 1-D uint8 of {plan.coef_bytes} bytes, got {tuple(coef_dev.shape)}")
+    if packed_dev.dim() != 1 or packed_dev.numel() != plan.prep.packed_bytes:
+        raise _lib.PigeonHipError(f"packed buffer must be 1-D uint8 of {plan.prep.packed_bytes} bytes, got {tuple(packed_dev.shape)}")
+    if packed_dev.device != coef_dev.device:
+        raise _lib.PigeonHipError("coefficient and packed buffers are on different devices")
+    if plan.n == 0:
+        return packed_dev
+    with torch.cuda.device(coef_dev.device):
+        if workspace is None:
+            workspace = torch.empty(max(plan.workspace_bytes, 16), dtype=torch.uint8, device=coef_dev.device)
+        _dev(workspace, torch.uint8)
+        coef_dev[:plan.header_bytes].copy_(torch.from_numpy(plan.header().copy()))
+        check(load().pg_jpeg_forward(_p(coef_dev), plan.coef_bytes, plan.items, plan.prep.items, plan.n, _p(packed_dev),
+                                     plan.prep.packed_bytes, _p(workspace), workspace.numel(), _stream()), "pg_jpeg_forward")
+    return packed_dev
+
+
 # ----------------------------------------------------------------------------------------- ViT encoder handle
 class VitEncoder:
     """Owns a pg_vit handle: 16-bit-packed weights (fp16 or bf16) resident in HBM, forward = ViT-L/14-336 + token mean.

@@ -44,12 +44,24 @@ def decode_data_uri(uri: str):
     return img.convert("RGB")
 
 
-def panorama_from_request(body: Dict) -> List:
+def data_uri_bytes(uri: str) -> bytes:
+    """'data:image/jpeg;base64,....' (or bare base64) -> the file's bytes, undecoded."""
+    if not isinstance(uri, str) or not uri:
+        raise BadRequest("image field must be a non-empty data URI string")
+    payload = uri.split(",", 1)[1] if uri.startswith("data:") else uri
+    try:
+        return base64.b64decode(payload, validate=False)
+    except Exception as e:
+        raise BadRequest(f"cannot decode image: {e}") from e
+
+
+def panorama_from_request(body: Dict, encoded: bool = False) -> List:
     """The four views of one location.  A single-image request (`classic.js` sends only `image`) is answered from that
-    view repeated four times: the panorama head averages the four panel embeddings (super_guessr.py:437)."""
+    view repeated four times: the panorama head averages the four panel embeddings (super_guessr.py:437).
+    encoded=True: the views stay the payloads' bytes, for `predict_panorama` to decode on the GPU."""
     if not isinstance(body, dict) or IMAGE_KEYS[0] not in body:
         raise BadRequest("JSON body with an 'image' field expected")
-    views = [decode_data_uri(body[k]) for k in IMAGE_KEYS if body.get(k)]
+    views = [(data_uri_bytes if encoded else decode_data_uri)(body[k]) for k in IMAGE_KEYS if body.get(k)]
     if len(views) == 1:
         views = views * 4
     if len(views) != 4:
@@ -59,12 +71,26 @@ def panorama_from_request(body: Dict) -> List:
 
 def predict_panorama(views: Sequence, model, refiner=None, preprocess: Optional[Callable] = None) -> Dict:
     """views: four PIL images -> {'lat', 'lng'} (+ 'geocell_margin', 'geocell_certain', 'reencoded_exact' when the model exposes the
-    certainty of its top-1).  `preprocess(list of PIL) -> (4,3,336,336)` defaults to the GPU path."""
+    certainty of its top-1).  `preprocess(list of PIL) -> (4,3,336,336)` defaults to the GPU path.  Views that are all `bytes` (image
+    files) go to the same path undecoded: baseline JPEGs are decoded on the GPU (pigeon_amd/jpeg.py: Pillow's pixels, bit for bit),
+    anything else by Pillow; a payload neither can read is a BadRequest.  With an injected `preprocess` bytes are decoded first."""
     import torch
+    views = list(views)
+    as_bytes = bool(views) and all(isinstance(v, (bytes, bytearray)) for v in views)
+    if as_bytes and preprocess is not None:
+        views = [decode_data_uri(base64.b64encode(bytes(v)).decode()) for v in views]
     if preprocess is None:
         from .clip_embedder import gpu_preprocess
         preprocess = gpu_preprocess
-    px = preprocess(list(views))                                   # (4,3,336,336), CLIP-normalised
+        if as_bytes:
+            from .jpeg import EncodedImages
+            views = EncodedImages(views)
+    try:
+        px = preprocess(views)                                     # (4,3,336,336), CLIP-normalised
+    except (ValueError, OSError) as e:
+        if not as_bytes:
+            raise
+        raise BadRequest(f"cannot decode image: {e}") from e       # a damaged scan / a file Pillow cannot identify or read
     px = px.reshape(1, 12, px.shape[-2], px.shape[-1])             # one panorama, panels along the channel axis (:386-393)
     with torch.no_grad():
         if hasattr(model, "encode_head"):
@@ -91,8 +117,9 @@ def predict_panorama(views: Sequence, model, refiner=None, preprocess: Optional[
     return res
 
 
-def make_app(model, refiner=None, preprocess: Optional[Callable] = None, game_log: Optional[List] = None):
-    """Starlette application with the two routes the extension calls."""
+def make_app(model, refiner=None, preprocess: Optional[Callable] = None, game_log: Optional[List] = None, encoded: bool = False):
+    """Starlette application with the two routes the extension calls.  encoded=True: the payloads are handed on as bytes and decoded
+    on the GPU (see predict_panorama); the response is the same."""
     from starlette.applications import Starlette
     from starlette.responses import JSONResponse
     from starlette.routing import Route
@@ -100,12 +127,15 @@ def make_app(model, refiner=None, preprocess: Optional[Callable] = None, game_lo
     async def predict(request):
         try:
             body = await request.json()
-            views = panorama_from_request(body)
+            views = panorama_from_request(body, encoded)
         except (BadRequest, json.JSONDecodeError) as e:
             return JSONResponse({"error": str(e)}, status_code=400)
         # called inline on the event loop, on purpose: the handles behind `model` are one per (device, stream) and not
         # thread-safe, so requests are answered one at a time -- a `def` handler would run in Starlette's pool
-        res = predict_panorama(views, model, refiner, preprocess)
+        try:
+            res = predict_panorama(views, model, refiner, preprocess)
+        except BadRequest as e:                                    # (encoded mode: the payloads are only decoded in there)
+            return JSONResponse({"error": str(e)}, status_code=400)
         return JSONResponse({"gameID": body.get("gameID"), "roundID": body.get("roundID"), "results": res})
 
     async def game(request):                                       # duel.js:86-97: fire-and-forget round log
@@ -150,7 +180,7 @@ def main(argv=None):
               f"{model.certainty.describe()}")
     refiner = ProtoRefiner(proto_path=args.protos, dataset_path=args.dataset) if args.protos else None
     torch.cuda.synchronize()
-    uvicorn.run(make_app(model, refiner), host=args.host, port=args.port)
+    uvicorn.run(make_app(model, refiner, encoded=args.encoded), host=args.host, port=args.port)
 
 
 def _arg_parser():
@@ -164,6 +194,9 @@ def _arg_parser():
     ap.add_argument("--no-exact-top1", dest="exact_top1", action="store_false",
                     help="switch the exact mode off (default on: panoramas whose discrete outputs are inside the 16-bit path's error band "
                          "are re-encoded in the encoder's exact mode, so that the answer is the reference's fp32 one)")
+    ap.add_argument("--encoded", action="store_true", default=False,
+                    help="hand the requests' payloads on as bytes: baseline JPEGs are decoded on the GPU into the buffer the resize reads "
+                         "(the same pixels as Pillow's), anything else by Pillow as before")
     ap.add_argument("--host", default="127.0.0.1")
     ap.add_argument("--port", type=int, default=5000)
     ap.add_argument("--calibration", default=None, metavar="FILE",

@@ -60,6 +60,10 @@ argp.add_argument('--raw-images', dest='raw_images', action='store_true', defaul
                        "evaluate: items hold raw `image` (or `image`, `image_2`, `image_3`, `image_4`) columns of any sizes "
                        "(the reference's EvalDataset); they are packed by the workers, resized on the GPU to 8-bit pixels and "
                        "evaluated from those bytes (pigeon_amd.evaluate.ImageEvalDataset)")
+argp.add_argument('--encoded', action='store_true', default=False,
+                  help="with --raw-images: the items' image columns hold FILES (bytes, paths, or a datasets.Image(decode=False) column); the "
+                       "workers only read them, baseline JPEGs are decoded on the GPU into the buffer the resize reads (Pillow's pixels, "
+                       "bit for bit), anything else by Pillow in the main process; the count of those and why is printed once")
 argp.add_argument('--calibration', default=None, metavar='FILE',
                   help="encoder calibration file (bias vector, certainty tolerance, exact-encoder verdict; keyed by the weight "
                        "fingerprint).  If FILE exists it is loaded before the first batch -- every rank loads the same one, nothing is "
@@ -111,8 +115,9 @@ class _SyntheticRawPanoramas(_SyntheticImages):
     """N seeded four-view items of raw uint8 images of mixed sizes, as a dataset with `image` ... `image_4` columns holds them."""
     SIZES = ((336, 336), (400, 640), (512, 384), (337, 500))
 
-    def __init__(self, n):
+    def __init__(self, n, encoded=False):
         super().__init__(n, panorama=True)
+        self.encoded = encoded
 
     def __getitem__(self, i):
         if isinstance(i, str):
@@ -122,7 +127,26 @@ class _SyntheticRawPanoramas(_SyntheticImages):
         for v, key in enumerate(('image', 'image_2', 'image_3', 'image_4')):
             h, w = self.SIZES[(i + v) % len(self.SIZES)]
             item[key] = torch.randint(0, 256, (h, w, 3), generator=g, dtype=torch.uint8).numpy()
+            if self.encoded:
+                item[key] = _jpeg_file(item[key], i + v)
         return item
+
+
+def _jpeg_file(arr, k):
+    """A synthetic image as the dict a datasets.Image(decode=False) column yields: a JPEG file of one of the three samplings."""
+    import io
+    from PIL import Image
+    buf = io.BytesIO()
+    Image.fromarray(arr).resize((arr.shape[1] // 8 + 1, arr.shape[0] // 8 + 1)).resize((arr.shape[1], arr.shape[0]), Image.BICUBIC).save(
+        buf, 'JPEG', quality=90, subsampling=k % 3)
+    return {'bytes': buf.getvalue(), 'path': None}
+
+
+class _SyntheticEncodedImages(_SyntheticRawPanoramas):
+    """N seeded single JPEG files of mixed sizes with an index: `embed --raw-images --encoded --synthetic N`."""
+
+    def __getitem__(self, i):
+        return {'image': super().__getitem__(i)['image'], 'index': i}
 
 
 def _vision_model(args):
@@ -159,7 +183,15 @@ def main():
     return res
 
 
+def _print_fallbacks(comm):
+    from pigeon_amd import jpeg
+    if comm.is_main_process and jpeg.fallback_summary():
+        print(jpeg.fallback_summary())
+
+
 def _dispatch(args, comm):
+    if args.encoded and not args.raw_images:
+        raise SystemExit('--encoded is a mode of --raw-images')
     from pigeon_amd import synthetic
     dev = f'cuda:{int(os.environ.get("LOCAL_RANK", "0"))}'
     torch.cuda.set_device(dev)
@@ -175,12 +207,14 @@ def _dispatch(args, comm):
         if have_cal and comm.is_main_process:
             print(f'Loaded calibration {args.calibration} (fingerprint {embedder.calibration_header["fingerprint"]})')
         if args.synthetic:
-            dataset = {'train': _SyntheticImages(args.synthetic, panorama=False)}
+            dataset = {'train': _SyntheticEncodedImages(args.synthetic, encoded=True) if args.raw_images and args.encoded
+                       else _SyntheticImages(args.synthetic, panorama=False)}
         else:
             from datasets import DatasetDict
             dataset = DatasetDict.load_from_disk(args.load[0])
         embed_images(embedder, dataset, comm, out_dir=args.out_dir, num_workers=0 if args.synthetic else 8,
-                     raw_images=args.raw_images, exact=args.exact)
+                     raw_images=args.raw_images, exact=args.exact, encoded=args.encoded)
+        _print_fallbacks(comm)
         if args.calibration and not have_cal and comm.is_main_process:
             if embedder.guard_stats is not None:
                 embedder.save_calibration(args.calibration, source=f'run.py embed, first batch, {embedder.guard_stats["images"]} images')
@@ -201,7 +235,7 @@ def _dispatch(args, comm):
             geocell_path = os.path.join(tmp, 'geocells.csv')
             synthetic.write_geocell_csv(geocell_path, synthetic.make_geocells(args.geocells, seed=0))
             bank = synthetic.make_bank(args.geocells, 20, seed=2, exact_means=False)
-            dataset = _SyntheticRawPanoramas(args.synthetic) if args.raw_images else _SyntheticImages(args.synthetic, panorama=True)
+            dataset = _SyntheticRawPanoramas(args.synthetic, args.encoded) if args.raw_images else _SyntheticImages(args.synthetic, panorama=True)
         else:
             from datasets import DatasetDict
             dataset = DatasetDict.load_from_disk(args.load[0])
@@ -209,11 +243,12 @@ def _dispatch(args, comm):
                 dataset = dataset['test'] if args.test else dataset['val']
         if args.raw_images:
             from pigeon_amd.evaluate import ImageEvalDataset
-            dataset = ImageEvalDataset(dataset)
+            dataset = ImageEvalDataset(dataset, encoded=args.encoded)
         results = evaluate(args.name, dataset, yfcc=args.yfcc, base_model=_vision_model(args), refine=True,
                            landmarks=args.landmarks, geocell_path=geocell_path, bank=bank, heading=args.heading,
                            multi_task=args.multitask, calibration=args.calibration, embedding_rel_tol=args.embedding_rel_tol,
                            country_path=args.countries, bank_rel_tol=args.bank_rel_tol)
+        _print_fallbacks(comm)
         if comm.is_main_process:
             print({k: (v if not hasattr(v, 'shape') or v.shape == () else tuple(v.shape)) for k, v in results.items() if k != 'exact_passes'})
             if 'geocell_certain' in results:
