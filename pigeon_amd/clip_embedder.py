@@ -8,19 +8,18 @@ runs entirely inside libpigeon_hip.so.
 from __future__ import annotations
 
 import os
-import threading
 from types import SimpleNamespace
 from typing import Callable, Dict, Optional
 
-import numpy as np
 import torch
 from torch import Tensor
 
 from . import hip_ops, synthetic
 from .certainty import SAFETY, CalibrationError, Certainty, combine_ranks, outside_contract, require_fingerprint
-from .config import CLIP_MODEL, OPENAI_CLIP_MEAN, OPENAI_CLIP_STD
+from .config import CLIP_MODEL
 from .jpeg import EncodedImages, decode_chunks, decode_images  # noqa: F401  (re-exported)
 from .packing import PackedImages, as_rgb_array, check_rgb_u8, chunk_by_bytes, pack_images, pack_into, packed_layout  # noqa: F401  (re-exported)
+from .preprocess import clip_preprocess, gpu_preprocess  # noqa: F401  (re-exported; CLIPEmbedding calls this module's `gpu_preprocess`)
 from .utils import load_state_dict
 
 
@@ -164,10 +163,15 @@ def load_pretrained_clip(name: Optional[str] = None) -> HipCLIPVisionModel:
     return m
 
 
+def _on_cuda(t: Tensor, device) -> Tensor:
+    """A host tensor goes to `device` if that is a cuda torch.device, else to the current one; a device tensor stays where it is."""
+    if t.is_cuda:
+        return t
+    return t.to(device if (isinstance(device, torch.device) and device.type == "cuda") else torch.device("cuda"))
+
+
 def _to_device_pixels(pixel_values: Tensor, device) -> Tensor:
-    if not pixel_values.is_cuda:
-        dev = device if (isinstance(device, torch.device) and device.type == "cuda") else torch.device("cuda")
-        pixel_values = pixel_values.to(dev)
+    pixel_values = _on_cuda(pixel_values, device)
     if pixel_values.dtype not in (torch.float32, torch.float16, torch.bfloat16):
         pixel_values = pixel_values.float()
     return pixel_values.contiguous()
@@ -199,239 +203,7 @@ def exclusive_pixel_bytes(pixel_bytes, **others) -> None:
 def pixel_bytes_to_device(pixel_bytes: Tensor, device) -> Tensor:
     """Checked `pixel_bytes` -> (B*4 or B, 3,336,336) uint8 on the device (a host tensor is copied as bytes)."""
     check_pixel_bytes(pixel_bytes)
-    if not pixel_bytes.is_cuda:
-        dev = device if (isinstance(device, torch.device) and device.type == "cuda") else torch.device("cuda")
-        pixel_bytes = pixel_bytes.to(dev)
-    return pixel_bytes.view((-1, 3, 336, 336))
-
-
-def _resize_output_size(h: int, w: int, size: int = 336):
-    """transformers 4.23.1 (reference env.yml:60) ImageFeatureExtractionMixin.resize with an int size and
-    default_to_square=False: the shorter edge becomes `size`, the longer one int(size * long / short)."""
-    short, long = (w, h) if w <= h else (h, w)
-    if short == size:
-        return h, w
-    new_short, new_long = size, int(size * long / short)
-    return (new_long, new_short) if w <= h else (new_short, new_long)
-
-
-def clip_preprocess(images) -> Tensor:
-    """CLIPProcessor restated for PIL inputs on the HOST (what `self.processor(images=...)` does at reference
-    models/clip_embedder.py:52; this is DataLoader-worker work in the reference too): convert RGB, resize shorter edge
-    to 336 (PIL BICUBIC), centre crop 336x336, float32 / 255.0, (x - mean) / std -> (N,3,336,336) fp32.
-    `gpu_preprocess` below is the device path and produces bit-identical values."""
-    from PIL import Image
-    if not isinstance(images, (list, tuple)):
-        images = [images]
-    out = []
-    mean = np.asarray(OPENAI_CLIP_MEAN).astype(np.float32)
-    std = np.asarray(OPENAI_CLIP_STD).astype(np.float32)
-    for im in images:
-        im = im.convert("RGB")
-        w, h = im.size
-        nh, nw = _resize_output_size(h, w)
-        if (nh, nw) != (h, w):
-            im = im.resize((nw, nh), resample=Image.BICUBIC)
-        left, top = (nw - 336) // 2, (nh - 336) // 2
-        im = im.crop((left, top, left + 336, top + 336))
-        a = np.asarray(im).astype(np.float32) / 255.0
-        out.append(((a - mean) / std).transpose(2, 0, 1))
-    return torch.from_numpy(np.ascontiguousarray(np.stack(out)))
-
-
-# pg_prep handles by (in_h, in_w, device): each owns the resize coefficient tables of one input geometry.  Street-view panels come
-# in a handful of sizes, photo collections (YFCC) in thousands: least-recently-used handles beyond the cap are destroyed.
-_PREPROCESSORS: "OrderedDict" = None
-_PREPROCESSORS_MAX = 64
-
-
-def _preprocessor(in_h: int, in_w: int, device_index: int) -> "hip_ops.Preprocessor":
-    global _PREPROCESSORS
-    from collections import OrderedDict
-    if _PREPROCESSORS is None:
-        _PREPROCESSORS = OrderedDict()
-    key = (int(in_h), int(in_w), int(device_index))
-    p = _PREPROCESSORS.pop(key, None)
-    if p is None:
-        p = hip_ops.Preprocessor(key[0], key[1], device=key[2])
-    _PREPROCESSORS[key] = p                                        # most recently used last
-    while len(_PREPROCESSORS) > _PREPROCESSORS_MAX:
-        old_key, old = _PREPROCESSORS.popitem(last=False)
-        torch.cuda.synchronize(old_key[2])                         # ITS device: its tables may still be read by a queued kernel
-        old.close()
-    return p
-
-
-# Pinned host staging buffers of gpu_preprocess's PIL / ndarray-list path, one per (count, image shape, device): [tensor, event of the
-# last host-to-device copy that read it].  A buffer is rewritten only after that copy has run (the event is long past in practice).
-_STAGING: Dict = {}
-_STAGING_MAX = 8
-
-
-def _staging(n: int, shape, dev) -> Tensor:
-    key = (int(n), tuple(int(v) for v in shape), int(dev.index))
-    ent = _STAGING.get(key)
-    if ent is None:
-        if len(_STAGING) >= _STAGING_MAX:
-            _STAGING.pop(next(iter(_STAGING)))
-        ent = _STAGING[key] = [torch.empty((key[0],) + key[1], dtype=torch.uint8).pin_memory(), None]
-    elif ent[1] is not None:
-        ent[1].synchronize()
-    return ent[0]
-
-
-def _staging_done(t: Tensor) -> None:
-    for ent in _STAGING.values():
-        if ent[0] is t:
-            ent[1] = torch.cuda.Event()
-            ent[1].record()
-            return
-
-
-# The ragged path (pg_prep_ragged_forward): one RaggedPreprocessor per device -- it owns the normalisation table and a workspace,
-# nothing per geometry -- and ONE pinned staging buffer per device, grown when a batch needs more: [tensor, event of the last copy].
-_RAGGED: Dict = {}
-_RAGGED_STAGING: Dict = {}
-# Lists of more than one shape take the ragged path: 512 images in 128 sizes measured 17.7 ms against 45.0 ms grouped by size
-# (tools/prep_ragged_ab.py, profiles/r07/prep_ragged_ab.txt, DESIGN.md section 4); PIGEON_PREP_RAGGED=0 keeps them on the grouped path.
-RAGGED_LISTS = os.environ.get("PIGEON_PREP_RAGGED", "1") not in ("", "0")
-RAGGED_MAX_BYTES = 256 << 20                                       # packed bytes per ragged call of the list path
-# gpu_preprocess fills shared pinned staging buffers (_STAGING, _RAGGED_STAGING) before it queues their copies: one caller at a time
-_PREP_LOCK = threading.RLock()
-
-
-def _ragged_preprocessor(device_index: int) -> "hip_ops.RaggedPreprocessor":
-    p = _RAGGED.get(int(device_index))
-    if p is None:
-        p = _RAGGED[int(device_index)] = hip_ops.RaggedPreprocessor(int(device_index))
-    return p
-
-
-def _ragged_staging(nbytes: int, dev) -> Tensor:
-    ent = _RAGGED_STAGING.get(int(dev.index))
-    if ent is None or ent[0].numel() < nbytes:
-        grown = nbytes if ent is None else max(nbytes, ent[0].numel() * 3 // 2)
-        ent = _RAGGED_STAGING[int(dev.index)] = [torch.empty(grown, dtype=torch.uint8).pin_memory(), None]
-    elif ent[1] is not None:
-        ent[1].synchronize()                                       # rewritten only after the last copy out of it has run
-    return ent[0][:nbytes]
-
-
-def _ragged_forward(host: Tensor, plan, dev, out_dtype, staged: bool) -> Tensor:
-    """`host`: plan.packed_bytes bytes with the pixels in place.  The descriptors go into its head, one copy, one forward."""
-    host.numpy()[:plan.header_bytes] = plan.header()
-    with torch.cuda.device(dev):
-        on_dev = host.to(dev, non_blocking=True)
-        if staged:
-            ent = _RAGGED_STAGING[int(dev.index)]
-            ent[1] = torch.cuda.Event()
-            ent[1].record()
-        return _ragged_preprocessor(dev.index).forward(on_dev, plan, out_dtype, header_written=True)
-
-
-def _gpu_preprocess_packed(packed: PackedImages, dev, out_dtype) -> Tensor:
-    data = packed.data
-    if not torch.is_tensor(data) or data.dtype != torch.uint8 or data.dim() != 1 or data.is_cuda or not data.is_contiguous():
-        raise ValueError("gpu_preprocess: PackedImages.data must be a contiguous 1-D uint8 host tensor")
-    plan = hip_ops.ragged_plan(packed.size_list())
-    if data.numel() != plan.packed_bytes:
-        raise ValueError(f"gpu_preprocess: PackedImages holds {data.numel()} bytes, its {plan.n} sizes need {plan.packed_bytes}")
-    if plan.n == 0:
-        return torch.empty((0, 3, 336, 336), dtype=out_dtype, device=dev)
-    if data.is_pinned():
-        out = _ragged_forward(data, plan, dev, out_dtype, staged=False)        # its head was left blank for exactly this
-        with torch.cuda.device(dev):
-            packed.copy_event = torch.cuda.Event()                 # the caller may rewrite the pinned buffer once this has passed
-            packed.copy_event.record()
-        return out
-    stage = _ragged_staging(plan.packed_bytes, dev)
-    stage.copy_(data)
-    return _ragged_forward(stage, plan, dev, out_dtype, staged=True)
-
-
-def _gpu_preprocess_encoded(encoded: EncodedImages, dev, out_dtype) -> Tensor:
-    """Files as bytes: decoded on the GPU into the packed buffer (pigeon_amd/jpeg.py), resized from there -- no host round trip."""
-    outs = []
-    for dec in decode_chunks(encoded, dev, RAGGED_MAX_BYTES):
-        with torch.cuda.device(dev):
-            outs.append(_ragged_preprocessor(dev.index).forward(dec.packed, dec.plan, out_dtype, header_written=True))
-    return outs[0] if len(outs) == 1 else torch.cat(outs, dim=0)
-
-
-def gpu_preprocess(images, device="cuda", out_dtype: torch.dtype = torch.float32) -> Tensor:
-    """See `_gpu_preprocess`.  Callers from several threads are served one after the other: the pinned staging buffers are shared."""
-    with _PREP_LOCK:
-        return _gpu_preprocess(images, device, out_dtype)
-
-
-def _gpu_preprocess(images, device="cuda", out_dtype: torch.dtype = torch.float32) -> Tensor:
-    """CLIP preprocessing on the GPU: `images` is a uint8 RGB tensor / ndarray (N,H,W,3) or (H,W,3), a list of PIL images / arrays,
-    a `PackedImages`, or an `EncodedImages` (files as bytes: decoded on the GPU, Pillow's pixels bit for bit, then resized in place).  Tensors and lists of ONE shape run pg_prep_forward (a handle per geometry); a `PackedImages` and a list of
-    several shapes run pg_prep_ragged_forward: one packed staging buffer and, per chunk of at most RAGGED_MAX_BYTES (256 MiB) of packed
-    bytes, one copy and three launches whatever the sizes.  A PINNED `PackedImages` is copied from in place: its head is overwritten
-    with the descriptors and the buffer belongs to the call until `copy_event` (set on the object) has passed.  Returns the
-    (N,3,336,336) pixel_values on `device`, bit-identical to `clip_preprocess` / the reference's CLIPProcessor.
-    `out_dtype`: torch.float32, torch.float16 (the fp32 value rounded) or torch.uint8 -- the resized, cropped byte itself, planar, in
-    front of the normalisation table: what the `pixel_bytes` arguments of the encoder and the model take (a quarter of the fp32 size)."""
-    dev = torch.device(device)
-    if dev.index is None:
-        dev = torch.device("cuda", torch.cuda.current_device())
-    if isinstance(images, PackedImages):
-        return _gpu_preprocess_packed(images, dev, out_dtype)
-    if isinstance(images, EncodedImages):
-        return _gpu_preprocess_encoded(images, dev, out_dtype)
-    if hasattr(images, "convert"):                                 # one PIL image, as `processor(images=img)` accepts it
-        images = [images]
-    if torch.is_tensor(images) or isinstance(images, np.ndarray):
-        t = torch.as_tensor(images)
-        if t.dim() == 3:
-            t = t[None]
-        groups = [(None, t)]
-    else:
-        # (a PIL image that is RGB already is not copied by `convert`: a serving request's four views are; round 6)
-        arrs = [as_rgb_array(im) for im in images]
-        by_size: Dict = {}
-        for i, a in enumerate(arrs):
-            by_size.setdefault(a.shape, []).append(i)
-        if RAGGED_LISTS and len(by_size) > 1:
-            for a in arrs:
-                check_rgb_u8(a)
-            # (a list beyond the byte budget or the 65535 images of one call goes in consecutive chunks: the staging buffer and the
-            # workspace stay bounded, and no list the grouped path took is refused)
-            outs = []
-            for lo, hi in chunk_by_bytes([a.shape[:2] for a in arrs], RAGGED_MAX_BYTES):
-                plan = hip_ops.ragged_plan([a.shape[:2] for a in arrs[lo:hi]])
-                stage = _ragged_staging(plan.packed_bytes, dev)    # the images go straight to their places in the pinned buffer
-                pack_into(arrs[lo:hi], [int(it.src_off) for it in plan.items], stage.numpy())
-                outs.append(_ragged_forward(stage, plan, dev, out_dtype, staged=True))
-            return outs[0] if len(outs) == 1 else torch.cat(outs, dim=0)
-        groups = []
-        for idx in by_size.values():
-            a0 = arrs[idx[0]]
-            if a0.dtype != np.uint8 or a0.ndim != 3:
-                groups.append((idx, torch.from_numpy(np.stack([arrs[i] for i in idx]))))       # refused below with the usual message
-                continue
-            # the images of one size go straight into a PINNED staging buffer (one copy instead of np.stack + the driver's own staging
-            # of a pageable source), from which the transfer below is asynchronous
-            stage = _staging(len(idx), a0.shape, dev)
-            view = stage.numpy()
-            for j, i in enumerate(idx):
-                view[j] = arrs[i]
-            groups.append((idx, stage))
-    n_total = sum(g[1].shape[0] for g in groups)
-    out = torch.empty((n_total, 3, 336, 336), dtype=out_dtype, device=dev)
-    for idx, t in groups:
-        if t.dtype != torch.uint8 or t.shape[-1] != 3:
-            raise ValueError(f"gpu_preprocess expects uint8 RGB (N,H,W,3), got {t.dtype} {tuple(t.shape)}")
-        with torch.cuda.device(dev):
-            on_dev = t.to(dev, non_blocking=True).contiguous()
-            _staging_done(t)                                       # (a pinned staging buffer is reused only after this copy has run)
-            px = _preprocessor(t.shape[1], t.shape[2], dev.index)(on_dev, out_dtype)
-        if idx is None:
-            out = px
-        else:
-            out[torch.as_tensor(idx, device=dev)] = px
-    return out
+    return _on_cuda(pixel_bytes, device).view((-1, 3, 336, 336))
 
 
 class CLIPEmbedding(torch.nn.Module):

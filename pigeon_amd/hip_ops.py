@@ -46,6 +46,12 @@ def _dev(t: torch.Tensor, dtype=None) -> torch.Tensor:
     return t
 
 
+def indexed_device(device) -> torch.device:
+    """`device` ("cuda", "cuda:1", a torch.device) as a torch.device with its index filled in."""
+    dev = torch.device(device)
+    return dev if dev.index is not None else torch.device("cuda", torch.cuda.current_device())
+
+
 def _shape(t: torch.Tensor, name: str, *dims):
     """The C ABI takes pointers plus a few sizes; every other extent is implied.  Refuse a tensor whose shape is not the implied
     one (None = any extent) instead of letting a kernel read past its end."""
@@ -419,9 +425,38 @@ def bytes_to_pixels(pixel_bytes: torch.Tensor) -> torch.Tensor:
     return lut.view(-1)[idx]
 
 
-class Preprocessor:
+class _Handle:
+    """Owner of one library handle `_h`: `close` (and collection) destroys it, once, through the library function `_destroy` names."""
+    _destroy = ""
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h.value:
+            getattr(load(), self._destroy)(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _prep_out_dtype(out_dtype: torch.dtype) -> int:
+    if out_dtype not in _PREP_OUT:
+        raise _lib.PigeonHipError("preprocess output dtype must be float32 or float16 (or uint8: the resized bytes)")
+    return _PREP_OUT[out_dtype]
+
+
+def _items_header(items, nbytes: int):
+    """A plan's ctypes descriptor array as the uint8 array the head of its buffer must hold."""
+    import numpy as np
+    return np.frombuffer(items, dtype=np.uint8, count=nbytes) if nbytes else np.zeros(0, dtype=np.uint8)
+
+
+class Preprocessor(_Handle):
     """CLIP preprocessing on the GPU for one input geometry: (N,H,W,3) uint8 RGB -> (N,3,336,336) pixel_values,
     bit-exact with `CLIPProcessor(images=pil)` (Pillow fixed-point bicubic + numpy float32 normalisation)."""
+    _destroy = "pg_prep_destroy"
 
     def __init__(self, in_h: int, in_w: int, device: int = 0):
         _lib.require_gpu()
@@ -437,30 +472,17 @@ class Preprocessor:
         _dev(images_u8, torch.uint8)
         if images_u8.dim() != 4 or tuple(images_u8.shape[1:]) != (self.in_h, self.in_w, 3):
             raise _lib.PigeonHipError(f"images must be (N,{self.in_h},{self.in_w},3) uint8, got {tuple(images_u8.shape)}")
-        if out_dtype not in _PREP_OUT:
-            raise _lib.PigeonHipError("preprocess output dtype must be float32 or float16 (or uint8: the resized bytes)")
+        dt = _prep_out_dtype(out_dtype)
         n = images_u8.shape[0]
         need = C.c_size_t()
         check(load().pg_prep_workspace_bytes(self._h, n, C.byref(need)), "pg_prep_workspace_bytes")
         if self._ws is None or self._ws.numel() < need.value or self._ws.device != images_u8.device:
             self._ws = torch.empty(need.value, dtype=torch.uint8, device=images_u8.device)
         out = torch.empty((n, 3, 336, 336), dtype=out_dtype, device=images_u8.device)
-        check(load().pg_prep_forward(self._h, _p(images_u8), n, _p(out), _PREP_OUT[out_dtype], _p(self._ws), self._ws.numel(),
-                                     _stream()), "pg_prep_forward")
+        check(load().pg_prep_forward(self._h, _p(images_u8), n, _p(out), dt, _p(self._ws), self._ws.numel(), _stream()), "pg_prep_forward")
         return out
 
     __call__ = forward
-
-    def close(self):
-        if self._h:
-            load().pg_prep_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 class RaggedPlan:
@@ -475,8 +497,7 @@ class RaggedPlan:
         self.header_bytes = self.n * _lib.PREP_ITEM_BYTES
 
     def header(self):
-        import numpy as np
-        return np.frombuffer(self.items, dtype=np.uint8, count=self.header_bytes) if self.n else np.zeros(0, dtype=np.uint8)
+        return _items_header(self.items, self.header_bytes)
 
 
 def ragged_plan(sizes) -> RaggedPlan:
@@ -491,9 +512,10 @@ def ragged_plan(sizes) -> RaggedPlan:
     return RaggedPlan(sizes, items, packed.value, ws.value)
 
 
-class RaggedPreprocessor:
+class RaggedPreprocessor(_Handle):
     """CLIP preprocessing on the GPU for a batch of images of DIFFERENT sizes in one packed buffer (layout: pigeon_hip.h,
     pg_prep_ragged_forward): the same bits per image as `Preprocessor(h, w)` on it alone, in three launches per call."""
+    _destroy = "pg_prep_ragged_destroy"
 
     def __init__(self, device: int = 0):
         _lib.require_gpu()
@@ -514,8 +536,7 @@ class RaggedPreprocessor:
             raise _lib.PigeonHipError(f"packed buffer must be 1-D uint8 of {plan.packed_bytes} bytes, got {tuple(packed_u8.shape)}")
         if packed_u8.device.index != self.device:
             raise _lib.PigeonHipError(f"packed buffer is on {packed_u8.device}, the preprocessor on cuda:{self.device}")
-        if out_dtype not in _PREP_OUT:
-            raise _lib.PigeonHipError("preprocess output dtype must be float32 or float16 (or uint8: the resized bytes)")
+        dt = _prep_out_dtype(out_dtype)
         out = torch.empty((plan.n, 3, 336, 336), dtype=out_dtype, device=packed_u8.device)
         if plan.n == 0:
             return out
@@ -523,22 +544,11 @@ class RaggedPreprocessor:
             self._ws = torch.empty(plan.workspace_bytes, dtype=torch.uint8, device=packed_u8.device)
         if not header_written:
             packed_u8[:plan.header_bytes].copy_(torch.from_numpy(plan.header().copy()))
-        check(load().pg_prep_ragged_forward(self._h, _p(packed_u8), plan.packed_bytes, plan.items, plan.n, _p(out), _PREP_OUT[out_dtype],
+        check(load().pg_prep_ragged_forward(self._h, _p(packed_u8), plan.packed_bytes, plan.items, plan.n, _p(out), dt,
                                             _p(self._ws), self._ws.numel(), _stream()), "pg_prep_ragged_forward")
         return out
 
     __call__ = forward
-
-    def close(self):
-        if self._h:
-            load().pg_prep_ragged_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 # ----------------------------------------------------------------------------------------- JPEG decoding
@@ -586,8 +596,7 @@ class JpegPlan:
         self.header_bytes = self.n * _lib.JPEG_ITEM_BYTES
 
     def header(self):
-        import numpy as np
-        return np.frombuffer(self.items, dtype=np.uint8, count=self.header_bytes) if self.n else np.zeros(0, dtype=np.uint8)
+        return _items_header(self.items, self.header_bytes)
 
 
 def jpeg_plan(infos) -> JpegPlan:
@@ -649,12 +658,13 @@ def jpeg_forward(coef_dev: torch.Tensor, plan: JpegPlan, packed_dev: torch.Tenso
 
 
 # ----------------------------------------------------------------------------------------- ViT encoder handle
-class VitEncoder:
+class VitEncoder(_Handle):
     """Owns a pg_vit handle: 16-bit-packed weights (fp16 or bf16) resident in HBM, forward = ViT-L/14-336 + token mean.
 
     state_dict keys may be in either transformers layout (vision_model.* or flat); values are CPU or device
     tensors of any float dtype (converted to fp32 on the host, then packed by the library).
     """
+    _destroy = "pg_vit_destroy"
 
     def __init__(self, state_dict: Dict[str, torch.Tensor], device: int = 0, max_chunk: int = 0,
                  layers: Optional[int] = None, mma_dtype: Optional[str] = None, precise: bool = False):
@@ -807,17 +817,6 @@ class VitEncoder:
         n = C.c_int64()
         check(load().pg_vit_range_alarm_read(self._h, C.byref(n), 1 if reset else 0), "pg_vit_range_alarm_read")
         return int(n.value)
-
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h.value:
-            load().pg_vit_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 # ----------------------------------------------------------------------------------------- head

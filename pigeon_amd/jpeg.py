@@ -14,6 +14,7 @@ import numpy as np
 import torch
 
 from . import _lib, hip_ops
+from .packing import PinnedStaging, chunk_by_bytes
 
 
 class EncodedImages:
@@ -77,7 +78,7 @@ class DecodedImages:
 # Fallbacks seen by this process, by reason: the CLI prints them once per run
 FALLBACKS: dict = {}
 _LOCK = threading.RLock()
-_STAGING: dict = {}                   # device index -> [pinned uint8 tensor, event of the last copy out of it]
+_STAGING: dict = {}                   # device index -> PinnedStaging of the coefficients, taken and copied from under _LOCK
 
 
 def fallback_summary() -> str:
@@ -86,16 +87,6 @@ def fallback_summary() -> str:
             return ""
         total = sum(FALLBACKS.values())
         return f"{total} image(s) decoded by Pillow on the host: " + ", ".join(f"{k} x{v}" for k, v in sorted(FALLBACKS.items()))
-
-
-def _staging(nbytes: int, dev) -> torch.Tensor:
-    ent = _STAGING.get(int(dev.index))
-    if ent is None or ent[0].numel() < nbytes:
-        grown = nbytes if ent is None else max(nbytes, ent[0].numel() * 3 // 2)
-        ent = _STAGING[int(dev.index)] = [torch.empty(grown, dtype=torch.uint8).pin_memory(), None]
-    elif ent[1] is not None:
-        ent[1].synchronize()                                       # rewritten only after the last copy out of it has run
-    return ent[0][:nbytes]
 
 
 def pillow_rgb(data: bytes) -> np.ndarray:
@@ -125,12 +116,11 @@ def _decode(files, infos, host, dev, threads) -> DecodedImages:
             packed = torch.empty(plan.prep.packed_bytes, dtype=torch.uint8, device=dev)
             if plan.n == 0:
                 return DecodedImages(packed, plan.prep, fallbacks)
-            stage = _staging(plan.coef_bytes, dev)
+            staging = _STAGING.setdefault(int(dev.index), PinnedStaging())
+            stage = staging.take(plan.coef_bytes)
             hip_ops.jpeg_entropy_decode(files, plan, stage, threads)           # raises before anything is queued on the GPU
             coef_dev = stage.to(dev, non_blocking=True)
-            ent = _STAGING[int(dev.index)]
-            ent[1] = torch.cuda.Event()
-            ent[1].record()
+            staging.copied()
             for i, arr in host.items():
                 off = int(plan.items[i].rgb_off)
                 packed[off:off + arr.size].copy_(torch.from_numpy(np.ascontiguousarray(arr)).view(-1))
@@ -141,11 +131,8 @@ def _decode(files, infos, host, dev, threads) -> DecodedImages:
 def decode_chunks(encoded, device="cuda", max_bytes: Optional[int] = None, threads: Optional[int] = None):
     """Generator of DecodedImages over consecutive runs of the files whose packed buffers hold at most `max_bytes` bytes each (None: one
     run).  Indices in errors and in `fallbacks` count from the start of `encoded`."""
-    from .packing import chunk_by_bytes
     files = encoded.files if isinstance(encoded, EncodedImages) else EncodedImages(encoded).files
-    dev = torch.device(device)
-    if dev.index is None:
-        dev = torch.device("cuda", torch.cuda.current_device())
+    dev = hip_ops.indexed_device(device)
     _lib.require_gpu()
     infos, host = probe_all(files)
     sizes = [(i.height, i.width) for i in infos]

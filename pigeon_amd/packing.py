@@ -3,7 +3,7 @@
 Nothing here touches the HIP library or a GPU, so DataLoader workers can pack: `pack_images` lays a list of images of any sizes
 out in ONE uint8 buffer by the rule of pg_prep_ragged_plan (include/pigeon_hip.h) and leaves the head of the buffer -- where the
 descriptors travel -- blank; the process that owns the GPU plans, fills that head in and makes one host-to-device copy
-(pigeon_amd.clip_embedder.gpu_preprocess)."""
+(pigeon_amd.preprocess.gpu_preprocess).  `PinnedStaging` is that process's side of the copy: it reaches torch.cuda only when used."""
 from __future__ import annotations
 
 from typing import List, Sequence, Tuple
@@ -84,6 +84,31 @@ class PackedImages:
 
     def pin_memory(self) -> "PackedImages":                        # (what DataLoader(pin_memory=True) calls on a custom batch)
         return PackedImages(self.data.pin_memory(), self.sizes)
+
+
+class PinnedStaging:
+    """One pinned host buffer that grows with the largest request, and the one rule of reusing it: it is rewritten only after the last
+    host-to-device copy that read it has run.  `take` hands out its first bytes, waiting for that copy if it is still pending; the
+    caller fills them, queues its `non_blocking` copy and calls `copied` on the stream that did the copy.  No lock of its own: the
+    caller's lock spans "fill the buffer ... copy queued"."""
+
+    def __init__(self):
+        self.buf, self.event = None, None
+
+    def take(self, nbytes: int) -> torch.Tensor:
+        """A 1-D uint8 pinned view of exactly `nbytes` bytes."""
+        if self.buf is None or self.buf.numel() < nbytes:
+            grown = nbytes if self.buf is None else max(nbytes, self.buf.numel() * 3 // 2)
+            # (the old buffer is dropped without waiting: torch's pinned allocator keeps it alive under a copy still in flight)
+            self.buf, self.event = torch.empty(grown, dtype=torch.uint8).pin_memory(), None
+        elif self.event is not None:
+            self.event.synchronize()
+        return self.buf[:nbytes]
+
+    def copied(self) -> None:
+        """The copy out of the buffer has just been queued on the current stream of the current device."""
+        self.event = torch.cuda.Event()
+        self.event.record()
 
 
 def pack_into(arrs: Sequence[np.ndarray], offs: Sequence[int], buf: np.ndarray) -> None:

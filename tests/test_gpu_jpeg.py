@@ -225,6 +225,21 @@ def test_mixed_batch_with_host_fallbacks(fx, subset):
     assert "3 image(s)" in fx["jpeg"].fallback_summary() or sum(fx["jpeg"].FALLBACKS.values()) >= 3
 
 
+def test_two_decodes_in_a_row_share_the_coefficient_staging_buffer(fx, subset):
+    """A larger batch, then a smaller one, nothing synchronised in between: the second call's coefficients go into the pinned buffer
+    the first call's copy may still be reading.  Both give Pillow's pixels."""
+    jpeg = fx["jpeg"]
+    first, second = subset, subset[5:1:-1]
+    decs = [jpeg.decode_images([fx["files"][i] for i in order], DEV) for order in (first, second)]
+    torch.cuda.synchronize()
+    for order, dec in zip((first, second), decs):
+        assert len(dec) == len(order)
+        for k, i in enumerate(order):
+            assert np.array_equal(dec.image(k).cpu().numpy(), fx["pixels"][i]), fx["names"][i]
+    staging = jpeg._STAGING[torch.cuda.current_device()]
+    assert type(staging).__name__ == "PinnedStaging" and staging.buf.is_pinned() and staging.event is not None
+
+
 def test_entropy_error_names_the_image_and_launches_nothing(fx, subset, monkeypatch):
     bad = bytearray(fx["files"][subset[0]])
     h = R.parse(bytes(bad))

@@ -200,7 +200,7 @@ def test_refused_before_launch(env):
 
 def test_gpu_preprocess_mixed_list_takes_the_ragged_path(env, monkeypatch):
     Image = pytest.importorskip("PIL.Image")
-    from pigeon_amd import clip_embedder as ce
+    from pigeon_amd import clip_embedder as ce, preprocess as pp
     ops = env["ops"]
     rng = np.random.default_rng(8)
     sizes = [(300, 400), (400, 300), (336, 336), (350, 500), (123, 457), (600, 338)]
@@ -209,7 +209,7 @@ def test_gpu_preprocess_mixed_list_takes_the_ragged_path(env, monkeypatch):
     as_pil = ims[:5] + [rgb[5]]
     want = ce.clip_preprocess(as_pil)
     ce.gpu_preprocess([rgb[0]])                                     # (the per-size cache is alive before the handles are forbidden)
-    cached = list(ce._PREPROCESSORS)
+    cached = list(pp._PREPROCESSORS)
     real = ops.Preprocessor
 
     def forbidden(*a, **k):
@@ -228,7 +228,7 @@ def test_gpu_preprocess_mixed_list_takes_the_ragged_path(env, monkeypatch):
     pinned.copy_event.synchronize()                                 # a pinned buffer is copied from in place: the event says when it is free
     assert pinned.data[:len(ims) * 80].any()
     assert ce.gpu_preprocess(ce.pack_images([])).shape == (0, 3, S, S)
-    assert list(ce._PREPROCESSORS) == cached
+    assert list(pp._PREPROCESSORS) == cached
     with pytest.raises(ValueError, match="uint8 RGB"):
         ce.gpu_preprocess([np.asarray(rgb[0]), np.zeros((5, 5, 3), dtype=np.float32)])
     # a list of one shape stays on pg_prep_forward
@@ -249,16 +249,16 @@ def test_gpu_preprocess_mixed_list_in_chunks_and_from_threads(env, monkeypatch):
     """A mixed list above the byte budget of one ragged call goes in consecutive chunks (same bits, same order), and callers from
     several threads, who share the pinned staging buffer, each get their own images' pixels."""
     import threading
-    from pigeon_amd import clip_embedder as ce
+    from pigeon_amd import clip_embedder as ce, preprocess as pp
     rng = np.random.default_rng(9)
     sizes = [(300, 400), (400, 300), (336, 336), (350, 500), (123, 457), (600, 338), (200, 210)]
     arrs = [rng.integers(0, 256, s + (3,), dtype=np.uint8) for s in sizes]
     want = ce.gpu_preprocess(arrs).cpu()
     assert torch.equal(want, ce.clip_preprocess([__import__("PIL.Image").Image.fromarray(a) for a in arrs]))
     calls = []
-    real = ce._ragged_forward
-    monkeypatch.setattr(ce, "_ragged_forward", lambda host, plan, *a, **k: (calls.append(plan.n), real(host, plan, *a, **k))[1])
-    monkeypatch.setattr(ce, "RAGGED_MAX_BYTES", 800_000)            # 360 + 360 kB fit, + 339 do not; 339 + 525 do not; 525 + 169; 608 + 126
+    real = pp._ragged_forward
+    monkeypatch.setattr(pp, "_ragged_forward", lambda host, plan, *a, **k: (calls.append(plan.n), real(host, plan, *a, **k))[1])
+    monkeypatch.setattr(pp, "RAGGED_MAX_BYTES", 800_000)            # 360 + 360 kB fit, + 339 do not; 339 + 525 do not; 525 + 169; 608 + 126
     assert torch.equal(ce.gpu_preprocess(arrs).cpu(), want)
     assert calls == [2, 1, 2, 2]
     monkeypatch.undo()
@@ -275,6 +275,40 @@ def test_gpu_preprocess_mixed_list_in_chunks_and_from_threads(env, monkeypatch):
         th.join()
     for (t, r), px in got.items():
         assert torch.equal(px, torch.cat([want[t:], want[:t]]).to(torch.float16)), (t, r)
+
+
+def test_one_staging_buffer_serves_every_list_path(env):
+    """The lists of ONE shape share one pinned staging buffer per device, whatever their count and shape; the lists of several shapes
+    have the device's other one (with the pageable PackedImages).  Five calls with nothing synchronised in between: a shorter view of
+    the one-shape buffer while the copy before may be queued, another output type, and a request that makes that buffer grow while the
+    copy before may be queued.  Every call gives the host path's pixels bit for bit, and no further staging object exists."""
+    import gc
+    Image = pytest.importorskip("PIL.Image")
+    from pigeon_amd import clip_embedder as ce, jpeg, preprocess as pp
+    from pigeon_amd.packing import PinnedStaging
+    rng = np.random.default_rng(10)
+    a, b, c = ([rng.integers(0, 256, s + (3,), dtype=np.uint8) for _ in range(k)] for s, k in (((60, 80), 3), ((80, 60), 2), ((97, 41), 1)))
+    calls = [(a, torch.float32), (a + b + c, torch.float32), (b, torch.float32), (a, torch.uint8), (c * 40, torch.float32)]
+    dev, need = torch.cuda.current_device(), 40 * 97 * 41 * 3
+    pp._UNIFORM_STAGING.pop(dev, None)                              # (whatever earlier tests grew it to: the last call here must grow it)
+    got = [ce.gpu_preprocess(ims, out_dtype=dt) for ims, dt in calls[:4]]
+    before = pp._UNIFORM_STAGING[dev].buf.numel()
+    assert 3 * 60 * 80 * 3 <= before < need                         # the 2 x (80, 60) list took a shorter view of the same buffer
+    got.append(ce.gpu_preprocess(*calls[4][:1], out_dtype=calls[4][1]))
+    torch.cuda.synchronize()
+    for k, ((ims, dt), px) in enumerate(zip(calls, got)):
+        want = ce.clip_preprocess([Image.fromarray(im) for im in ims])
+        assert px.dtype == dt and torch.equal(px.cpu() if dt != torch.uint8 else env["ops"].bytes_to_pixels(px.cpu()), want), k
+    # exactly one buffer per device for the one-shape lists and one for the ragged path, keyed by the device alone ...
+    for table in (pp._UNIFORM_STAGING, pp._STAGING):
+        assert [i for i in table if type(i) is not int] == [] and type(table[dev]) is PinnedStaging and table[dev].buf.is_pinned()
+    assert pp._UNIFORM_STAGING[dev] is not pp._STAGING[dev]
+    assert pp._UNIFORM_STAGING[dev].buf.numel() >= need > before    # ... the first one grown by the 40-image list
+    assert pp._STAGING[dev].buf.numel() >= env["ops"].ragged_plan([im.shape[:2] for im in a + b + c]).packed_bytes
+    # ... and every staging object alive is one of those (or the JPEG decoder's): none kept anywhere else, per count or per shape
+    known = {id(s) for table in (pp._UNIFORM_STAGING, pp._STAGING, jpeg._STAGING) for s in table.values()}
+    gc.collect()
+    assert {id(o) for o in gc.get_objects() if type(o) is PinnedStaging} == known
 
 
 def test_embed_images_raw_equals_the_host_path(env, tmp_path):

@@ -631,3 +631,30 @@ def test_build_headers_cover_every_include(tmp_path):
     for src in ("gemm_pp.hip", "precise.hip"):
         s = os.path.join(tmp_path, os.path.relpath(os.path.join(build.CSRC, src), root))
         assert build._stale(os.path.join(tmp_path, src.replace(".hip", ".o")), [s] + hdrs), src
+
+
+def test_image_input_modules_and_re_exports():
+    """The image front end lives in pigeon_amd/preprocess.py; clip_embedder re-exports it, and the packing / jpeg names, as the SAME
+    objects (every `from pigeon_amd.clip_embedder import ...` keeps working).  `pigeon_amd.packing` alone -- what a DataLoader worker
+    imports -- pulls in none of the modules that bind the library and initialises no GPU, `PinnedStaging` included."""
+    import subprocess
+    from pigeon_amd import clip_embedder, jpeg, packing, preprocess
+    for name in ("gpu_preprocess", "clip_preprocess"):
+        assert getattr(clip_embedder, name) is getattr(preprocess, name), name
+    for name in ("PackedImages", "pack_images", "pack_into", "packed_layout", "chunk_by_bytes", "as_rgb_array", "check_rgb_u8"):
+        assert getattr(clip_embedder, name) is getattr(packing, name), name
+    for name in ("EncodedImages", "decode_images", "decode_chunks"):
+        assert getattr(clip_embedder, name) is getattr(jpeg, name), name
+    assert preprocess.PinnedStaging is packing.PinnedStaging is jpeg.PinnedStaging
+    code = (
+        "import sys, torch\n"
+        "import pigeon_amd.packing as p\n"
+        "for m in ('_lib', 'hip_ops', 'jpeg', 'preprocess', 'clip_embedder'):\n"
+        "    assert 'pigeon_amd.' + m not in sys.modules, m + ' was imported'\n"
+        "s = p.PinnedStaging()\n"
+        "assert s.buf is None and s.event is None and not torch.cuda.is_initialized()\n"
+        "print('packing alone')\n")
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, cwd=root,
+                       env=dict(os.environ, HIP_VISIBLE_DEVICES="", PYTHONPATH=root))
+    assert r.returncode == 0 and "packing alone" in r.stdout, r.stderr
