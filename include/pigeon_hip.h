@@ -50,7 +50,8 @@ extern "C" {
                               *    + PG_DTYPE_U8 pixels and pg_prep_norm_lut, additive; + pg_vit_param_read, additive;
                               *    + pg_refine_certainty_bank, additive;
                               *    + pg_jpeg_probe, pg_jpeg_reason, pg_jpeg_plan, pg_jpeg_entropy_decode, pg_jpeg_forward, pg_jpeg_info and
-                              *      pg_jpeg_item, additive) */
+                              *      pg_jpeg_item, additive;
+                              *    + pg_token_attribution, additive) */
 
 const char* pg_last_error(void);
 int pg_abi_version(void);
@@ -425,6 +426,33 @@ int pg_head_wstats(const float* W, int C, const float* beta, float* out2, void* 
  * differs from image to image, which pg_head_certainty / pg_refine_certainty account for.  The norm is summed in a fixed order (a row's
  * bits do not depend on the batch).  Asynchronous on `stream`. */
 int pg_embedding_debias(float* emb, int64_t n, int dim, const float* bias, void* stream);
+
+/* Patch attribution: a geocell logit, or the difference of two, as an exact sum over tokens (csrc/attribution.hip).  The embedding is
+ * the plain mean of the 577 rows of last_hidden_state and the head one Linear over the mean of the P views (reference
+ * models/clip_embedder.py:65, models/super_guessr.py:398, :437, :447), so
+ *     logit[c] - logit[r] = (b[c] - b[r]) + sum over views p, tokens t of  h[p,t,:] . (W[c] - W[r]) / (577 P)
+ * and this entry point computes the summands.
+ *   hidden   DEVICE (n_images, 577, 1024) fp32: what pg_vit_forward_hidden / pg_vit_forward_precise write as `hidden_out`;
+ *            n_images = B * P, P >= 1 views per sample as in pg_head_forward (anything else: PG_EINVAL)
+ *   W        DEVICE (C, 1024) fp32, the head's weight;  hidden and W 16-byte aligned
+ *   cells    DEVICE (B, K) int64, 1 <= K <= 16: the cells to explain, per sample
+ *   against  DEVICE (B) int64 or NULL: the cell each of the sample's K cells is compared with; an entry of -1 (or NULL) means none
+ *   out      DEVICE (B, P, 577, K) fp32:
+ *              g[j] = W[cells[b,k]][j] - W[against[b]][j]   in fp32, one rounding (W[cells[b,k]][j] itself without `against`)
+ *              d    = sum_j h[b,p,t,j] * g[j]               in fp32, in this fixed order: lane l = 0..63 of a wave runs
+ *                     s_l = fma(h[j], g[j], s_l) over j = 256 i + 4 l + e, i = 0..3 outer, e = 0..3 inner, from s_l = 0; then the
+ *                     64 partial sums are added by the butterfly v <- v + v(lane xor o), o = 32, 16, 8, 4, 2, 1
+ *              out  = d / (float)(577 P)                     one IEEE division
+ * The bits of out[b,p,t,k] are a function of that hidden row, the two rows of W and P alone: not of the batch size, of K, or of the
+ * position k.  Token 0 is the class token, token 1 + 24 y + x the patch in row y, column x of the 336 x 336 crop.
+ * The indices are device data and the kernel checks them: cells[b,k] outside [0, C) makes column (b, k) NaN on all of its P * 577
+ * rows; against[b] outside [0, C) other than -1 makes every column of sample b NaN; no such index ever forms an address, and nothing
+ * else in `out` is affected.  Nothing outside `out` is written.
+ * n_images = 0 is a no-op (PG_OK; the buffers may be NULL); n_images < 0 or not a multiple of P, P < 1, K outside 1..16, C < 1, a
+ * NULL hidden / W / cells / out and a misaligned hidden / W are PG_EINVAL with a message naming the argument.  One launch,
+ * asynchronous on `stream`. */
+int pg_token_attribution(const float* hidden, int n_images, int P, const float* W, int C, const int64_t* cells,
+                         const int64_t* against, int K, float* out, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * CLIP image preprocessing (the step in front of the encoder): uint8 RGB -> pixel_values.

@@ -926,6 +926,55 @@ def embedding_debias(emb: torch.Tensor, bias: torch.Tensor) -> torch.Tensor:
     return emb
 
 
+def _arg(t, name: str, dtype: torch.dtype) -> torch.Tensor:
+    """A contiguous device tensor of `dtype`, or a PigeonHipError that names the argument."""
+    if not torch.is_tensor(t):
+        raise _lib.PigeonHipError(f"{name} must be a tensor, got {type(t).__name__}")
+    if not t.is_cuda:
+        raise _lib.PigeonHipError(f"{name} must be a device tensor, got one on {t.device}")
+    if t.dtype != dtype:
+        raise _lib.PigeonHipError(f"{name} must have dtype {dtype}, got {t.dtype}")
+    if not t.is_contiguous():
+        raise _lib.PigeonHipError(f"{name} must be contiguous, got strides {tuple(t.stride())} for shape {tuple(t.shape)}")
+    return t
+
+
+def token_attribution(hidden: torch.Tensor, W: torch.Tensor, cells: torch.Tensor, against: Optional[torch.Tensor] = None,
+                      panels: int = 1, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """pg_token_attribution: each of K head directions as a sum over tokens.  hidden (n,577,1024) fp32 (last_hidden_state of
+    n = B * panels images), W (C,1024) fp32, cells (B,K) int64 with 1 <= K <= 16, against (B,) int64 or None (an entry of -1: none).
+    Returns maps (B,panels,577,K) fp32:  maps[b,p,t,k] = hidden[b*panels+p,t] . (W[cells[b,k]] - W[against[b]]) / (577 panels), so
+    that maps.sum((1,2)) is the token part of logit[cells[b,k]] - logit[against[b]] of the mean-pooled linear head.  An index outside
+    [0, C) makes its column (cells) or its sample (against) NaN; it is never dereferenced.  All tensors on the device.  `out`
+    (B,panels,577,K) fp32: write there instead of a fresh tensor."""
+    _arg(hidden, "hidden", torch.float32); _arg(W, "W", torch.float32); _arg(cells, "cells", torch.int64)
+    if hidden.dim() != 3 or tuple(hidden.shape[1:]) != (TOKENS, HIDDEN):
+        raise _lib.PigeonHipError(f"hidden must have shape (*,{TOKENS},{HIDDEN}), got {tuple(hidden.shape)}")
+    _shape(W, "W", None, HIDDEN)
+    n, P, Cn = int(hidden.shape[0]), int(panels), int(W.shape[0])
+    if P < 1 or n % P != 0:
+        raise _lib.PigeonHipError(f"panels = {panels}: hidden holds {n} images, not a multiple of it (PG_EINVAL)")
+    if Cn < 1:
+        raise _lib.PigeonHipError("W must have at least one row (PG_EINVAL)")
+    B = n // P
+    _shape(cells, "cells", B, None)
+    K = int(cells.shape[1])
+    if not 1 <= K <= 16:
+        raise _lib.PigeonHipError(f"cells must have 1..16 columns (K), got {K} (PG_EINVAL)")
+    if against is not None:
+        _arg(against, "against", torch.int64); _shape(against, "against", B)
+    if out is None:
+        out = torch.empty((B, P, TOKENS, K), dtype=torch.float32, device=hidden.device)
+    _arg(out, "out", torch.float32); _shape(out, "out", B, P, TOKENS, K)
+    for name, t in (("W", W), ("cells", cells), ("against", against), ("out", out)):
+        if t is not None and t.device != hidden.device:
+            raise _lib.PigeonHipError(f"{name} is on {t.device}, hidden on {hidden.device}")
+    with torch.cuda.device(hidden.device):
+        check(load().pg_token_attribution(_p(hidden), n, P, _p(W), Cn, _p(cells), _p(against), K, _p(out), _stream()),
+              "pg_token_attribution")
+    return out
+
+
 def fingerprint(t: torch.Tensor, seed: int = 0):
     """pg_fingerprint -> (int, int): the 128-bit digest (csrc/fingerprint.hip) of the bytes of the contiguous device tensor `t`, which
     must start on a 16-byte boundary (PigeonHipError otherwise).  Synchronises the current stream: the result is a host value."""

@@ -69,11 +69,13 @@ def panorama_from_request(body: Dict, encoded: bool = False) -> List:
     return views
 
 
-def predict_panorama(views: Sequence, model, refiner=None, preprocess: Optional[Callable] = None) -> Dict:
+def predict_panorama(views: Sequence, model, refiner=None, preprocess: Optional[Callable] = None, attribution: bool = False) -> Dict:
     """views: four PIL images -> {'lat', 'lng'} (+ 'geocell_margin', 'geocell_certain', 'reencoded_exact' when the model exposes the
     certainty of its top-1).  `preprocess(list of PIL) -> (4,3,336,336)` defaults to the GPU path.  Views that are all `bytes` (image
     files) go to the same path undecoded: baseline JPEGs are decoded on the GPU (pigeon_amd/jpeg.py: Pillow's pixels, bit for bit),
-    anything else by Pillow; a payload neither can read is a BadRequest.  With an injected `preprocess` bytes are decoded first."""
+    anything else by Pillow; a payload neither can read is a BadRequest.  With an injected `preprocess` bytes are decoded first.
+    attribution=True adds 'attribution': the top-1 cell against its runner-up as a sum over the views' patches (`model.attribute`,
+    pigeon_amd/explain.py `attribution_json`; on the exact tier when this panorama was re-encoded there)."""
     import torch
     views = list(views)
     as_bytes = bool(views) and all(isinstance(v, (bytes, bytearray)) for v in views)
@@ -114,6 +116,11 @@ def predict_panorama(views: Sequence, model, refiner=None, preprocess: Optional[
         res["geocell_margin"] = float(model.last_margin.reshape(-1)[0])
         res["geocell_certain"] = bool(model.last_certain.reshape(-1)[0])
         res["reencoded_exact"] = bool(getattr(model, "last_reencoded", None) is not None and model.last_reencoded.numel() > 0)
+    if attribution:
+        from .explain import attribution_json
+        with torch.no_grad():
+            att = model.attribute(pixel_values=px, tier="exact" if res.get("reencoded_exact") else "fast")
+        res["attribution"] = attribution_json(att)
     return res
 
 
@@ -130,10 +137,14 @@ def make_app(model, refiner=None, preprocess: Optional[Callable] = None, game_lo
             views = panorama_from_request(body, encoded)
         except (BadRequest, json.JSONDecodeError) as e:
             return JSONResponse({"error": str(e)}, status_code=400)
+        attribution = body.get("attribution") is True
+        if attribution and not hasattr(model, "attribute"):
+            return JSONResponse({"error": "this model has no patch attribution ('attribution': true needs SuperGuessr.attribute)"},
+                                status_code=400)
         # called inline on the event loop, on purpose: the handles behind `model` are one per (device, stream) and not
         # thread-safe, so requests are answered one at a time -- a `def` handler would run in Starlette's pool
         try:
-            res = predict_panorama(views, model, refiner, preprocess)
+            res = predict_panorama(views, model, refiner, preprocess, attribution=attribution)
         except BadRequest as e:                                    # (encoded mode: the payloads are only decoded in there)
             return JSONResponse({"error": str(e)}, status_code=400)
         return JSONResponse({"gameID": body.get("gameID"), "roundID": body.get("roundID"), "results": res})

@@ -29,6 +29,8 @@ from .utils import ModelOutput, TopK, resolve_name
 
 # reference models/super_guessr.py:12-23
 MultiTaskPredictions = namedtuple('MultiTaskPredictions', 'loss_reg preds_mt loss_climate preds_climate loss_month preds_month')
+# what `SuperGuessr.attribute` returns: maps (B,P,577,K), offset (B,K), cells (B,K), against (B,), logits (B,K)
+Attribution = namedtuple('Attribution', 'maps offset cells against logits')
 NUM_MULTI_TASK_VARIABLES = 6
 REGRESSION_LOSS_SCALING = 8
 NUM_CLIMATES = 28
@@ -411,6 +413,111 @@ class SuperGuessr(nn.Module):
         o = self._head_with_tol(self._head_rows(emb), exact=True)
         o['embedding'] = emb
         return o
+
+    @torch.no_grad()
+    def attribute(self, pixel_values: Tensor = None, pixel_bytes: Tensor = None, cells=None, k: int = 1, against='runner_up',
+                  tier: str = 'fast') -> Attribution:
+        """WHY a cell: each geocell logit -- or the difference of two -- as an exact sum over the views' tokens.
+
+        The embedding is the plain mean of the 577 rows of last_hidden_state (:398) and the head one Linear over the mean of the views
+        (:437, :447), so for g = W[cell] - W[against]
+            logit[cell] - logit[against] = (b[cell] - b[against]) + sum_p sum_t h[p,t,:] . g / (577 P)
+        is an identity: the class-activation map of a mean-pooled linear head.  One encoder pass that keeps the hidden states
+        (`tier='fast'`: pg_vit_forward_hidden, `tier='exact'`: pg_vit_forward_precise; a tower whose calibration sends every sample to the
+        exact encoder is attributed there whatever `tier` says, as `encode_head` encodes it), the embedding treated as `encode_head`
+        treats it (pg_embedding_debias on the fast tier when a calibrated bias is loaded), pg_head_forward, and pg_token_attribution
+        over the hidden rows.  Returns `Attribution`:
+          maps    (B,P,577,K) fp32  the summands; token 0 is the class token, token 1 + 24 y + x the patch in row y, column x of the
+                                    336 x 336 crop (pigeon_amd/explain.py `patch_grid`); P = 4 views, 1 with panorama=False
+          offset  (B,K) fp32        everything that is not a token: b[cell] - b[against] and, on a de-biased fast pass,
+                                    -(1/P) sum_p |e_p|_2 (g . beta) for the bias vector beta the embeddings had subtracted
+          cells   (B,K) int64       `cells` as given, or with cells=None this pass's top-`k` cells (k <= 16)
+          against (B,) int64        -1: none (the maps explain logit[cell] itself)
+          logits  (B,K) fp32        the model's own logit[cell] - logit[against] of this pass (pg_head_forward's fp32 logits)
+        so that maps.sum((1,2)) + offset reproduces logits up to fp32 summation error.
+        `against`: None; a (B,) tensor of cells (-1: none for that sample); or 'runner_up' (default): the pass's top-2 cell -- the
+        direction W[top1] - W[top2] is the one the certainty contract reasons about -- except for a sample whose FIRST listed cell is
+        that runner-up itself, which is compared against the top-1.  A column whose cell equals `against` is exact zeros.  With a single
+        geocell there is no runner-up (-1).  A listed index outside [0, C) gives NaN in its column (its sample, for `against`) of maps,
+        offset and logits.
+        Images go through the encoder in chunks of at most 128 (the hidden states of a chunk are 0.28 GiB).  The call is read-only on
+        the object: it neither starts nor feeds the auto-calibration, leaves `last_*` alone and queues nothing on the deferred engine."""
+        self._check_pixel_bytes(pixel_bytes, pixel_values, None)
+        if self.base_model is None:
+            raise ValueError('attribute needs a base model: the attribution is over the encoder\'s tokens')
+        if (pixel_values is None) == (pixel_bytes is None):
+            raise ValueError('attribute: exactly one of pixel_values and pixel_bytes')
+        if tier not in ('fast', 'exact'):
+            raise ValueError(f"attribute: tier must be 'fast' or 'exact', got {tier!r}")
+        if not self.cell_layer.weight.is_cuda:
+            raise RuntimeError('pigeon_amd.SuperGuessr runs on the GPU only: call .to("cuda") first (no CPU fallback)')
+        if not (against is None or torch.is_tensor(against) or against == 'runner_up'):
+            raise ValueError(f"attribute: against must be 'runner_up', None or a (B,) tensor, got {against!r}")
+        dev = self.cell_layer.weight.device
+        P, Cn = self._panels(), self.num_cells
+        px = pixel_bytes if pixel_bytes is not None else pixel_values
+        px = px.reshape((-1, 3, 336, 336)).to(dev)
+        if pixel_bytes is None and px.dtype == torch.uint8:
+            px = px.float()                              # (pixel_values: numbers, as in `encode_head`)
+        if px.shape[0] % P:
+            raise ValueError(f'attribute: {px.shape[0]} images are not whole samples of {P} views')
+        B = px.shape[0] // P
+        if cells is not None:
+            cells = torch.as_tensor(cells, dtype=torch.int64).to(dev).reshape((B, -1)).contiguous()
+            k = int(cells.shape[1])
+        if not 1 <= int(k) <= 16 or (cells is None and k > Cn):
+            raise ValueError(f'attribute: k = {k} cells per sample (1..16, at most the {Cn} geocells)')
+        if torch.is_tensor(against):
+            against = against.to(dev, torch.int64).reshape((B,)).contiguous()
+        exact = tier == 'exact' or bool(self.certainty.force_exact and self.exact_top1)
+        base = self._encoder()
+        px = base._pixels(None, px) if pixel_bytes is not None else base._pixels(px, None)
+        if exact:
+            base.enable_precise(True)
+        enc = base._encoder(px.device)
+        W = self.cell_layer.weight.data
+        W = (W if W.dtype == torch.float32 else W.float()).contiguous()
+        hb = self.cell_layer.bias.data.float()
+        beta = None if exact else self.certainty.bias_on(dev)
+        per = max(1, 128 // P)                           # samples per chunk: at most 128 images
+        parts = []
+        for s0 in range(0, B, per):
+            n = min(per, B - s0)
+            chunk = px[s0 * P:(s0 + n) * P].contiguous()
+            emb, hid = (enc.forward_precise if exact else enc.forward)(chunk, return_hidden=True)
+            norms = None
+            if beta is not None:
+                norms = emb.double().norm(dim=1).reshape((n, P))       # |e_p|_2 of the embeddings as the encoder wrote them
+                hip_ops.embedding_debias(emb, beta)
+            head_in = self._head_rows(emb.reshape((n, 4, emb.shape[-1])) if self.panorama else emb)
+            o = hip_ops.head_forward(head_in, W, hb, self.lla_geocells.data, min(Cn, max(2, k)))
+            top = o['topk_indices']
+            c = top[:, :k].contiguous() if cells is None else cells[s0:s0 + n]
+            if torch.is_tensor(against):
+                a = against[s0:s0 + n]
+            elif against is None or Cn < 2:
+                a = torch.full((n,), -1, dtype=torch.int64, device=dev)
+            else:                                        # 'runner_up'
+                a = torch.where(c[:, 0] == top[:, 1], top[:, 0], top[:, 1]).contiguous()
+            maps = hip_ops.token_attribution(hid, W, c, a, panels=P)
+            del hid
+            # the model's own logit differences and the part that is no token; an index the kernel refuses is NaN here too
+            c_ok, a_none = (c >= 0) & (c < Cn), a == -1
+            ok = c_ok & (a_none | ((a >= 0) & (a < Cn)))[:, None]
+            cc, ac = c.clamp(0, Cn - 1), a.clamp(0, Cn - 1)
+            lg = o['logits']
+            nan = torch.full((), float('nan'), dtype=torch.float32, device=dev)
+            la = torch.where(a_none, torch.zeros((), device=dev), lg.gather(1, ac[:, None])[:, 0])
+            diff = torch.where(ok, lg.gather(1, cc) - la[:, None], nan)
+            off = hb[cc].double() - torch.where(a_none, torch.zeros((), dtype=torch.float64, device=dev), hb[ac].double())[:, None]
+            if beta is not None:
+                g = W[cc] - torch.where(a_none[:, None], torch.zeros((), device=dev), W[ac])[:, None, :]      # (n,K,1024) fp32, as the kernel forms it
+                off = off - norms.mean(dim=1)[:, None] * (g.double() * beta.double()).sum(dim=-1)
+            parts.append((maps, torch.where(ok, off.float(), nan), c, a, diff))
+        if not parts:
+            z = lambda *s, dt=torch.float32: torch.zeros(s, dtype=dt, device=dev)
+            return Attribution(z(0, P, 577, k), z(0, k), z(0, k, dt=torch.int64), z(0, dt=torch.int64), z(0, k))
+        return Attribution(*(torch.cat([p[i] for p in parts]) if len(parts) > 1 else parts[0][i] for i in range(5)))
 
     def _publish(self, st: dict) -> None:
         if 'certain' not in st:                          # a state straight from `encode_head` (no engine behind it)
