@@ -51,7 +51,8 @@ extern "C" {
                               *    + pg_refine_certainty_bank, additive;
                               *    + pg_jpeg_probe, pg_jpeg_reason, pg_jpeg_plan, pg_jpeg_entropy_decode, pg_jpeg_forward, pg_jpeg_info and
                               *      pg_jpeg_item, additive;
-                              *    + pg_token_attribution, additive) */
+                              *    + pg_token_attribution, additive;
+                              *    + pg_equirect_plan, pg_equirect_forward, pg_eq_view and pg_eq_item, additive) */
 
 const char* pg_last_error(void);
 int pg_abi_version(void);
@@ -602,6 +603,60 @@ int pg_jpeg_entropy_decode(int n, const void* const* data, const size_t* nbytes,
  * `stream`: one copy and two launches. */
 int pg_jpeg_forward(const void* coef_dev, size_t coef_bytes, const pg_jpeg_item* items_host, const pg_prep_item* prep_items_host, int n,
                     void* packed_dev, size_t packed_bytes, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Equirectangular panoramas in front of the ragged resize: perspective (gnomonic) S x S views of an H x W equirectangular image,
+ * 8-bit RGB, written straight into the packed buffer pg_prep_ragged_forward reads.  One integer result per pixel (DESIGN.md,
+ * "Equirectangular panoramas in"; tests/_equirectref.py is the numpy restatement).  The host computes the only two quantities that
+ * carry the angles, in float64, and they travel as doubles:
+ *   inv_f = tan(fov / 2) / (S / 2)
+ *   rot   = Ry(yaw) . Rx(pitch), camera -> panorama, row-major; axes x right, y DOWN, z forward; yaw positive to the right, pitch
+ *           positive upwards:  [[C, Sn*s, Sn*c], [0, c, -s], [-Sn, C*s, C*c]]  with c, s of the pitch and C, Sn of the yaw.
+ * Pixel (row i, column j), IEEE float64, in this order, no contraction:
+ *   x = (j + 0.5 - S/2) * inv_f,  y = (i + 0.5 - S/2) * inv_f,  w_k = (rot[k][0]*x + rot[k][1]*y) + rot[k][2]
+ *   lambda = atan2(w_X, w_Z),  phi = atan2(-w_Y, sqrt(w_X*w_X + w_Z*w_Z))
+ *   u = (lambda * (1/(2 pi)) + 0.5) * W - 0.5,  v = (0.5 - phi * (1/pi)) * H - 0.5 clamped to [0, H - 1]
+ *   u0 = floor(u), v0 = floor(v), a = floor((u - u0) * 256 + 0.5), b = floor((v - v0) * 256 + 0.5)     (0 .. 256)
+ *   columns u0 mod W and (u0 + 1) mod W (true modulo: the seam wraps), rows v0 and min(v0 + 1, H - 1)
+ *   out_c = (p00*(256-a)*(256-b) + p01*a*(256-b) + p10*(256-a)*b + p11*a*b + 32768) >> 16
+ * The weights sum to 65536: a constant image stays constant.  Addresses come from clamped or wrapped integers only.
+ * ------------------------------------------------------------------------------------------------ */
+#define PG_EQ_ITEM_BYTES 128
+#define PG_EQ_MAX_VIEW 4096
+typedef struct pg_eq_view {           /* what the caller knows of one view (input of pg_equirect_plan), 96 bytes */
+    int32_t src_h, src_w;             /* the panorama's size, 1..16384 */
+    int32_t src_index;                /* which of the plan's source offsets holds it */
+    int32_t size;                     /* S, 1..PG_EQ_MAX_VIEW */
+    double rot[9];                    /* row-major, finite */
+    double inv_f;                     /* finite, positive */
+} pg_eq_view;
+typedef struct pg_eq_item {           /* one view of a batch (plain data, PG_EQ_ITEM_BYTES bytes) */
+    uint64_t src_off;                 /* byte offset of the panorama's (src_h, src_w, 3) RGB in the source buffer (multiple of 16) */
+    uint64_t dst_off;                 /* byte offset of the view's (size, size, 3) RGB in the packed buffer: its pg_prep_item.src_off */
+    int32_t src_h, src_w, size;
+    int32_t reserved0;                /* zero */
+    double rot[9];
+    double inv_f;
+    int32_t reserved[4];              /* zero */
+} pg_eq_item;
+/* HOST ONLY (no HIP call; works in a process that never opens a GPU).  n views; view i reads the panorama at src_offs[views[i].src_index]
+ * of the source buffer (n_src offsets, multiples of 16; several views may name one panorama).  Fills items_out[n]; prep_items_out[n],
+ * *packed_bytes and *prep_workspace_bytes are exactly what pg_prep_ragged_plan gives for n images of size x size, and
+ * items_out[i].dst_off == prep_items_out[i].src_off.  PG_EINVAL naming the view for a size out of range, a rot or inv_f that is not
+ * finite (inv_f: and positive), a source index outside [0, n_src) or a misaligned source offset.  n = 0: both sizes 0. */
+int pg_equirect_plan(int n, const pg_eq_view* views, int n_src, const uint64_t* src_offs, pg_eq_item* items_out,
+                     pg_prep_item* prep_items_out, size_t* packed_bytes, size_t* prep_workspace_bytes);
+/* src_dev: DEVICE, src_bytes bytes, 16-byte aligned: the panoramas at their offsets.  It may be a packed buffer written by
+ * pg_jpeg_forward or filled from host pixels -- its descriptors in the head are simply not read -- so a panorama file goes file bytes
+ * -> JPEG kernels -> this kernel -> resize without visiting the host.  Writes every view to [dst_off, dst_off + size * size * 3) of
+ * packed_dev, copies prep_items_host (n * PG_PREP_ITEM_BYTES bytes) into its head, and writes nothing else; packed_dev can then go to
+ * pg_prep_ragged_forward as it is.  Before anything is launched every descriptor is checked: sizes 1..16384 (source) and
+ * 1..PG_EQ_MAX_VIEW (view), finite rot and finite positive inv_f, zero reserved fields, offsets that are multiples of 16, ascending
+ * overlap-free destination ranges inside packed_bytes, source ranges inside src_bytes, dst_off == prep_items_host[i].src_off, and the
+ * two buffers must not overlap: PG_EINVAL naming the view.  n = 0 is a no-op.  Asynchronous on `stream`: two copies (the two
+ * descriptor arrays; the views' go to stream-ordered scratch) and one launch. */
+int pg_equirect_forward(const void* src_dev, size_t src_bytes, const pg_eq_item* items_host, const pg_prep_item* prep_items_host, int n,
+                        void* packed_dev, size_t packed_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * The one collective of the path: all-gather over RCCL (xGMI inside a node).

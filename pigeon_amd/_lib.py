@@ -70,6 +70,22 @@ JPEG_REASONS = ("ok", "not_jpeg", "progressive", "lossless", "hierarchical", "ar
                 "sampling", "multiscan", "dnl", "size", "malformed")          # PG_JPEG_R_*: index = code
 
 
+class EqView(C.Structure):
+    """pg_eq_view (include/pigeon_hip.h): what the caller knows of one view of a panorama, the input of pg_equirect_plan."""
+    _fields_ = [("src_h", C.c_int32), ("src_w", C.c_int32), ("src_index", C.c_int32), ("size", C.c_int32), ("rot", C.c_double * 9),
+                ("inv_f", C.c_double)]
+
+
+class EqItem(C.Structure):
+    """pg_eq_item (include/pigeon_hip.h): one view of an equirectangular batch, EQ_ITEM_BYTES bytes."""
+    _fields_ = [("src_off", C.c_uint64), ("dst_off", C.c_uint64), ("src_h", C.c_int32), ("src_w", C.c_int32), ("size", C.c_int32),
+                ("reserved0", C.c_int32), ("rot", C.c_double * 9), ("inv_f", C.c_double), ("reserved", C.c_int32 * 4)]
+
+
+EQ_ITEM_BYTES = 128
+assert C.sizeof(EqItem) == EQ_ITEM_BYTES and C.sizeof(EqView) == 96
+
+
 # name -> (restype, argtypes); must list EVERY symbol declared in include/pigeon_hip.h (tests check this)
 _P, _I, _I64, _F, _D, _SZ = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_double, C.c_size_t
 SIGNATURES = {
@@ -128,6 +144,9 @@ SIGNATURES = {
                           C.POINTER(_SZ)]),
     "pg_jpeg_entropy_decode": (_I, [_I, C.POINTER(_P), C.POINTER(_SZ), C.POINTER(JpegItem), _P, _SZ, _I, C.POINTER(_I)]),
     "pg_jpeg_forward": (_I, [_P, _SZ, C.POINTER(JpegItem), C.POINTER(PrepItem), _I, _P, _SZ, _P, _SZ, _P]),
+    "pg_equirect_plan": (_I, [_I, C.POINTER(EqView), _I, C.POINTER(C.c_uint64), C.POINTER(EqItem), C.POINTER(PrepItem), C.POINTER(_SZ),
+                              C.POINTER(_SZ)]),
+    "pg_equirect_forward": (_I, [_P, _SZ, C.POINTER(EqItem), C.POINTER(PrepItem), _I, _P, _SZ, _P]),
     "pg_proto_build": (_I, [_P, _I, _I64, _P, _P, _I64, _P, _P]),
     "pg_haversine_matrix": (_I, [_P, _I, _P, _I, _I, _P, _P]),
     "pg_haversine_pairs": (_I, [_P, _P, _I, _I64, _P, _P]),

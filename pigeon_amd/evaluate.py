@@ -167,10 +167,12 @@ class ImageEvalDataset:
     the whole mixed-size batch to 8-bit pixels in one ragged call (`preprocess`) and submits them as `pixel_bytes`.  String keys are
     column reads of the wrapped dataset (`dataset['labels']`, as `evaluate_model` collects the labels for the metrics).
     encoded=True: the image columns hold files (bytes, paths, or the dicts of HF `Image(decode=False)` columns); a worker ships the
-    bytes as an `EncodedImages` and the decode runs on the GPU too (`gpu_preprocess(EncodedImages)`, pigeon_amd/jpeg.py)."""
+    bytes as an `EncodedImages` and the decode runs on the GPU too (`gpu_preprocess(EncodedImages)`, pigeon_amd/jpeg.py).
+    equirect=True: every item's single `image` column holds ONE equirectangular panorama (raw, or a file with encoded=True); the four
+    views at headings 0 / 90 / 180 / 270 are rendered from it on the GPU (pigeon_amd/panorama.py) in front of the resize."""
 
-    def __init__(self, dataset, encoded: bool = False):
-        self.dataset, self.encoded = dataset, encoded
+    def __init__(self, dataset, encoded: bool = False, equirect: bool = False):
+        self.dataset, self.encoded, self.equirect = dataset, encoded, equirect
 
     def __len__(self) -> int:
         return len(self.dataset)
@@ -182,8 +184,12 @@ class ImageEvalDataset:
         item = self.dataset[idx]
         if 'image' not in item:
             raise KeyError("ImageEvalDataset: items need an 'image' column (or 'image', 'image_2', 'image_3', 'image_4')")
+        if self.equirect and 'image_2' in item:
+            raise KeyError("ImageEvalDataset(equirect=True): items hold ONE equirectangular 'image', these also have 'image_2'")
         views = [item[k] for k in (IMAGE_KEYS if 'image_2' in item else IMAGE_KEYS[:1])]
         out = {k: v for k, v in item.items() if 'image' not in k}              # (the reference drops every image column the same way)
+        if self.equirect:
+            out['equirect'] = True
         if self.encoded:                                           # the files' bytes as they are: the worker does nothing but read
             from .jpeg import EncodedImages, image_bytes
             out['images'] = EncodedImages([image_bytes(v) for v in views])
@@ -200,7 +206,9 @@ class ImageEvalDataset:
         views = {len(b['images']) for b in batch}
         if len(views) != 1:
             raise ValueError(f'ImageEvalDataset: items of one batch hold {sorted(views)} views; every item must have the same number')
-        out = default_collate([{k: v for k, v in b.items() if k != 'images'} for b in batch])
+        out = default_collate([{k: v for k, v in b.items() if k not in ('images', 'equirect')} for b in batch])
+        if any(b.get('equirect') for b in batch):
+            out['equirect'] = True
         from .jpeg import EncodedImages
         parts = [b['images'] for b in batch]
         out['images'] = EncodedImages.concat(parts) if isinstance(parts[0], EncodedImages) else concat_packed(parts)
@@ -214,6 +222,11 @@ class ImageEvalDataset:
         from .clip_embedder import gpu_preprocess
         data = dict(data)
         packed, views = data.pop('images'), int(data.pop('views'))
+        if data.pop('equirect', False):                            # one panorama per item: its four views, panorama-major
+            from .panorama import HEADINGS, panorama_pixels
+            px = panorama_pixels(packed, device, torch.uint8)
+            data['pixel_bytes'] = px.reshape((len(packed), 3 * len(HEADINGS), 336, 336))
+            return data
         px = gpu_preprocess(packed, device, torch.uint8)
         data['pixel_bytes'] = px.reshape((len(packed) // views, 3 * views, 336, 336))
         return data

@@ -657,6 +657,62 @@ def jpeg_forward(coef_dev: torch.Tensor, plan: JpegPlan, packed_dev: torch.Tenso
     return packed_dev
 
 
+# ----------------------------------------------------------------------------------------- equirectangular panoramas
+class EquirectPlan:
+    """What pg_equirect_plan makes of a list of views: one pg_eq_item per view (`items`), the ragged resize's plan for n images of
+    size x size (`prep`, a RaggedPlan: same integers as `ragged_plan`) and the bytes the source buffer must at least hold."""
+
+    def __init__(self, items, prep: "RaggedPlan", src_bytes: int):
+        self.items, self.prep = items, prep
+        self.n = len(items)
+        self.src_bytes = int(src_bytes)
+
+
+def equirect_plan(views, src_offs) -> EquirectPlan:
+    """pg_equirect_plan.  `views`: a list of (src_h, src_w, src_index, size, rot, inv_f) with `rot` nine floats (row-major, camera ->
+    panorama) and inv_f = tan(fov / 2) / (size / 2); `src_offs`: byte offset of every panorama in the source buffer.  Host only."""
+    n = len(views)
+    arr = (_lib.EqView * n)()
+    for v, (h, w, k, s, rot, inv_f) in zip(arr, views):
+        rot = [float(r) for r in (rot.reshape(-1).tolist() if hasattr(rot, "reshape") else rot)]
+        if len(rot) != 9:
+            raise _lib.PigeonHipError(f"a view's rotation must have 9 entries, got {len(rot)}")
+        v.src_h, v.src_w, v.src_index, v.size, v.inv_f = int(h), int(w), int(k), int(s), float(inv_f)
+        v.rot[:] = rot
+    offs = [int(o) for o in src_offs]
+    if any(o < 0 for o in offs):
+        raise _lib.PigeonHipError("equirect_plan: a source offset is negative")
+    offs_c = (C.c_uint64 * max(len(offs), 1))(*offs)
+    items, prep_items = (_lib.EqItem * n)(), (_lib.PrepItem * n)()
+    packed, prep_ws = C.c_size_t(), C.c_size_t()
+    check(load().pg_equirect_plan(n, arr, len(offs), offs_c, items, prep_items, C.byref(packed), C.byref(prep_ws)), "pg_equirect_plan")
+    prep = RaggedPlan([(int(v.size), int(v.size)) for v in arr], prep_items, packed.value, prep_ws.value)
+    src_bytes = max([int(it.src_off) + int(it.src_h) * int(it.src_w) * 3 for it in items], default=0)
+    return EquirectPlan(items, prep, src_bytes)
+
+
+def equirect_forward(src_dev: torch.Tensor, plan: EquirectPlan, packed_dev: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """pg_equirect_forward: the panoramas in `src_dev` (DEVICE 1-D uint8; a packed buffer of the JPEG stage or of host pixels will do,
+    its head is not read) -> every view's RGB at its place in `packed_dev` (1-D uint8 of plan.prep.packed_bytes bytes, made here if
+    None) and the resize's descriptors in its head.  Returns packed_dev."""
+    _dev(src_dev, torch.uint8)
+    if src_dev.dim() != 1 or src_dev.numel() < plan.src_bytes:
+        raise _lib.PigeonHipError(f"source buffer must be 1-D uint8 of at least {plan.src_bytes} bytes, got {tuple(src_dev.shape)}")
+    if packed_dev is None:
+        packed_dev = torch.empty(plan.prep.packed_bytes, dtype=torch.uint8, device=src_dev.device)
+    _dev(packed_dev, torch.uint8)
+    if packed_dev.dim() != 1 or packed_dev.numel() != plan.prep.packed_bytes:
+        raise _lib.PigeonHipError(f"packed buffer must be 1-D uint8 of {plan.prep.packed_bytes} bytes, got {tuple(packed_dev.shape)}")
+    if packed_dev.device != src_dev.device:
+        raise _lib.PigeonHipError("source and packed buffers are on different devices")
+    if plan.n == 0:
+        return packed_dev
+    with torch.cuda.device(src_dev.device):
+        check(load().pg_equirect_forward(_p(src_dev), src_dev.numel(), plan.items, plan.prep.items, plan.n, _p(packed_dev),
+                                         plan.prep.packed_bytes, _stream()), "pg_equirect_forward")
+    return packed_dev
+
+
 # ----------------------------------------------------------------------------------------- ViT encoder handle
 class VitEncoder(_Handle):
     """Owns a pg_vit handle: 16-bit-packed weights (fp16 or bf16) resident in HBM, forward = ViT-L/14-336 + token mean.

@@ -12,7 +12,7 @@ from torch import Tensor
 
 from . import hip_ops
 from .config import OPENAI_CLIP_MEAN, OPENAI_CLIP_STD
-from .jpeg import EncodedImages, decode_chunks
+from .jpeg import DecodedImages, EncodedImages, decode_chunks
 from .packing import PackedImages, PinnedStaging, as_rgb_array, check_rgb_u8, chunk_by_bytes, pack_into
 
 
@@ -148,7 +148,8 @@ def _gpu_preprocess_mixed(arrs, dev, out_dtype) -> Tensor:
 
 def gpu_preprocess(images, device="cuda", out_dtype: torch.dtype = torch.float32) -> Tensor:
     """CLIP preprocessing on the GPU: `images` is a uint8 RGB tensor / ndarray (N,H,W,3) or (H,W,3), a list of PIL images / arrays,
-    a `PackedImages`, or an `EncodedImages` (files as bytes: decoded on the GPU, Pillow's pixels bit for bit, then resized in place).
+    a `PackedImages`, an `EncodedImages` (files as bytes: decoded on the GPU, Pillow's pixels bit for bit, then resized in place) or a
+    `DecodedImages` (a packed DEVICE buffer with its plan: what `decode_images` and `panorama.equirect_views` return).
     Tensors and lists of ONE shape run pg_prep_forward (a handle per geometry); a `PackedImages` and a list of several shapes run
     pg_prep_ragged_forward: one packed staging buffer and, per chunk of at most RAGGED_MAX_BYTES (256 MiB) of packed bytes, one copy
     and three launches whatever the sizes.  A PINNED `PackedImages` is copied from in place: its head is overwritten with the
@@ -163,6 +164,9 @@ def gpu_preprocess(images, device="cuda", out_dtype: torch.dtype = torch.float32
             return _gpu_preprocess_packed(images, dev, out_dtype)
         if isinstance(images, EncodedImages):
             return _gpu_preprocess_encoded(images, dev, out_dtype)
+        if isinstance(images, DecodedImages):                      # pixels on the device already: decoded files, rendered panorama views
+            with torch.cuda.device(images.packed.device):
+                return _ragged_preprocessor(images.packed.device.index).forward(images.packed, images.plan, out_dtype, header_written=True)
         if hasattr(images, "convert"):                             # one PIL image, as `processor(images=img)` accepts it
             images = [images]
         staging = None

@@ -23,6 +23,7 @@ import json
 from typing import Callable, Dict, List, Optional, Sequence
 
 IMAGE_KEYS = ("image", "image_2", "image_3", "image_4")          # duel.js:59-62, in heading order
+PANORAMA_KEY = "panorama"                                        # ours: one equirectangular image instead of the four views
 
 
 class BadRequest(ValueError):
@@ -55,10 +56,28 @@ def data_uri_bytes(uri: str) -> bytes:
         raise BadRequest(f"cannot decode image: {e}") from e
 
 
-def panorama_from_request(body: Dict, encoded: bool = False) -> List:
+class EquirectRequest:
+    """One equirectangular panorama of a request (`image`: a PIL image, or the file's bytes in the encoded mode) and the compass
+    heading of its centre column: `predict_panorama` renders the four views 0 / 90 / 180 / 270 from it on the GPU."""
+
+    def __init__(self, image, centre_heading: float = 0.0):
+        self.image, self.centre_heading = image, float(centre_heading)
+
+
+def panorama_from_request(body: Dict, encoded: bool = False):
     """The four views of one location.  A single-image request (`classic.js` sends only `image`) is answered from that
     view repeated four times: the panorama head averages the four panel embeddings (super_guessr.py:437).
-    encoded=True: the views stay the payloads' bytes, for `predict_panorama` to decode on the GPU."""
+    encoded=True: the views stay the payloads' bytes, for `predict_panorama` to decode on the GPU.
+    A body with the key `panorama` (ONE data URI: an equirectangular image) and optionally `panorama_heading` (compass heading of its
+    centre column, default 0) gives an EquirectRequest instead, answered like a four-image request; together with any of `image` ..
+    `image_4` it is a BadRequest."""
+    if isinstance(body, dict) and PANORAMA_KEY in body:
+        if any(k in body for k in IMAGE_KEYS):
+            raise BadRequest("'panorama' cannot be combined with 'image' .. 'image_4': send the equirectangular image or the four views")
+        heading = body.get("panorama_heading", 0.0)
+        if isinstance(heading, bool) or not isinstance(heading, (int, float)) or heading != heading or abs(heading) == float("inf"):
+            raise BadRequest("'panorama_heading' must be a finite number (degrees)")
+        return EquirectRequest((data_uri_bytes if encoded else decode_data_uri)(body[PANORAMA_KEY]), heading)
     if not isinstance(body, dict) or IMAGE_KEYS[0] not in body:
         raise BadRequest("JSON body with an 'image' field expected")
     views = [(data_uri_bytes if encoded else decode_data_uri)(body[k]) for k in IMAGE_KEYS if body.get(k)]
@@ -70,23 +89,36 @@ def panorama_from_request(body: Dict, encoded: bool = False) -> List:
 
 
 def predict_panorama(views: Sequence, model, refiner=None, preprocess: Optional[Callable] = None, attribution: bool = False) -> Dict:
-    """views: four PIL images -> {'lat', 'lng'} (+ 'geocell_margin', 'geocell_certain', 'reencoded_exact' when the model exposes the
+    """views: four PIL images (or the EquirectRequest of a `panorama` body) -> {'lat', 'lng'} (+ 'geocell_margin', 'geocell_certain', 'reencoded_exact' when the model exposes the
     certainty of its top-1).  `preprocess(list of PIL) -> (4,3,336,336)` defaults to the GPU path.  Views that are all `bytes` (image
     files) go to the same path undecoded: baseline JPEGs are decoded on the GPU (pigeon_amd/jpeg.py: Pillow's pixels, bit for bit),
     anything else by Pillow; a payload neither can read is a BadRequest.  With an injected `preprocess` bytes are decoded first.
     attribution=True adds 'attribution': the top-1 cell against its runner-up as a sum over the views' patches (`model.attribute`,
     pigeon_amd/explain.py `attribution_json`; on the exact tier when this panorama was re-encoded there)."""
     import torch
-    views = list(views)
-    as_bytes = bool(views) and all(isinstance(v, (bytes, bytearray)) for v in views)
-    if as_bytes and preprocess is not None:
-        views = [decode_data_uri(base64.b64encode(bytes(v)).decode()) for v in views]
-    if preprocess is None:
-        from .clip_embedder import gpu_preprocess
-        preprocess = gpu_preprocess
+    if isinstance(views, EquirectRequest):
+        # one equirectangular image: its four views are rendered on the GPU (pigeon_amd/panorama.py) into the buffer the resize reads;
+        # a file's bytes go there as bytes.  The views exist on the device only, so an injected host `preprocess` cannot take them.
+        if preprocess is not None:
+            raise BadRequest("a 'panorama' request is rendered by the GPU preprocessing; this server runs with an injected one")
+        from .panorama import panorama_pixels
+        heading, as_bytes = views.centre_heading, isinstance(views.image, (bytes, bytearray))
+        views = views.image
         if as_bytes:
             from .jpeg import EncodedImages
-            views = EncodedImages(views)
+            views = EncodedImages([bytes(views)])
+        preprocess = lambda source: panorama_pixels(source, centre_heading=heading)        # noqa: E731
+    else:
+        views = list(views)
+        as_bytes = bool(views) and all(isinstance(v, (bytes, bytearray)) for v in views)
+        if as_bytes and preprocess is not None:
+            views = [decode_data_uri(base64.b64encode(bytes(v)).decode()) for v in views]
+        if preprocess is None:
+            from .clip_embedder import gpu_preprocess
+            preprocess = gpu_preprocess
+            if as_bytes:
+                from .jpeg import EncodedImages
+                views = EncodedImages(views)
     try:
         px = preprocess(views)                                     # (4,3,336,336), CLIP-normalised
     except (ValueError, OSError) as e:

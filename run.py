@@ -15,6 +15,8 @@ replaced by seeded synthetic fixtures:  `--synthetic N` embeds / evaluates N syn
   torchrun --nproc-per-node 8 --master-addr 127.0.0.1 run.py embed random --synthetic 4096
   python run.py embed random --synthetic 64 --calibration cal.npz                  # first run writes cal.npz, later runs load it
   python run.py embed saved_models/StreetviewCLIP.model -l data/hf_dataset --exact  # the exact encoder: embeddings for a prototype bank
+  python run.py evaluate saved_models/head.model -l data/hf_pano -b saved_models/StreetviewCLIP.model --raw-images --encoded --equirect
+                                                                                   # one equirectangular file per item: views rendered on the GPU
 """
 import argparse
 import logging
@@ -64,6 +66,10 @@ argp.add_argument('--encoded', action='store_true', default=False,
                   help="with --raw-images: the items' image columns hold FILES (bytes, paths, or a datasets.Image(decode=False) column); the "
                        "workers only read them, baseline JPEGs are decoded on the GPU into the buffer the resize reads (Pillow's pixels, "
                        "bit for bit), anything else by Pillow in the main process; the count of those and why is printed once")
+argp.add_argument('--equirect', action='store_true', default=False,
+                  help="evaluate, with --raw-images: every item's single `image` column holds ONE equirectangular panorama (a file with "
+                       "--encoded); the four 90-degree views at headings 0 / 90 / 180 / 270 are rendered from it on the GPU at "
+                       "round(W / pi) pixels (at least 336) in front of the resize (pigeon_amd/panorama.py)")
 argp.add_argument('--calibration', default=None, metavar='FILE',
                   help="encoder calibration file (bias vector, certainty tolerance, exact-encoder verdict; keyed by the weight "
                        "fingerprint).  If FILE exists it is loaded before the first batch -- every rank loads the same one, nothing is "
@@ -142,6 +148,23 @@ def _jpeg_file(arr, k):
     return {'bytes': buf.getvalue(), 'path': None}
 
 
+class _SyntheticEquirect(_SyntheticImages):
+    """N seeded equirectangular panoramas of two sizes, one `image` column each: raw uint8 arrays, or JPEG files with encoded."""
+    SIZES = ((256, 512), (300, 640))
+
+    def __init__(self, n, encoded=False):
+        super().__init__(n, panorama=True)
+        self.encoded = encoded
+
+    def __getitem__(self, i):
+        if isinstance(i, str):
+            return super().__getitem__(i)
+        g = torch.Generator().manual_seed(8765 + i)
+        h, w = self.SIZES[i % len(self.SIZES)]
+        img = torch.randint(0, 256, (h, w, 3), generator=g, dtype=torch.uint8).numpy()
+        return {'labels': torch.zeros(2, dtype=torch.float64), 'labels_clf': torch.tensor(0), 'image': _jpeg_file(img, i) if self.encoded else img}
+
+
 class _SyntheticEncodedImages(_SyntheticRawPanoramas):
     """N seeded single JPEG files of mixed sizes with an index: `embed --raw-images --encoded --synthetic N`."""
 
@@ -192,6 +215,8 @@ def _print_fallbacks(comm):
 def _dispatch(args, comm):
     if args.encoded and not args.raw_images:
         raise SystemExit('--encoded is a mode of --raw-images')
+    if args.equirect and not (args.raw_images and args.function == 'evaluate'):
+        raise SystemExit('--equirect is a mode of evaluate --raw-images')
     from pigeon_amd import synthetic
     dev = f'cuda:{int(os.environ.get("LOCAL_RANK", "0"))}'
     torch.cuda.set_device(dev)
@@ -235,7 +260,10 @@ def _dispatch(args, comm):
             geocell_path = os.path.join(tmp, 'geocells.csv')
             synthetic.write_geocell_csv(geocell_path, synthetic.make_geocells(args.geocells, seed=0))
             bank = synthetic.make_bank(args.geocells, 20, seed=2, exact_means=False)
-            dataset = _SyntheticRawPanoramas(args.synthetic, args.encoded) if args.raw_images else _SyntheticImages(args.synthetic, panorama=True)
+            if args.equirect:
+                dataset = _SyntheticEquirect(args.synthetic, args.encoded)
+            else:
+                dataset = _SyntheticRawPanoramas(args.synthetic, args.encoded) if args.raw_images else _SyntheticImages(args.synthetic, panorama=True)
         else:
             from datasets import DatasetDict
             dataset = DatasetDict.load_from_disk(args.load[0])
@@ -243,7 +271,7 @@ def _dispatch(args, comm):
                 dataset = dataset['test'] if args.test else dataset['val']
         if args.raw_images:
             from pigeon_amd.evaluate import ImageEvalDataset
-            dataset = ImageEvalDataset(dataset, encoded=args.encoded)
+            dataset = ImageEvalDataset(dataset, encoded=args.encoded, equirect=args.equirect)
         results = evaluate(args.name, dataset, yfcc=args.yfcc, base_model=_vision_model(args), refine=True,
                            landmarks=args.landmarks, geocell_path=geocell_path, bank=bank, heading=args.heading,
                            multi_task=args.multitask, calibration=args.calibration, embedding_rel_tol=args.embedding_rel_tol,
