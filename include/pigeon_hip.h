@@ -52,7 +52,8 @@ extern "C" {
                               *    + pg_jpeg_probe, pg_jpeg_reason, pg_jpeg_plan, pg_jpeg_entropy_decode, pg_jpeg_forward, pg_jpeg_info and
                               *      pg_jpeg_item, additive;
                               *    + pg_token_attribution, additive;
-                              *    + pg_equirect_plan, pg_equirect_forward, pg_eq_view and pg_eq_item, additive) */
+                              *    + pg_equirect_plan, pg_equirect_forward, pg_eq_view and pg_eq_item, additive;
+                              *    + pg_guess_spread, pg_guess_spread_plan, additive) */
 
 const char* pg_last_error(void);
 int pg_abi_version(void);
@@ -700,6 +701,37 @@ int pg_haversine_pairs(const double* x, const void* y, int y_dtype, int64_t N, d
 /* Label smoothing (reference preprocessing/utils.py:7-19): out = exp(-(d - rowmin(d)) / constant), NaN/inf -> 0.
  * distances, out: DEVICE (N,M) fp64 (may alias). */
 int pg_smooth_labels(const double* distances, int N, int M, double constant, double* out, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Guess spread (csrc/spread.hip): how far off a point may be, from the head's logits.  The reference has no code for it; the contract is
+ * this project's own and is restated in tests/_spreadref.py.  Per batch row b and query point g, all arithmetic in float64:
+ *   m   = max_c l[b,c]        w_c = exp((double)l[b,c] - (double)m)        Z = sum_c w_c
+ *   d_c = the km pg_haversine_matrix computes for x = point[b,g] (fp64), y = centroid[c] -- one device function, csrc/haversine.h
+ *   expected_km[b,g]    = (sum_c w_c * d_c) / Z
+ *   expected_score[b,g] = (sum_c w_c * 5000 * exp(-d_c / 1492.7)) / Z         the GeoGuessr score before its rounding
+ *   key_c = d_c + extent_c      extent_c >= 0: how far cell c reaches from its centroid; extent_km == NULL: key_c = d_c
+ *   M(t)  = sum over { c : key_c <= t } of w_c
+ *   radius_km[b,g,j]    = min { key_c : M(key_c) >= quantiles[j] * Z }
+ * radius[j] is the smallest circle around the point that holds, whole, cells carrying quantiles[j] of the probability.  With extent 0
+ * the mass sits at the centroids: a confident head asked about its own centroid gets a radius of (almost) 0, not the cell's size.
+ * Every sum over cells is taken in one fixed order that depends on C only (no atomics): a (row, point)'s outputs are the same bits
+ * alone, inside any batch, at any position, in LDS or in scratch; M(+inf) is the same sequence of additions as Z.  A -inf logit is a
+ * cell of weight 0 (a masked cell).  A NaN or +inf logit, a non-finite point, a row of -inf only, and a key that is not a finite
+ * non-negative number (non-finite centroids or extents) give NaN in every output of that (row, point) and touch no other.
+ * logits DEVICE (B,C) fp32; centroids DEVICE (C,2) fp64 [lng,lat]; extent_km DEVICE (C,) fp64 or NULL; points DEVICE (B,G,2) fp64;
+ * quantiles HOST nq doubles in (0, 1], nq 1 .. 4; expected_km, expected_score DEVICE (B,G) fp64; radius_km DEVICE (B,G,nq) fp64.
+ * B == 0 or G == 0 is a no-op.  PG_EINVAL, naming the argument and before any HIP call, for C < 1, nq outside 1 .. 4, a quantile outside
+ * (0, 1], a negative B or G, B * G > 2^31 - 1 and a null pointer.  C above pg_guess_spread_plan's out[2] takes 16 * B * G * C bytes
+ * of stream-ordered scratch.
+ * ------------------------------------------------------------------------------------------------ */
+int pg_guess_spread(const float* logits, int B, int C, const double* centroids, const double* extent_km, const double* points, int G,
+                    const double* quantiles, int nq, double* expected_km, double* expected_score, double* radius_km, void* stream);
+/* What pg_guess_spread does with C cells (host arithmetic, no GPU; PG_EINVAL for C < 1):
+ *   out[0]  where the cells' (key, weight) pairs live: 0 = LDS, 1 = stream-ordered device scratch (same bits)
+ *   out[1]  bytes of dynamic LDS a workgroup asks for (0 in form 1)
+ *   out[2]  the largest C of form 0
+ *   out[3]  threads of the workgroup; there is one per (row, point) */
+int pg_guess_spread_plan(int C, int32_t out[4]);
 
 /* ------------------------------------------------------------------------------------------------
  * The prototype cluster table (reference dataset_creation/prototype/prototype.py:121-149): per-geocell OPTICS graphs, csrc/optics.hip.

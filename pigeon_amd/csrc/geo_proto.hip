@@ -14,6 +14,7 @@
 //   Both feed the soft-label cross entropy at reference models/super_guessr.py:469-474.
 #include "common.h"
 #include "pigeon_internal.h"
+#include "haversine.h"
 
 #include <cmath>
 
@@ -87,32 +88,14 @@ extern "C" int pg_proto_build(const float* train_emb, int panels, int64_t num_tr
 }
 
 // --------------------------------------------------------------------------------------------- haversine matrix
-// torch.deg2rad multiplies by the double constant pi/180 rounded to the tensor's dtype
-#define DEG2RAD_D 0.017453292519943295769236907684886127134428718885417
-template <typename X> struct Deg;
-template <> struct Deg<double> {
-    static __device__ __forceinline__ double rad(double v) { return v * DEG2RAD_D; }
-    static __device__ __forceinline__ double cosv(double r) { return cos(r); }
-};
-template <> struct Deg<float> {
-    static __device__ __forceinline__ float rad(float v) { return v * (float)DEG2RAD_D; }
-    static __device__ __forceinline__ float cosv(float r) { return (float)cos((double)r); }   // correctly rounded fp32 cos
-};
-
+// the arithmetic (DEG2RAD_D, Deg<X>, pg_haversine_km<X>) lives in haversine.h, shared with spread.hip
 template <typename X>
 __global__ __launch_bounds__(256) void haversine_matrix_kernel(const X* __restrict__ x, const double* __restrict__ y,
                                                                double* __restrict__ out, int N, int M) {
     const int i = blockIdx.y;
     const int j = blockIdx.x * 256 + threadIdx.x;
     if (j >= M) return;
-    const X xlng = Deg<X>::rad(x[2 * i]), xlat = Deg<X>::rad(x[2 * i + 1]);
-    const double ylng = y[2 * j] * DEG2RAD_D, ylat = y[2 * j + 1] * DEG2RAD_D;
-    const double dlng = (double)xlng - ylng, dlat = (double)xlat - ylat;
-    const double p = (double)Deg<X>::cosv(xlat) * cos(ylat);
-    const double s1 = sin(dlat / 2), s0 = sin(dlng / 2);
-    const double a = s1 * s1 + p * (s0 * s0);
-    const double c = 2 * asin(sqrt(a));
-    out[(int64_t)i * M + j] = (6378137.0 * c) / 1000;
+    out[(int64_t)i * M + j] = pg_haversine_km<X>(x[2 * i], x[2 * i + 1], y[2 * j], y[2 * j + 1]);
 }
 
 extern "C" int pg_haversine_matrix(const void* x, int x_dtype, const double* y, int N, int M, double* out, void* stream) {

@@ -76,6 +76,32 @@ def recover_regression_values(values: np.ndarray, yfcc: bool = False, scaler=Non
     return vals - np.array([416 if yfcc else 408, 1, 0, 1, 1, 1]).transpose()
 
 
+def spread_metrics(radius_km, quantiles, distances, expected_km=None, expected_score=None) -> Dict[str, float]:
+    """How the head's probabilities compare with the truth: for every quantile q of `SuperGuessr.spread` (radius_km (N, nq), in the
+    order of `quantiles`) `Radius_<100 q>_coverage`, the share of samples whose true distance (`distances` (N,) km) is at most their
+    radius -- to be read against q: a calibrated head covers q of the samples -- and `Median_radius_<100 q>_km`; with the two
+    expectations also `Mean_expected_km` and `Mean_expected_score`.  A sample whose radius is NaN is not covered."""
+    radius_km, distances = np.asarray(radius_km, dtype=np.float64), np.asarray(distances, dtype=np.float64)
+    if radius_km.ndim != 2 or radius_km.shape != (distances.shape[0], len(quantiles)):
+        raise ValueError(f'spread_metrics: radius_km {radius_km.shape} does not match {distances.shape[0]} samples x {len(quantiles)} quantiles')
+    out = {}
+    for j, q in enumerate(quantiles):
+        tag = f'{100 * float(q):g}'
+        out[f'Radius_{tag}_coverage'] = float(np.mean(distances <= radius_km[:, j]))
+        out[f'Median_radius_{tag}_km'] = float(np.median(radius_km[:, j]))
+    if expected_km is not None:
+        out['Mean_expected_km'] = float(np.mean(np.asarray(expected_km, dtype=np.float64)))
+    if expected_score is not None:
+        out['Mean_expected_score'] = float(np.mean(np.asarray(expected_score, dtype=np.float64)))
+    return out
+
+
+def _final_spread(model: SuperGuessr, st: dict, refined, quantiles):
+    """`model.spread` of a settled state at its FINAL guess: the refined point when there is one (fp32 -> fp64, exact), else the
+    state's own centroid.  Device tensors only."""
+    return model.spread(points=None if refined is None else refined.to(torch.float64), quantiles=quantiles, state=st)
+
+
 def _class_labels(labels) -> np.ndarray:
     labels = np.asarray(labels)
     return np.argmax(labels, axis=-1) if labels.ndim > 1 else labels          # (N, classes) one-hot / probabilities, or (N,) indices
@@ -125,7 +151,8 @@ def compute_geoguessr_metrics(results, scaler=None, countries=None) -> Dict[str,
 
 @torch.no_grad()
 def certain_forward(model: SuperGuessr, refiner: Optional[ProtoRefiner], pixel_values=None, embedding=None, labels=None,
-                    labels_clf=None, labels_multi_task=None, labels_climate=None, labels_month=None, pixel_bytes=None, **_unused):
+                    labels_clf=None, labels_multi_task=None, labels_climate=None, labels_month=None, pixel_bytes=None, spread=None,
+                    **_unused):
     """`model(**data)` followed by `refiner(...)` with the reference's discrete outputs (a z ~ 4 statistical statement for the samples called certain, pigeon_amd/certainty.py): one fast pass, the tolerance of every
     discrete decision downstream of the embedding -- the top-1 cell (pg_head_certainty) and, with a refiner, the winning candidate,
     the candidate-set boundary, the nearest prototype and the farthest member (pg_refine_certainty) -- and ONE exact pass
@@ -139,7 +166,10 @@ def certain_forward(model: SuperGuessr, refiner: Optional[ProtoRefiner], pixel_v
     caller need not run the refiner again; multi-task models: aux_tol (B,) f32 the tolerance of the climate and month argmaxes,
     aux_code (B,) i32 which class sets it -- `head_tol` is already the minimum over the geocell, climate and month decisions).
     `pixel_bytes` (instead of pixel_values / embedding): uint8 (B,12,336,336) or (B,3,336,336) 8-bit pixels (`SuperGuessr.encode_head`);
-    every output and every `info` entry equals what the fp32 pixels `table[bytes]` give."""
+    every output and every `info` entry equals what the fp32 pixels `table[bytes]` give.
+    `spread` (quantiles, e.g. (0.5, 0.9); default None: nothing is computed): adds info['spread'], `SuperGuessr.spread` of the final
+    guess -- the refined point with a refiner, else the top-1 centroid -- from the settled state's logits (re-encoded rows: their
+    exact-tier logits)."""
     if pixel_bytes is not None:
         model._check_pixel_bytes(pixel_bytes, pixel_values, embedding)
     res = model.engine(refiner).submit(pixel_values, embedding, pixel_bytes=pixel_bytes)[0]
@@ -152,6 +182,8 @@ def certain_forward(model: SuperGuessr, refiner: Optional[ProtoRefiner], pixel_v
     if 'aux_tol' in st:
         info['aux_tol'], info['aux_code'] = st['aux_tol'], st['aux_code']
     model.last_certain = info['certain']
+    if spread is not None:
+        info['spread'] = _final_spread(model, st, st.get('refined_LLH') if refiner is not None else None, spread)
     return out, info
 
 
@@ -234,13 +266,17 @@ class ImageEvalDataset:
 
 def evaluate_model(model: SuperGuessr, dataset, metrics: Optional[Callable] = None, train_args=None,
                    refiner: Optional[ProtoRefiner] = None, yfcc: bool = False, writer=None, step: int = 0,
-                   batch_size: Optional[int] = None, num_workers: int = 0):
+                   batch_size: Optional[int] = None, num_workers: int = 0, spread=None):
     """reference training/train_eval_loop.py:35-161 (eval loop :77-112).
 
     dataset items are dicts of forward() keyword arguments (pixel_values | pixel_bytes | embedding, labels, labels_clf, ...), or
     -- an `ImageEvalDataset` -- raw images of any sizes, which are resized to `pixel_bytes` here, a batch at a time on the GPU.
     Returns the dict of concatenated numpy results; if `metrics` is given it is called with the same 11-tuple
     the reference builds (:138-140) and its dict is merged in.
+    `spread` (quantiles, e.g. (0.5, 0.9); default None: nothing is computed): `SuperGuessr.spread` of every finished batch's final
+    guess, from its final state (rows the exact tier re-encoded: their re-encoded logits), on device tensors without a host
+    synchronisation: results['expected_km'], ['expected_score'] (N,), ['radius_km'] (N, nq), ['spread_quantiles']; when the dataset
+    has a `labels` column also `spread_metrics`: Radius_<100 q>_coverage, Median_radius_<100 q>_km, Mean_expected_km / _score.
     """
     from torch.utils.data import DataLoader
     logger.warning('Starting evaluation ...')
@@ -258,6 +294,7 @@ def evaluate_model(model: SuperGuessr, dataset, metrics: Optional[Callable] = No
     combined_loss_mt = [0.0, 0.0, 0.0]                     # reg, climate, month
     multi_task = bool(getattr(model, 'multi_task', False))
     combined_certain = []
+    combined_spread = []
     n_seen = 0
     # The reference's loop (:77-112) computes a batch and appends its predictions; the predictions are only read after the loop
     # (:114-140).  Here a batch's rows that the 16-bit encoder cannot settle are queued on the device and re-encoded by the exact
@@ -290,6 +327,8 @@ def evaluate_model(model: SuperGuessr, dataset, metrics: Optional[Callable] = No
             combined_top5_cells.append(top5.indices)
             combined_top5_probs.append(top5.values)
             combined_certain.append(res['certain'])                              # every output of the sample is the reference's
+            if spread is not None:
+                combined_spread.append(_final_spread(model, res['state'], res['state'].get('refined_LLH') if refiner is not None else None, spread))
             n_seen += outputs.preds_geocell.shape[0]
 
     with torch.no_grad():
@@ -322,6 +361,16 @@ def evaluate_model(model: SuperGuessr, dataset, metrics: Optional[Callable] = No
         results.update(preds_mt=preds_mt, preds_climate=preds_climate, preds_month=preds_month,
                        loss_reg=float(combined_loss_mt[0]) / max(n_seen, 1), loss_climate=float(combined_loss_mt[1]) / max(n_seen, 1),
                        loss_month=float(combined_loss_mt[2]) / max(n_seen, 1))
+    if spread is not None:
+        results.update(expected_km=to_np([s.expected_km for s in combined_spread]), expected_score=to_np([s.expected_score for s in combined_spread]),
+                       radius_km=to_np([s.radius_km for s in combined_spread]), spread_quantiles=tuple(float(q) for q in spread))
+        try:
+            true_lla = np.asarray(dataset['labels'])
+        except (KeyError, IndexError, TypeError, ValueError):
+            true_lla = None                                                       # no labels: the three columns only
+        if true_lla is not None and len(true_lla) == len(preds):
+            results.update(spread_metrics(results['radius_km'], results['spread_quantiles'], haversine_np(preds, true_lla),
+                                          results['expected_km'], results['expected_score']))
     if metrics is not None:                                                       # :122-140
         labels_lla, labels_cell = dataset['labels'], dataset['labels_clf']
         if isinstance(labels_lla, np.ndarray) == False:
@@ -341,7 +390,7 @@ def evaluate(model: str, dataset, yfcc: bool, landmarks: bool, base_model=None, 
              refine: bool = True, geocell_path: Optional[str] = None, proto_path: Optional[str] = None,
              dataset_path=None, bank=None, head_state: Optional[str] = None, multi_task: bool = False,
              calibration: Optional[str] = None, embedding_rel_tol: Optional[float] = None, country_path: Optional[str] = None,
-             bank_rel_tol=None):
+             bank_rel_tol=None, spread=None):
     """reference evaluation/evaluate.py:10-85.
 
     `base_model`: as in the reference a STRING -- config.CLIP_MODEL for the pretrained tower, or the path of a checkpoint whose
@@ -369,6 +418,7 @@ def evaluate(model: str, dataset, yfcc: bool, landmarks: bool, base_model=None, 
     named).  None: what the bank itself records, else exact.
     `country_path`: the GeoJSON of country polygons behind `Country_accuracy` (reference evaluation/metrics.py:17).  None: the file
     config.COUNTRY_PATH names if it exists, else the key is left out as before; a path given explicitly must exist.
+    `spread`: quantiles handed to `evaluate_model(spread=...)`; None (default): no spread is computed.
     """
     import os
     from . import config as cfg
@@ -453,7 +503,7 @@ def evaluate(model: str, dataset, yfcc: bool, landmarks: bool, base_model=None, 
         if refiner.bank_rel_tol > 0:
             print(f'Prototype bank declared at a relative error of {refiner.bank_rel_tol:.3g}: the refiner\'s certainty accounts for it')
     metrics = compute_geoguessr_metrics if countries is None else (lambda r: compute_geoguessr_metrics(r, countries=countries))
-    results = evaluate_model(full_model, dataset, metrics, None, refiner)
+    results = evaluate_model(full_model, dataset, metrics, None, refiner, spread=spread)
     if write_calibration:
         if full_model.base_model is not None and full_model.certainty.calibrated:
             full_model.save_calibration(calibration, source=f'evaluate, first batch, {full_model.certainty.stats.get("samples")} samples')

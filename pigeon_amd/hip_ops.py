@@ -247,6 +247,54 @@ def smooth_labels(distances: torch.Tensor, constant: float) -> torch.Tensor:
     return out
 
 
+# ----------------------------------------------------------------------------------------- guess spread
+def guess_spread(logits: torch.Tensor, centroids: torch.Tensor, points: torch.Tensor, quantiles=(0.5, 0.9),
+                 extent_km: Optional[torch.Tensor] = None, out: Optional[Dict[str, torch.Tensor]] = None):
+    """pg_guess_spread: logits (B,C) fp32, centroids (C,2) fp64 [lng,lat], points (B,2) or (B,G,2) fp64, extent_km (C,) fp64 or None,
+    quantiles 1 .. 4 numbers in (0, 1] -> (expected_km, expected_score, radius_km), fp64, of shape (B,), (B,), (B,nq) for (B,2) points
+    and (B,G), (B,G), (B,G,nq) for (B,G,2) points.  The contract is include/pigeon_hip.h's.  `out` (keys expected_km, expected_score,
+    radius_km) supplies the output tensors; no host synchronisation."""
+    _dev(logits, torch.float32); _shape(logits, "logits", None, None)
+    B, Cn = int(logits.shape[0]), int(logits.shape[1])
+    _dev(centroids, torch.float64); _shape(centroids, "centroids", Cn, 2)
+    _dev(points, torch.float64)
+    flat = points.dim() == 2
+    if flat:
+        _shape(points, "points", B, 2)
+    else:
+        _shape(points, "points", B, None, 2)
+    G = 1 if flat else int(points.shape[1])
+    if extent_km is not None:
+        _dev(extent_km, torch.float64); _shape(extent_km, "extent_km", Cn)
+    for name, t in (("centroids", centroids), ("points", points), ("extent_km", extent_km)):
+        if t is not None and t.device != logits.device:
+            raise _lib.PigeonHipError(f"guess_spread: {name} is on {t.device}, logits on {logits.device}")
+    qs = [float(q) for q in quantiles]
+    if not 1 <= len(qs) <= 4:
+        raise _lib.PigeonHipError(f"guess_spread: quantiles must hold 1 .. 4 numbers, got {len(qs)}")
+    nq = len(qs)
+    shapes = {"expected_km": (B,) if flat else (B, G), "expected_score": (B,) if flat else (B, G),
+              "radius_km": (B, nq) if flat else (B, G, nq)}
+    if out is None:
+        out = {k: torch.empty(s, dtype=torch.float64, device=logits.device) for k, s in shapes.items()}
+    for k, s in shapes.items():
+        _dev(out[k], torch.float64); _shape(out[k], k, *s)
+        if out[k].device != logits.device:
+            raise _lib.PigeonHipError(f"guess_spread: {k} is on {out[k].device}, logits on {logits.device}")
+    qarr = (C.c_double * nq)(*qs)
+    with torch.cuda.device(logits.device):
+        check(load().pg_guess_spread(_p(logits), B, Cn, _p(centroids), _p(extent_km), _p(points), G, qarr, nq, _p(out["expected_km"]),
+                                     _p(out["expected_score"]), _p(out["radius_km"]), _stream()), "pg_guess_spread")
+    return out["expected_km"], out["expected_score"], out["radius_km"]
+
+
+def guess_spread_plan(C_cells: int) -> dict:
+    """pg_guess_spread_plan: where pg_guess_spread keeps the (key, weight) pairs of C cells (host arithmetic, no GPU)."""
+    o = (C.c_int32 * 4)()
+    check(load().pg_guess_spread_plan(int(C_cells), o), "pg_guess_spread_plan")
+    return {"form": int(o[0]), "lds_bytes": int(o[1]), "lds_cells": int(o[2]), "threads": int(o[3])}
+
+
 # ----------------------------------------------------------------------------------------- prototype cluster table
 def _cell_tables(who: str, cell_off: torch.Tensor, mat_off: Optional[torch.Tensor]):
     """The CSR invariants of a packed batch of cells, on the host (the C calls read both tables there): cell_off rises from 0, cell c's

@@ -178,6 +178,26 @@ def exact_state(bank: RegionBank, point, region: int) -> int:
     return INSIDE if parity else OUTSIDE
 
 
+# ---------------------------------------------------------------------------------------------------- cell extents
+def cell_extents_km(bank: RegionBank, centroids) -> np.ndarray:
+    """(R,) fp64 km: the haversine distance (reference preprocessing/geo_utils.py:58-74, R = 6378.137 km) from region r's centroid
+    -- `centroids` (R, 2) [lng, lat] -- to the farthest vertex of its rings; 0 for a region without rings.  Host arithmetic, run once
+    per geocell table: what `SuperGuessr.spread` adds to a cell's distance so that a radius holds the cell whole."""
+    cen = np.ascontiguousarray(np.asarray(centroids), dtype=np.float64)
+    if cen.shape != (len(bank), 2):
+        raise ValueError(f"cell_extents_km: expected ({len(bank)}, 2) centroids, got shape {cen.shape}")
+    out = np.zeros((len(bank),), dtype=np.float64)
+    for r in range(len(bank)):
+        lo, hi = bank.ring_off[bank.region_off[r]], bank.ring_off[bank.region_off[r + 1]]
+        if hi == lo:
+            continue
+        v = np.deg2rad(bank.xy[lo:hi])
+        c = np.deg2rad(cen[r])
+        a = np.sin((c[1] - v[:, 1]) / 2) ** 2 + np.cos(c[1]) * np.cos(v[:, 1]) * np.sin((c[0] - v[:, 0]) / 2) ** 2
+        out[r] = (6378137.0 * (2 * np.arcsin(np.sqrt(np.minimum(a, 1.0))))).max() / 1000
+    return out
+
+
 # ---------------------------------------------------------------------------------------------------- lookups
 def _points(who: str, lnglat, finite: bool) -> np.ndarray:
     pts = np.ascontiguousarray(np.asarray(lnglat), dtype=np.float64)           # fp32 predictions widen exactly

@@ -24,6 +24,7 @@ from typing import Callable, Dict, List, Optional, Sequence
 
 IMAGE_KEYS = ("image", "image_2", "image_3", "image_4")          # duel.js:59-62, in heading order
 PANORAMA_KEY = "panorama"                                        # ours: one equirectangular image instead of the four views
+SPREAD_QUANTILES = (0.5, 0.9)                                    # of `spread=True`: the radii a response carries
 
 
 class BadRequest(ValueError):
@@ -88,14 +89,21 @@ def panorama_from_request(body: Dict, encoded: bool = False):
     return views
 
 
-def predict_panorama(views: Sequence, model, refiner=None, preprocess: Optional[Callable] = None, attribution: bool = False) -> Dict:
+def predict_panorama(views: Sequence, model, refiner=None, preprocess: Optional[Callable] = None, attribution: bool = False,
+                     spread: bool = False) -> Dict:
     """views: four PIL images (or the EquirectRequest of a `panorama` body) -> {'lat', 'lng'} (+ 'geocell_margin', 'geocell_certain', 'reencoded_exact' when the model exposes the
     certainty of its top-1).  `preprocess(list of PIL) -> (4,3,336,336)` defaults to the GPU path.  Views that are all `bytes` (image
     files) go to the same path undecoded: baseline JPEGs are decoded on the GPU (pigeon_amd/jpeg.py: Pillow's pixels, bit for bit),
     anything else by Pillow; a payload neither can read is a BadRequest.  With an injected `preprocess` bytes are decoded first.
     attribution=True adds 'attribution': the top-1 cell against its runner-up as a sum over the views' patches (`model.attribute`,
-    pigeon_amd/explain.py `attribution_json`; on the exact tier when this panorama was re-encoded there)."""
+    pigeon_amd/explain.py `attribution_json`; on the exact tier when this panorama was re-encoded there).
+    spread=True adds how far off the answer may be (`model.spread` at the returned point, SPREAD_QUANTILES): 'expected_km',
+    'expected_score' (the GeoGuessr score before its rounding) and 'radius_km': {"0.5": km, "0.9": km}, the radii of the circles
+    around the answer that hold, whole, cells carrying that share of the head's probability."""
     import torch
+    if spread and not hasattr(model, "spread"):
+        raise ValueError("predict_panorama(spread=True): this model has no `spread` (it needs SuperGuessr.spread)")
+    sp = None
     if isinstance(views, EquirectRequest):
         # one equirectangular image: its four views are rendered on the GPU (pigeon_amd/panorama.py) into the buffer the resize reads;
         # a file's bytes go there as bytes.  The views exist on the device only, so an injected host `preprocess` cannot take them.
@@ -131,7 +139,8 @@ def predict_panorama(views: Sequence, model, refiner=None, preprocess: Optional[
             # pigeon_amd.SuperGuessr: the same call with the certainty of every discrete output (top-1 cell AND what the refiner below
             # will pick) checked, and the panorama re-encoded in the exact mode if it is not certain (exact_top1, the default)
             from .evaluate import certain_forward
-            out, info = certain_forward(model, refiner, pixel_values=px)
+            out, info = certain_forward(model, refiner, pixel_values=px, spread=SPREAD_QUANTILES if spread else None)
+            sp = info.get("spread")
             pred_llh, topk, embedding = out[0], out[1], out[-1]    # multi-task models put preds_mt in between (:463-464)
             if refiner is not None:
                 pred_llh = info["refined_LLH"]                     # the refinement certain_forward ran (once; re-run for re-encoded rows)
@@ -141,6 +150,8 @@ def predict_panorama(views: Sequence, model, refiner=None, preprocess: Optional[
             if refiner is not None:
                 _, pred_llh, _ = refiner(embedding=embedding, initial_preds=pred_llh, candidate_cells=topk.indices,
                                          candidate_probs=topk.values)
+            if spread:
+                sp = model.spread(points=pred_llh.reshape(-1, 2).to(torch.float64), quantiles=SPREAD_QUANTILES)
     lng, lat = (float(v) for v in pred_llh.reshape(-1, 2)[0].tolist())
     res = {"lat": lat, "lng": lng}
     # certainty of the geocell top-1 (pigeon_amd.SuperGuessr, round 4): extra keys, the extension reads lat / lng only
@@ -148,6 +159,10 @@ def predict_panorama(views: Sequence, model, refiner=None, preprocess: Optional[
         res["geocell_margin"] = float(model.last_margin.reshape(-1)[0])
         res["geocell_certain"] = bool(model.last_certain.reshape(-1)[0])
         res["reencoded_exact"] = bool(getattr(model, "last_reencoded", None) is not None and model.last_reencoded.numel() > 0)
+    if sp is not None:                                             # extra keys as well: the extension reads lat / lng only
+        res["expected_km"] = float(sp.expected_km.reshape(-1)[0])
+        res["expected_score"] = float(sp.expected_score.reshape(-1)[0])
+        res["radius_km"] = {f"{q:g}": float(r) for q, r in zip(sp.quantiles, sp.radius_km.reshape(-1, len(sp.quantiles))[0].tolist())}
     if attribution:
         from .explain import attribution_json
         with torch.no_grad():
@@ -156,9 +171,13 @@ def predict_panorama(views: Sequence, model, refiner=None, preprocess: Optional[
     return res
 
 
-def make_app(model, refiner=None, preprocess: Optional[Callable] = None, game_log: Optional[List] = None, encoded: bool = False):
+def make_app(model, refiner=None, preprocess: Optional[Callable] = None, game_log: Optional[List] = None, encoded: bool = False,
+             spread: bool = False):
     """Starlette application with the two routes the extension calls.  encoded=True: the payloads are handed on as bytes and decoded
-    on the GPU (see predict_panorama); the response is the same."""
+    on the GPU (see predict_panorama); the response is the same.  spread=True: every answer carries 'expected_km', 'expected_score'
+    and 'radius_km' (see predict_panorama); a model without `spread` is refused here, not per request."""
+    if spread and not hasattr(model, "spread"):
+        raise ValueError("make_app(spread=True): this model has no `spread` (it needs SuperGuessr.spread)")
     from starlette.applications import Starlette
     from starlette.responses import JSONResponse
     from starlette.routing import Route
@@ -176,7 +195,7 @@ def make_app(model, refiner=None, preprocess: Optional[Callable] = None, game_lo
         # called inline on the event loop, on purpose: the handles behind `model` are one per (device, stream) and not
         # thread-safe, so requests are answered one at a time -- a `def` handler would run in Starlette's pool
         try:
-            res = predict_panorama(views, model, refiner, preprocess, attribution=attribution)
+            res = predict_panorama(views, model, refiner, preprocess, attribution=attribution, spread=spread)
         except BadRequest as e:                                    # (encoded mode: the payloads are only decoded in there)
             return JSONResponse({"error": str(e)}, status_code=400)
         return JSONResponse({"gameID": body.get("gameID"), "roundID": body.get("roundID"), "results": res})
@@ -195,7 +214,7 @@ def make_app(model, refiner=None, preprocess: Optional[Callable] = None, game_lo
 
 
 def main(argv=None):
-    """python -m pigeon_amd.serve --head <head.model> [--geocells <csv>] [--protos <csv> --dataset <dir>] [--calibration <file>] [--port 5000]"""
+    """python -m pigeon_amd.serve --head <head.model> [--geocells <csv>] [--protos <csv> --dataset <dir>] [--calibration <file>] [--spread] [--port 5000]"""
     import os
     ap = _arg_parser()
     args = ap.parse_args(argv)
@@ -223,7 +242,7 @@ def main(argv=None):
               f"{model.certainty.describe()}")
     refiner = ProtoRefiner(proto_path=args.protos, dataset_path=args.dataset) if args.protos else None
     torch.cuda.synchronize()
-    uvicorn.run(make_app(model, refiner, encoded=args.encoded), host=args.host, port=args.port)
+    uvicorn.run(make_app(model, refiner, encoded=args.encoded, spread=args.spread), host=args.host, port=args.port)
 
 
 def _arg_parser():
@@ -240,6 +259,9 @@ def _arg_parser():
     ap.add_argument("--encoded", action="store_true", default=False,
                     help="hand the requests' payloads on as bytes: baseline JPEGs are decoded on the GPU into the buffer the resize reads "
                          "(the same pixels as Pillow's), anything else by Pillow as before")
+    ap.add_argument("--spread", action="store_true", default=False,
+                    help="add to every answer how far off it may be: expected_km, expected_score and radius_km {\"0.5\", \"0.9\"} "
+                         "(SuperGuessr.spread at the returned point); the extension reads lat / lng only")
     ap.add_argument("--host", default="127.0.0.1")
     ap.add_argument("--port", type=int, default=5000)
     ap.add_argument("--calibration", default=None, metavar="FILE",

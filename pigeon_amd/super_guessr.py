@@ -31,6 +31,8 @@ from .utils import ModelOutput, TopK, resolve_name
 MultiTaskPredictions = namedtuple('MultiTaskPredictions', 'loss_reg preds_mt loss_climate preds_climate loss_month preds_month')
 # what `SuperGuessr.attribute` returns: maps (B,P,577,K), offset (B,K), cells (B,K), against (B,), logits (B,K)
 Attribution = namedtuple('Attribution', 'maps offset cells against logits')
+# what `SuperGuessr.spread` returns: expected_km (B,) / (B,G), expected_score likewise, radius_km (B,nq) / (B,G,nq), the quantiles
+Spread = namedtuple('Spread', 'expected_km expected_score radius_km quantiles')
 NUM_MULTI_TASK_VARIABLES = 6
 REGRESSION_LOSS_SCALING = 8
 NUM_CLIMATES = 28
@@ -123,6 +125,8 @@ class SuperGuessr(nn.Module):
             geocell_path = GEOCELL_PATH_YFCC if self.yfcc else GEOCELL_PATH
         self.lla_geocells = self.load_geocells(geocell_path)
         self.num_cells = self.lla_geocells.size(0)
+        # how far every cell reaches from its centroid, km (`spread`): not persistent, the state dict keeps the reference's keys
+        self.register_buffer('cell_extent_km', self.load_cell_extents(geocell_path), persistent=False)
         self.input_dim = self.hidden_size
 
         self.cell_layer = nn.Linear(self.input_dim, self.num_cells)
@@ -199,6 +203,19 @@ class SuperGuessr(nn.Module):
         geo_df = pd.read_csv(path)
         lla_coords = torch.tensor(np.ascontiguousarray(geo_df[['lng', 'lat']].values))
         return nn.parameter.Parameter(data=lla_coords, requires_grad=False)
+
+    def load_cell_extents(self, path: str) -> Tensor:
+        """(C,) float64 km: with a `polygon` column (the one `RegionBank.from_geocell_csv` reads) the haversine distance from every
+        cell's centroid to its farthest ring vertex, computed once on the host (pigeon_amd.regions.cell_extents_km); zeros without."""
+        centroids = self.lla_geocells.data.cpu().numpy()
+        if 'polygon' not in pd.read_csv(path, nrows=0).columns:
+            return torch.zeros((centroids.shape[0],), dtype=torch.float64)
+        from .regions import RegionBank, cell_extents_km
+        try:
+            return torch.from_numpy(cell_extents_km(RegionBank.from_geocell_csv(path), centroids))
+        except ValueError as why:                        # a table whose polygons do not parse still serves every other entry point
+            print(f'Cell extents: the `polygon` column of {path} could not be read ({why}); using 0 km')
+            return torch.zeros((centroids.shape[0],), dtype=torch.float64)
 
     def load_state(self, path: str):
         """reference models/super_guessr.py:222-238: name-wise copy of a saved state dict"""
@@ -518,6 +535,26 @@ class SuperGuessr(nn.Module):
             z = lambda *s, dt=torch.float32: torch.zeros(s, dtype=dt, device=dev)
             return Attribution(z(0, P, 577, k), z(0, k), z(0, k, dt=torch.int64), z(0, dt=torch.int64), z(0, k))
         return Attribution(*(torch.cat([p[i] for p in parts]) if len(parts) > 1 else parts[0][i] for i in range(5)))
+
+    @torch.no_grad()
+    def spread(self, points: Tensor = None, quantiles=(0.5, 0.9), state: dict = None) -> Spread:
+        """How far off a guess may be (pg_guess_spread; contract: include/pigeon_hip.h), from the geocell logits of `state` -- default
+        `last_state`, what the last forward left behind, with re-encoded rows carrying their exact-tier logits.
+          points     (B,2) or (B,G,2) [lng, lat], G candidate guesses per sample; None: the state's own `preds_LLH`
+          quantiles  1 .. 4 numbers in (0, 1]
+        Returns Spread(expected_km, expected_score, radius_km, quantiles), float64 device tensors: under the head's softmax, the expected
+        distance in km and the expected GeoGuessr score (before its rounding) of each point, and per quantile q the radius of the
+        smallest circle around the point that holds, whole, cells carrying q of the probability.  "Whole" counts a cell at its
+        centroid's distance plus `cell_extent_km`; without a `polygon` column the extents are 0, the mass sits at the centroids, and a
+        confident head asked about its own centroid gets a radius of 0 (to the distance kernel's 1e-11 km), not the cell's size.
+        Nothing is synchronised; nothing is computed unless this is called."""
+        st = self.last_state if state is None else state
+        if st is None:
+            raise RuntimeError('SuperGuessr.spread: no state -- run a forward first, or pass `state`')
+        logits = st['logits']
+        pts = st['preds_LLH'] if points is None else torch.as_tensor(points).to(logits.device, torch.float64)
+        ek, es, rk = hip_ops.guess_spread(logits, self.lla_geocells.data, pts.contiguous(), quantiles, extent_km=self.cell_extent_km)
+        return Spread(ek, es, rk, tuple(float(q) for q in quantiles))
 
     def _publish(self, st: dict) -> None:
         if 'certain' not in st:                          # a state straight from `encode_head` (no engine behind it)

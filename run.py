@@ -94,6 +94,10 @@ argp.add_argument('--bank-rel-tol', dest='bank_rel_tol', default=None, metavar='
                        "the loaded tower's ends the run).  Default: what the bank records, else exact")
 
 
+argp.add_argument('--spread', action='store_true', default=False,
+                  help="evaluate: how far off every guess may be (SuperGuessr.spread: expected km, expected GeoGuessr score, the radii "
+                       "holding 0.5 and 0.9 of the head's probability) and, against the labels, how often the truth lies inside them "
+                       "(Radius_50_coverage / Radius_90_coverage, to be read against 0.5 and 0.9)")
 argp.add_argument('--countries', default=None, metavar='FILE',
                   help="evaluate: GeoJSON of country polygons (Polygon / MultiPolygon features) for `Country_accuracy`; default: "
                        "config.COUNTRY_PATH if that file exists, else the key is left out")
@@ -275,10 +279,15 @@ def _dispatch(args, comm):
         results = evaluate(args.name, dataset, yfcc=args.yfcc, base_model=_vision_model(args), refine=True,
                            landmarks=args.landmarks, geocell_path=geocell_path, bank=bank, heading=args.heading,
                            multi_task=args.multitask, calibration=args.calibration, embedding_rel_tol=args.embedding_rel_tol,
-                           country_path=args.countries, bank_rel_tol=args.bank_rel_tol)
+                           country_path=args.countries, bank_rel_tol=args.bank_rel_tol, spread=(0.5, 0.9) if args.spread else None)
         _print_fallbacks(comm)
         if comm.is_main_process:
             print({k: (v if not hasattr(v, 'shape') or v.shape == () else tuple(v.shape)) for k, v in results.items() if k != 'exact_passes'})
+            if 'Radius_50_coverage' in results:
+                print(f"spread: the 50 % radius (median {results['Median_radius_50_km']:.1f} km) holds the truth for "
+                      f"{results['Radius_50_coverage']:.1%} of the samples, the 90 % radius (median {results['Median_radius_90_km']:.1f} km) "
+                      f"for {results['Radius_90_coverage']:.1%}; mean expected error {results['Mean_expected_km']:.1f} km, mean expected "
+                      f"score {results['Mean_expected_score']:.0f}")
             if 'geocell_certain' in results:
                 # beyond the reference's output: how many samples' discrete outputs are certain to be the fp32 reference's (a z ~ 4
                 # statistical statement, pigeon_amd/certainty.py), and how many are near-ties of the reference itself
