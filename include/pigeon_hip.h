@@ -53,7 +53,8 @@ extern "C" {
                               *      pg_jpeg_item, additive;
                               *    + pg_token_attribution, additive;
                               *    + pg_equirect_plan, pg_equirect_forward, pg_eq_view and pg_eq_item, additive;
-                              *    + pg_guess_spread, pg_guess_spread_plan, additive) */
+                              *    + pg_guess_spread, pg_guess_spread_plan, additive;
+                              *    + pg_head_train_loss, pg_head_train_update, pg_head_train_plan, additive) */
 
 const char* pg_last_error(void);
 int pg_abi_version(void);
@@ -732,6 +733,61 @@ int pg_guess_spread(const float* logits, int B, int C, const double* centroids, 
  *   out[2]  the largest C of form 0
  *   out[3]  threads of the workgroup; there is one per (row, point) */
 int pg_guess_spread_plan(int C, int32_t out[4]);
+
+/* ------------------------------------------------------------------------------------------------
+ * Training the geocell head on embeddings (csrc/head_train.hip): one step of cell_layer = Linear(1024 -> C) under the reference's
+ * loss (models/super_guessr.py:469-474: CrossEntropyLoss against haversine-smoothed or one-hot targets) and torch.optim.AdamW,
+ * as two stream-ordered calls.  Restated in tests/_trainref.py.
+ *
+ * pg_head_train_loss.  emb DEVICE (B,P,1024) fp32, P = 1 or 4; W DEVICE (C,1024) fp32; bias DEVICE (C,) fp32; centroids DEVICE (C,2)
+ * fp64 [lng,lat] (may be NULL without labels_llh); labels_llh DEVICE (B,2) fp64 [lng,lat] or NULL; labels_clf DEVICE (B,) int64 or
+ * NULL (read only when labels_llh is NULL; one of the two is needed).  Outputs: xbar DEVICE (B,1024) fp32, g DEVICE (B,C) fp32,
+ * loss_rows DEVICE (B,) fp64, logits DEVICE (B,C) fp32 or NULL.
+ *   xbar[b,j]  = (((0.f + emb[b,0,j]) + emb[b,1,j]) + ...) * (1.0f / P)
+ *   logit[b,c] = the fmaf chain over j = 0 .. 1023 ascending from 0.f of xbar[b,j] * W[c,j], then + bias[c]
+ * -- pg_head_forward's arithmetic: the logits a head is trained on are the bits inference computes.  Then per row, in fp64 from the
+ * fp32 logits l_c, one workgroup per row:
+ *   targets  labels_llh given: d_c = the km pg_haversine_matrix computes for x = labels_llh[b] (fp64), y = centroid[c];
+ *                              y_c = exp(-(d_c - min_c d_c) / tau), a non-finite y_c is 0 (pg_smooth_labels)
+ *            else:             y_c = (c == labels_clf[b]), a comparison
+ *   S = sum_c y_c     m = max_c l_c     e_c = exp(l_c - m)     Z = sum_c e_c     T = sum_c y_c * l_c (fused multiply-add)
+ *   loss_rows[b] = S * (m + log(Z)) - T
+ *   g[b,c]       = (float)(((S * e_c) / Z - y_c) * grad_scale)
+ * (the factor S: smoothed targets do not sum to 1 and CrossEntropyLoss with probability targets does not normalise them).  Every sum
+ * over cells is taken in one fixed order that depends on C only (thread-strided ascending, wave butterfly, waves pairwise; no
+ * atomics): a row's outputs are the same bits alone, inside any batch, at any position, with the targets in LDS or in scratch.
+ * A row whose label point is not finite, or whose labels_clf is outside [0, C), gets loss_rows[b] = NaN and a zero g row: it does not
+ * train and touches nothing else.  No input value forms an address or bounds a loop; non-finite embeddings or weights propagate as
+ * in torch.  C above pg_head_train_plan's out[2] takes 8 * B * C bytes of stream-ordered scratch.
+ * B == 0 is a no-op.  PG_EINVAL, naming the argument and before any HIP call: B < 0, C < 1, P not 1 or 4, tau not finite and
+ * positive, grad_scale not finite, a null pointer.
+ *
+ * pg_head_train_update.  g (B,C), xbar (B,1024): what pg_head_train_loss wrote.  W (C,1024), bias (C,), m_W, v_W (C,1024), m_b, v_b
+ * (C,): DEVICE fp32, updated in place.  dW_out (C,1024), db_out (C,): DEVICE fp32 or NULL.
+ *   dW[c,j] = the fmaf chain over b = 0 .. B-1 ascending from 0.f of g[b,c] * xbar[b,j];  db[c] = (((0.f + g[0,c]) + g[1,c]) + ...)
+ * -- no split over b, no atomics, each (cell tile, column tile) produced whole by one workgroup -- and, from the accumulators,
+ * torch.optim.AdamW's update of every element (w, m, v) with its gradient d, each line one correctly rounded fp32 operation or fma:
+ *   w1 = w * decay;   m' = fma(omb1, d, b1 * m);   v' = fma(omb2, d * d, b2 * v);   q = sqrt(v') / bc2s + eps;
+ *   w' = fma(-step_size, m' / q, w1)
+ * with the scalars computed on the host in double and rounded to fp32: decay = 1 - lr * weight_decay, b1 = beta1, omb1 = 1 - beta1,
+ * b2 = beta2, omb2 = 1 - beta2, step_size = lr / (1 - beta1^step), bc2s = sqrt(1 - beta2^step), eps.  No gradient buffer exists
+ * unless dW_out / db_out is given.  W is written here only, in a launch after the one that read it: stream order is the only
+ * synchronisation the two calls need.
+ * B == 0 is a no-op.  PG_EINVAL, naming the argument and before any HIP call: B < 0, C < 1, step < 1, lr or eps not finite and
+ * positive, a beta outside [0, 1), weight_decay negative or not finite, a null pointer.
+ * ------------------------------------------------------------------------------------------------ */
+int pg_head_train_loss(const float* emb, int B, int P, const float* W, const float* bias, const double* centroids, int C,
+                       const double* labels_llh, const int64_t* labels_clf, double tau, double grad_scale, float* xbar, float* g,
+                       double* loss_rows, float* logits, void* stream);
+int pg_head_train_update(const float* g, const float* xbar, int B, int C, float* W, float* bias, float* m_W, float* v_W, float* m_b,
+                         float* v_b, int64_t step, double lr, double beta1, double beta2, double eps, double weight_decay, float* dW_out,
+                         float* db_out, void* stream);
+/* What pg_head_train_loss does with C cells (host arithmetic, no GPU; PG_EINVAL for C < 1):
+ *   out[0]  where a row's targets live: 0 = LDS, 1 = stream-ordered device scratch (same bits)
+ *   out[1]  bytes of dynamic LDS a workgroup asks for (0 in form 1)
+ *   out[2]  the largest C of form 0
+ *   out[3]  threads of the workgroup; there is one per row */
+int pg_head_train_plan(int C, int32_t out[4]);
 
 /* ------------------------------------------------------------------------------------------------
  * The prototype cluster table (reference dataset_creation/prototype/prototype.py:121-149): per-geocell OPTICS graphs, csrc/optics.hip.

@@ -163,6 +163,9 @@ SIGNATURES = {
     "pg_region_plan": (_I, [C.POINTER(RegionBankStruct), C.POINTER(C.c_int32)]),
     "pg_tune_region_wave_edges": (_I, [_I]),
     "pg_head_forward": (_I, [_P, _I, _I, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P]),
+    "pg_head_train_loss": (_I, [_P, _I, _I, _P, _P, _P, _I, _P, _P, _D, _D, _P, _P, _P, _P, _P]),
+    "pg_head_train_update": (_I, [_P, _P, _I, _I, _P, _P, _P, _P, _P, _P, _I64, _D, _D, _D, _D, _D, _P, _P, _P]),
+    "pg_head_train_plan": (_I, [_I, C.POINTER(C.c_int32)]),
     "pg_head_margin": (_I, [_P, _I, _I, _P, _I, _P, _P, _P, _P, _P]),
     "pg_head_certainty": (_I, [_P, _I, _I, _P, _I, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P]),
     "pg_aux_heads_forward": (_I, [_P, _I, _I, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P]),

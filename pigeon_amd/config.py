@@ -1,5 +1,7 @@
-"""Constants of the hot path, same names and values as reference config.py:1-92 (the reference's
-`TrainingArguments` blocks, config.py:94-177, are training configuration and out of scope)."""
+"""Constants of the hot path, same names and values as reference config.py:1-92, and `TrainArgs` / `TRAIN_ARGS`: the fields of
+the reference's `TRAIN_ARGS` (config.py:94-109) that the head-training loop of pigeon_amd/train.py reads.  The other
+`TrainingArguments` blocks (config.py:111-177) configure training of the vision tower and are out of scope."""
+from dataclasses import dataclass
 
 # OpenAI's pretrained implementation (reference config.py:6-7)
 CLIP_MODEL = 'openai/clip-vit-large-patch14-336'
@@ -49,3 +51,20 @@ OPENAI_CLIP_STD = [0.26862954, 0.26130258, 0.27577711]
 # Geoguessr score decay (reference config.py:52) and haversine label smoothing (config.py:55)
 DECAY_CONSTANT = 1492.7
 LABEL_SMOOTHING_CONSTANT = 65  # (PIGEOTTO), 75 (PIGEON)
+
+
+@dataclass
+class TrainArgs:
+    """What `pigeon_amd.train.train_model` reads from its `train_args` (any object with these fields will do; transformers'
+    TrainingArguments is one).  The defaults are the values of the reference's TRAIN_ARGS (config.py:94-109)."""
+    output_dir: str = 'saved_models'
+    per_device_train_batch_size: int = 256
+    per_device_eval_batch_size: int = 256
+    num_train_epochs: int = 1000
+    learning_rate: float = 2e-5
+    logging_steps: int = 1
+    gradient_accumulation_steps: int = 1
+    seed: int = 330
+
+
+TRAIN_ARGS = TrainArgs()

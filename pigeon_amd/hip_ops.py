@@ -295,6 +295,99 @@ def guess_spread_plan(C_cells: int) -> dict:
     return {"form": int(o[0]), "lds_bytes": int(o[1]), "lds_cells": int(o[2]), "threads": int(o[3])}
 
 
+# ----------------------------------------------------------------------------------------- training the head
+def _same_device(who: str, ref_name: str, ref: torch.Tensor, **tensors):
+    for name, t in tensors.items():
+        if t is not None and t.device != ref.device:
+            raise _lib.PigeonHipError(f"{who}: {name} is on {t.device}, {ref_name} on {ref.device}")
+
+
+def head_train_loss(emb: torch.Tensor, W: torch.Tensor, bias: torch.Tensor, centroids: Optional[torch.Tensor],
+                    labels_llh: Optional[torch.Tensor] = None, labels_clf: Optional[torch.Tensor] = None, tau: float = 75.0,
+                    grad_scale: float = 1.0, out: Optional[Dict[str, torch.Tensor]] = None, want_logits: bool = False):
+    """pg_head_train_loss: emb (B,P,1024) or (B,1024) fp32 with P = 1 or 4, W (C,1024) fp32, bias (C,) fp32, centroids (C,2) fp64
+    [lng,lat], labels_llh (B,2) fp64 (smoothed targets) or else labels_clf (B,) int64 (one-hot targets) -> dict of xbar (B,1024) fp32,
+    g (B,C) fp32 (the gradient over the logits times grad_scale), loss_rows (B,) fp64 and, with want_logits or an `out` that holds
+    one, logits (B,C) fp32.  The contract is include/pigeon_hip.h's.  `out` supplies the output tensors; no host synchronisation."""
+    who = "head_train_loss"
+    _dev(emb, torch.float32)
+    if emb.dim() == 2:
+        _shape(emb, "emb", None, HIDDEN)
+        P = 1
+    else:
+        _shape(emb, "emb", None, None, HIDDEN)
+        P = int(emb.shape[1])
+    if P not in (1, 4):
+        raise _lib.PigeonHipError(f"{who}: emb holds {P} panels per sample; 1 or 4 expected")
+    B = int(emb.shape[0])
+    _dev(W, torch.float32); _shape(W, "W", None, HIDDEN)
+    Cn = int(W.shape[0])
+    _dev(bias, torch.float32); _shape(bias, "bias", Cn)
+    if labels_llh is None and labels_clf is None:
+        raise _lib.PigeonHipError(f"{who}: one of labels_llh and labels_clf is needed")
+    if labels_llh is not None:
+        if centroids is None:
+            raise _lib.PigeonHipError(f"{who}: smoothed targets need centroids")
+        _dev(labels_llh, torch.float64); _shape(labels_llh, "labels_llh", B, 2)
+        labels_clf = None
+    else:
+        _dev(labels_clf, torch.int64); _shape(labels_clf, "labels_clf", B)
+    if centroids is not None:
+        _dev(centroids, torch.float64); _shape(centroids, "centroids", Cn, 2)
+    _same_device(who, "emb", emb, W=W, bias=bias, centroids=centroids, labels_llh=labels_llh, labels_clf=labels_clf)
+    shapes = {"xbar": ((B, HIDDEN), torch.float32), "g": ((B, Cn), torch.float32), "loss_rows": ((B,), torch.float64)}
+    if want_logits or (out is not None and "logits" in out):
+        shapes["logits"] = ((B, Cn), torch.float32)
+    if out is None:
+        out = {}
+    res = {}
+    for k, (s, dt) in shapes.items():
+        t = out.get(k)
+        if t is None:
+            t = torch.empty(s, dtype=dt, device=emb.device)
+        _dev(t, dt); _shape(t, k, *s)
+        _same_device(who, "emb", emb, **{k: t})
+        res[k] = t
+    with torch.cuda.device(emb.device):
+        check(load().pg_head_train_loss(_p(emb), B, P, _p(W), _p(bias), _p(centroids), Cn, _p(labels_llh), _p(labels_clf), float(tau),
+                                        float(grad_scale), _p(res["xbar"]), _p(res["g"]), _p(res["loss_rows"]), _p(res.get("logits")),
+                                        _stream()), "pg_head_train_loss")
+    return res
+
+
+def head_train_update(g: torch.Tensor, xbar: torch.Tensor, W: torch.Tensor, bias: torch.Tensor, m_W: torch.Tensor, v_W: torch.Tensor,
+                      m_b: torch.Tensor, v_b: torch.Tensor, step: int, lr: float = 2e-5, beta1: float = 0.9, beta2: float = 0.999,
+                      eps: float = 1e-8, weight_decay: float = 0.01, dW_out: Optional[torch.Tensor] = None,
+                      db_out: Optional[torch.Tensor] = None) -> None:
+    """pg_head_train_update: g (B,C), xbar (B,1024) as pg_head_train_loss wrote them; W, m_W, v_W (C,1024) and bias, m_b, v_b (C,)
+    fp32, updated IN PLACE through their raw pointers by torch.optim.AdamW's rule (the caller bumps version counters); dW_out (C,1024)
+    / db_out (C,) fp32 receive the gradient when given.  The contract is include/pigeon_hip.h's.  No host synchronisation."""
+    who = "head_train_update"
+    _dev(g, torch.float32); _shape(g, "g", None, None)
+    B, Cn = int(g.shape[0]), int(g.shape[1])
+    _dev(xbar, torch.float32); _shape(xbar, "xbar", B, HIDDEN)
+    for name, t in (("W", W), ("m_W", m_W), ("v_W", v_W)):
+        _dev(t, torch.float32); _shape(t, name, Cn, HIDDEN)
+    for name, t in (("bias", bias), ("m_b", m_b), ("v_b", v_b)):
+        _dev(t, torch.float32); _shape(t, name, Cn)
+    if dW_out is not None:
+        _dev(dW_out, torch.float32); _shape(dW_out, "dW_out", Cn, HIDDEN)
+    if db_out is not None:
+        _dev(db_out, torch.float32); _shape(db_out, "db_out", Cn)
+    _same_device(who, "g", g, xbar=xbar, W=W, bias=bias, m_W=m_W, v_W=v_W, m_b=m_b, v_b=v_b, dW_out=dW_out, db_out=db_out)
+    with torch.cuda.device(g.device):
+        check(load().pg_head_train_update(_p(g), _p(xbar), B, Cn, _p(W), _p(bias), _p(m_W), _p(v_W), _p(m_b), _p(v_b), int(step), float(lr),
+                                          float(beta1), float(beta2), float(eps), float(weight_decay), _p(dW_out), _p(db_out), _stream()),
+              "pg_head_train_update")
+
+
+def head_train_plan(C_cells: int) -> dict:
+    """pg_head_train_plan: where pg_head_train_loss keeps a row's targets for C cells (host arithmetic, no GPU)."""
+    o = (C.c_int32 * 4)()
+    check(load().pg_head_train_plan(int(C_cells), o), "pg_head_train_plan")
+    return {"form": int(o[0]), "lds_bytes": int(o[1]), "lds_cells": int(o[2]), "threads": int(o[3])}
+
+
 # ----------------------------------------------------------------------------------------- prototype cluster table
 def _cell_tables(who: str, cell_off: torch.Tensor, mat_off: Optional[torch.Tensor]):
     """The CSR invariants of a packed batch of cells, on the host (the C calls read both tables there): cell_off rises from 0, cell c's
