@@ -54,7 +54,8 @@ extern "C" {
                               *    + pg_token_attribution, additive;
                               *    + pg_equirect_plan, pg_equirect_forward, pg_eq_view and pg_eq_item, additive;
                               *    + pg_guess_spread, pg_guess_spread_plan, additive;
-                              *    + pg_head_train_loss, pg_head_train_update, pg_head_train_plan, additive) */
+                              *    + pg_head_train_loss, pg_head_train_update, pg_head_train_plan, additive;
+                              *    + pg_score_table, pg_guess_best, pg_guess_best_plan, additive) */
 
 const char* pg_last_error(void);
 int pg_abi_version(void);
@@ -733,6 +734,47 @@ int pg_guess_spread(const float* logits, int B, int C, const double* centroids, 
  *   out[2]  the largest C of form 0
  *   out[3]  threads of the workgroup; there is one per (row, point) */
 int pg_guess_spread_plan(int C, int32_t out[4]);
+
+/* ------------------------------------------------------------------------------------------------
+ * The guess by expected score (csrc/guess_best.hip): of M candidate points shared by the batch, the one whose expectation under the
+ * head's softmax is best.  The reference has no code for it (layers/hedge.py opens with a TODO); the contract is this project's own
+ * and is restated in tests/_bestref.py.
+ *
+ * pg_score_table.  candidates DEVICE (M,2) fp64 [lng,lat]; centroids DEVICE (C,2) fp64; table DEVICE (M,C) fp64, candidate-major:
+ *   d = the km pg_haversine_matrix computes for x = candidates[j] (fp64), y = centroids[c] -- one device function, csrc/haversine.h
+ *   kind 0 (km):     table[j,c] = d
+ *   kind 1 (score):  table[j,c] = 5000.0 * exp(-d / 1492.7)                     the GeoGuessr score before its rounding
+ * A non-finite candidate or centroid gives NaN entries.  M == 0 is a no-op.  PG_EINVAL, naming the argument and before any HIP call,
+ * for C < 1, a negative M, a kind other than 0 and 1, M * C beyond one launch (2^39 elements) and a null pointer.
+ *
+ * pg_guess_best.  logits DEVICE (B,C) fp32; table DEVICE (M,C) fp64 (any values: pg_score_table's, or the caller's own);
+ * best_idx DEVICE (B,) int32; best_value DEVICE (B,) fp64; expected DEVICE (B,M) fp64 or NULL.  Per row b, all in float64:
+ *   m = max_c l[b,c]      w_c = exp((double)l[b,c] - (double)m)      Z = sum_c w_c         pg_guess_spread's weights and Z, the same bits
+ *   E[b,j]        = (sum_c w_c * table[j,c]) / Z
+ *   best_idx[b]   = the smallest j whose E[b,j] equals max_j E[b,j] (maximize != 0; min_j for maximize == 0); a NaN E[b,j] never wins
+ *   best_value[b] = E[b, best_idx[b]]
+ * Every sum over cells is taken in one fixed order that depends on C only (no atomics, no split over C): E[b,j] is the same bits for a
+ * row alone, inside any batch, at any row position, with any M, at any candidate position and in either form of the plan.  The pick
+ * across candidate tiles is a second pass over per-tile partials.  A -inf logit is a cell of weight 0, and 0 * NaN is NaN: a NaN
+ * table entry makes its candidate NaN for every row.  A NaN or +inf logit, or a row of -inf only, gives best_idx = -1, best_value =
+ * NaN and a NaN `expected` row, and touches no other row; a row whose every E is NaN gives -1 / NaN as well.  No input value forms an
+ * address or bounds a loop.  B == 0 or M == 0 is a no-op.  PG_EINVAL, naming the argument and before any HIP call, for C < 1, a
+ * negative B or M, B * M > 2^31 - 1 and a null logits, table, best_idx or best_value.  Takes pg_guess_best_plan's out[5] bytes of
+ * stream-ordered scratch: the weights (B,C) fp64, Z, and one (value, index) partial per row and candidate tile.
+ * ------------------------------------------------------------------------------------------------ */
+int pg_score_table(const double* candidates, int M, const double* centroids, int C, int kind, double* table, void* stream);
+int pg_guess_best(const float* logits, int B, int C, const double* table, int M, int maximize, int32_t* best_idx, double* best_value,
+                  double* expected, void* stream);
+/* What pg_guess_best does with these shapes (host arithmetic, no GPU; PG_EINVAL as pg_guess_best's for the three sizes):
+ *   out[0]  the form: 0 = 32 x 32 tiles, 1 = 64 x 64 tiles, taken when ceil(B / 64) * ceil(M / 64) >= 256 workgroups (same bits)
+ *   out[1]  rows per tile
+ *   out[2]  candidates per tile
+ *   out[3]  cells per K step (a C that is no multiple of it is padded with zeros on both sides of the product)
+ *   out[4]  workgroups of the product kernel: ceil(B / out[1]) * ceil(M / out[2])
+ *   out[5]  bytes of stream-ordered scratch (saturates at 2^31 - 1; 0 when B or M is 0)
+ *   out[6]  threads of a workgroup
+ *   out[7]  candidate tiles = partials per row that the second pass reads */
+int pg_guess_best_plan(int B, int C, int M, int32_t out[8]);
 
 /* ------------------------------------------------------------------------------------------------
  * Training the geocell head on embeddings (csrc/head_train.hip): one step of cell_layer = Linear(1024 -> C) under the reference's

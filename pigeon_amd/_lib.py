@@ -153,6 +153,9 @@ SIGNATURES = {
     "pg_smooth_labels": (_I, [_P, _I, _I, _D, _P, _P]),
     "pg_guess_spread": (_I, [_P, _I, _I, _P, _P, _P, _I, C.POINTER(_D), _I, _P, _P, _P, _P]),
     "pg_guess_spread_plan": (_I, [_I, C.POINTER(C.c_int32)]),
+    "pg_score_table": (_I, [_P, _I, _P, _I, _I, _P, _P]),
+    "pg_guess_best": (_I, [_P, _I, _I, _P, _I, _I, _P, _P, _P, _P]),
+    "pg_guess_best_plan": (_I, [_I, _I, _I, C.POINTER(C.c_int32)]),
     "pg_haversine_blocks": (_I, [_P, _P, _P, _I, _D, _P, _P]),
     "pg_optics_graph": (_I, [_P, _P, _P, _I, _I, _P, _P, _P, _P, _P]),
     "pg_optics_plan": (_I, [_I64, _I, C.POINTER(C.c_int32)]),

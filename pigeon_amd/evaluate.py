@@ -102,6 +102,18 @@ def _final_spread(model: SuperGuessr, st: dict, refined, quantiles):
     return model.spread(points=None if refined is None else refined.to(torch.float64), quantiles=quantiles, state=st)
 
 
+def _final_best_guess(model: SuperGuessr, st: dict, refined, objective: str):
+    """`model.best_guess` of a settled state against its FINAL guess as the incumbent (as `_final_spread`).  Device tensors only."""
+    return model.best_guess(objective=objective, incumbent=None if refined is None else refined.to(torch.float64), state=st)
+
+
+def best_guess_metrics(best_llh, distances_fn, labels, taken) -> Dict[str, float]:
+    """The existing km and score metrics on the guesses chosen by expectation (`best_llh` (N,2)), and the share of rows changed."""
+    d = distances_fn(np.asarray(best_llh), np.asarray(labels))
+    return {'Mean_km_error_best': np.mean(d), 'Median_km_error_best': np.median(d), 'Geoguessr_score_best': geoguessr_score(d),
+            'Best_guess_changed': float(np.mean(np.asarray(taken, dtype=bool)))}
+
+
 def _class_labels(labels) -> np.ndarray:
     labels = np.asarray(labels)
     return np.argmax(labels, axis=-1) if labels.ndim > 1 else labels          # (N, classes) one-hot / probabilities, or (N,) indices
@@ -152,7 +164,7 @@ def compute_geoguessr_metrics(results, scaler=None, countries=None) -> Dict[str,
 @torch.no_grad()
 def certain_forward(model: SuperGuessr, refiner: Optional[ProtoRefiner], pixel_values=None, embedding=None, labels=None,
                     labels_clf=None, labels_multi_task=None, labels_climate=None, labels_month=None, pixel_bytes=None, spread=None,
-                    **_unused):
+                    best_guess=None, **_unused):
     """`model(**data)` followed by `refiner(...)` with the reference's discrete outputs (a z ~ 4 statistical statement for the samples called certain, pigeon_amd/certainty.py): one fast pass, the tolerance of every
     discrete decision downstream of the embedding -- the top-1 cell (pg_head_certainty) and, with a refiner, the winning candidate,
     the candidate-set boundary, the nearest prototype and the farthest member (pg_refine_certainty) -- and ONE exact pass
@@ -169,7 +181,9 @@ def certain_forward(model: SuperGuessr, refiner: Optional[ProtoRefiner], pixel_v
     every output and every `info` entry equals what the fp32 pixels `table[bytes]` give.
     `spread` (quantiles, e.g. (0.5, 0.9); default None: nothing is computed): adds info['spread'], `SuperGuessr.spread` of the final
     guess -- the refined point with a refiner, else the top-1 centroid -- from the settled state's logits (re-encoded rows: their
-    exact-tier logits)."""
+    exact-tier logits).
+    `best_guess` ('score' | 'km'; default None: nothing is computed): adds info['best_guess'], `SuperGuessr.best_guess` over the model's
+    own centroids under that objective, with the final guess -- the refined point with a refiner -- as the incumbent."""
     if pixel_bytes is not None:
         model._check_pixel_bytes(pixel_bytes, pixel_values, embedding)
     res = model.engine(refiner).submit(pixel_values, embedding, pixel_bytes=pixel_bytes)[0]
@@ -184,6 +198,8 @@ def certain_forward(model: SuperGuessr, refiner: Optional[ProtoRefiner], pixel_v
     model.last_certain = info['certain']
     if spread is not None:
         info['spread'] = _final_spread(model, st, st.get('refined_LLH') if refiner is not None else None, spread)
+    if best_guess is not None:
+        info['best_guess'] = _final_best_guess(model, st, st.get('refined_LLH') if refiner is not None else None, best_guess)
     return out, info
 
 
@@ -266,7 +282,7 @@ class ImageEvalDataset:
 
 def evaluate_model(model: SuperGuessr, dataset, metrics: Optional[Callable] = None, train_args=None,
                    refiner: Optional[ProtoRefiner] = None, yfcc: bool = False, writer=None, step: int = 0,
-                   batch_size: Optional[int] = None, num_workers: int = 0, spread=None):
+                   batch_size: Optional[int] = None, num_workers: int = 0, spread=None, best_guess=None):
     """reference training/train_eval_loop.py:35-161 (eval loop :77-112).
 
     dataset items are dicts of forward() keyword arguments (pixel_values | pixel_bytes | embedding, labels, labels_clf, ...), or
@@ -277,6 +293,11 @@ def evaluate_model(model: SuperGuessr, dataset, metrics: Optional[Callable] = No
     guess, from its final state (rows the exact tier re-encoded: their re-encoded logits), on device tensors without a host
     synchronisation: results['expected_km'], ['expected_score'] (N,), ['radius_km'] (N, nq), ['spread_quantiles']; when the dataset
     has a `labels` column also `spread_metrics`: Radius_<100 q>_coverage, Median_radius_<100 q>_km, Mean_expected_km / _score.
+    `best_guess` ('score' | 'km'; default None: nothing is computed): `SuperGuessr.best_guess` of every finished batch over the model's
+    centroids, its final guess as the incumbent, on device tensors without a host synchronisation: results['best_LLH'] (N,2),
+    ['best_index'], ['best_expected'], ['best_taken'] (N,); when the dataset has a `labels` column also Mean_km_error_best,
+    Median_km_error_best, Geoguessr_score_best (the existing metric functions on best_LLH) and Best_guess_changed, the share of rows
+    taken.  Every other key is computed as without it.
     """
     from torch.utils.data import DataLoader
     logger.warning('Starting evaluation ...')
@@ -295,6 +316,7 @@ def evaluate_model(model: SuperGuessr, dataset, metrics: Optional[Callable] = No
     multi_task = bool(getattr(model, 'multi_task', False))
     combined_certain = []
     combined_spread = []
+    combined_best = []
     n_seen = 0
     # The reference's loop (:77-112) computes a batch and appends its predictions; the predictions are only read after the loop
     # (:114-140).  Here a batch's rows that the 16-bit encoder cannot settle are queued on the device and re-encoded by the exact
@@ -329,6 +351,8 @@ def evaluate_model(model: SuperGuessr, dataset, metrics: Optional[Callable] = No
             combined_certain.append(res['certain'])                              # every output of the sample is the reference's
             if spread is not None:
                 combined_spread.append(_final_spread(model, res['state'], res['state'].get('refined_LLH') if refiner is not None else None, spread))
+            if best_guess is not None:
+                combined_best.append(_final_best_guess(model, res['state'], res['state'].get('refined_LLH') if refiner is not None else None, best_guess))
             n_seen += outputs.preds_geocell.shape[0]
 
     with torch.no_grad():
@@ -371,6 +395,16 @@ def evaluate_model(model: SuperGuessr, dataset, metrics: Optional[Callable] = No
         if true_lla is not None and len(true_lla) == len(preds):
             results.update(spread_metrics(results['radius_km'], results['spread_quantiles'], haversine_np(preds, true_lla),
                                           results['expected_km'], results['expected_score']))
+    if best_guess is not None:
+        results.update(best_LLH=to_np([g.point for g in combined_best]), best_index=to_np([g.index for g in combined_best]),
+                       best_expected=to_np([g.expected for g in combined_best]), best_taken=to_np([g.taken for g in combined_best]))
+        try:
+            true_lla = np.asarray(dataset['labels'])
+        except (KeyError, IndexError, TypeError, ValueError):
+            true_lla = None
+        best_extra = {}
+        if true_lla is not None and len(true_lla) == len(preds):
+            best_extra = best_guess_metrics(results['best_LLH'], haversine_np, true_lla, results['best_taken'])
     if metrics is not None:                                                       # :122-140
         labels_lla, labels_cell = dataset['labels'], dataset['labels_clf']
         if isinstance(labels_lla, np.ndarray) == False:
@@ -381,6 +415,8 @@ def evaluate_model(model: SuperGuessr, dataset, metrics: Optional[Callable] = No
             labels_month = np.asarray(dataset['labels_month']) if preds_month is not None else None
         results.update(metrics((preds, preds_geocells, preds_mt, preds_climate, preds_month, top5_geocells,
                                 labels_lla, labels_cell, labels_mt, labels_climate, labels_month)))
+    if best_guess is not None:
+        results.update(best_extra)
     model.train()
     logger.warning('Back to training ...')
     return results
@@ -390,7 +426,7 @@ def evaluate(model: str, dataset, yfcc: bool, landmarks: bool, base_model=None, 
              refine: bool = True, geocell_path: Optional[str] = None, proto_path: Optional[str] = None,
              dataset_path=None, bank=None, head_state: Optional[str] = None, multi_task: bool = False,
              calibration: Optional[str] = None, embedding_rel_tol: Optional[float] = None, country_path: Optional[str] = None,
-             bank_rel_tol=None, spread=None):
+             bank_rel_tol=None, spread=None, best_guess=None):
     """reference evaluation/evaluate.py:10-85.
 
     `base_model`: as in the reference a STRING -- config.CLIP_MODEL for the pretrained tower, or the path of a checkpoint whose
@@ -419,6 +455,7 @@ def evaluate(model: str, dataset, yfcc: bool, landmarks: bool, base_model=None, 
     `country_path`: the GeoJSON of country polygons behind `Country_accuracy` (reference evaluation/metrics.py:17).  None: the file
     config.COUNTRY_PATH names if it exists, else the key is left out as before; a path given explicitly must exist.
     `spread`: quantiles handed to `evaluate_model(spread=...)`; None (default): no spread is computed.
+    `best_guess`: 'score' | 'km', handed to `evaluate_model(best_guess=...)`; None (default): nothing is computed.
     """
     import os
     from . import config as cfg
@@ -503,7 +540,7 @@ def evaluate(model: str, dataset, yfcc: bool, landmarks: bool, base_model=None, 
         if refiner.bank_rel_tol > 0:
             print(f'Prototype bank declared at a relative error of {refiner.bank_rel_tol:.3g}: the refiner\'s certainty accounts for it')
     metrics = compute_geoguessr_metrics if countries is None else (lambda r: compute_geoguessr_metrics(r, countries=countries))
-    results = evaluate_model(full_model, dataset, metrics, None, refiner, spread=spread)
+    results = evaluate_model(full_model, dataset, metrics, None, refiner, spread=spread, best_guess=best_guess)
     if write_calibration:
         if full_model.base_model is not None and full_model.certainty.calibrated:
             full_model.save_calibration(calibration, source=f'evaluate, first batch, {full_model.certainty.stats.get("samples")} samples')

@@ -295,6 +295,56 @@ def guess_spread_plan(C_cells: int) -> dict:
     return {"form": int(o[0]), "lds_bytes": int(o[1]), "lds_cells": int(o[2]), "threads": int(o[3])}
 
 
+# ----------------------------------------------------------------------------------------- guess by expected score
+_TABLE_KINDS = {"km": 0, "score": 1}
+
+
+def score_table(candidates: torch.Tensor, centroids: torch.Tensor, kind: str = "score") -> torch.Tensor:
+    """pg_score_table: candidates (M,2) fp64 [lng,lat], centroids (C,2) fp64 -> table (M,C) fp64, candidate-major: the km of
+    pg_haversine_matrix (kind='km') or 5000 exp(-km / 1492.7) (kind='score').  No host synchronisation."""
+    if kind not in _TABLE_KINDS:
+        raise _lib.PigeonHipError(f"score_table: kind must be 'score' or 'km', got {kind!r}")
+    _dev(candidates, torch.float64); _shape(candidates, "candidates", None, 2)
+    _dev(centroids, torch.float64); _shape(centroids, "centroids", None, 2)
+    if centroids.device != candidates.device:
+        raise _lib.PigeonHipError(f"score_table: centroids is on {centroids.device}, candidates on {candidates.device}")
+    M, Cn = int(candidates.shape[0]), int(centroids.shape[0])
+    table = torch.empty((M, Cn), dtype=torch.float64, device=candidates.device)
+    with torch.cuda.device(candidates.device):
+        check(load().pg_score_table(_p(candidates), M, _p(centroids), Cn, _TABLE_KINDS[kind], _p(table), _stream()), "pg_score_table")
+    return table
+
+
+def guess_best(logits: torch.Tensor, table: torch.Tensor, maximize: bool = True, return_expected: bool = False):
+    """pg_guess_best: logits (B,C) fp32, table (M,C) fp64 -> (best_idx int64 (B,), best_value fp64 (B,)[, expected fp64 (B,M)]): per
+    row the candidate whose expectation under the row's softmax is largest (maximize) or smallest, the first among equals, -1 / NaN
+    for a row the contract answers with NaN.  The contract is include/pigeon_hip.h's.  No host synchronisation."""
+    _dev(logits, torch.float32); _shape(logits, "logits", None, None)
+    B, Cn = int(logits.shape[0]), int(logits.shape[1])
+    _dev(table, torch.float64); _shape(table, "table", None, Cn)
+    if table.device != logits.device:
+        raise _lib.PigeonHipError(f"guess_best: table is on {table.device}, logits on {logits.device}")
+    M = int(table.shape[0])
+    idx = torch.empty((B,), dtype=torch.int32, device=logits.device)
+    val = torch.empty((B,), dtype=torch.float64, device=logits.device)
+    exp = torch.empty((B, M), dtype=torch.float64, device=logits.device) if return_expected else None
+    with torch.cuda.device(logits.device):
+        check(load().pg_guess_best(_p(logits), B, Cn, _p(table), M, 1 if maximize else 0, _p(idx), _p(val), _p(exp), _stream()),
+              "pg_guess_best")
+    if M == 0:                                             # a no-op in the library: nothing to choose from
+        idx.fill_(-1); val.fill_(float("nan"))
+    idx = idx.to(torch.int64)
+    return (idx, val, exp) if return_expected else (idx, val)
+
+
+def guess_best_plan(B: int, C_cells: int, M: int) -> dict:
+    """pg_guess_best_plan: what pg_guess_best does with B rows, C cells and M candidates (host arithmetic, no GPU)."""
+    o = (C.c_int32 * 8)()
+    check(load().pg_guess_best_plan(int(B), int(C_cells), int(M), o), "pg_guess_best_plan")
+    return {"form": int(o[0]), "rows_per_tile": int(o[1]), "candidates_per_tile": int(o[2]), "cells_per_step": int(o[3]),
+            "workgroups": int(o[4]), "scratch_bytes": int(o[5]), "threads": int(o[6]), "candidate_tiles": int(o[7])}
+
+
 # ----------------------------------------------------------------------------------------- training the head
 def _same_device(who: str, ref_name: str, ref: torch.Tensor, **tensors):
     for name, t in tensors.items():

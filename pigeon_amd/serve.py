@@ -90,7 +90,7 @@ def panorama_from_request(body: Dict, encoded: bool = False):
 
 
 def predict_panorama(views: Sequence, model, refiner=None, preprocess: Optional[Callable] = None, attribution: bool = False,
-                     spread: bool = False) -> Dict:
+                     spread: bool = False, best_guess: bool = False) -> Dict:
     """views: four PIL images (or the EquirectRequest of a `panorama` body) -> {'lat', 'lng'} (+ 'geocell_margin', 'geocell_certain', 'reencoded_exact' when the model exposes the
     certainty of its top-1).  `preprocess(list of PIL) -> (4,3,336,336)` defaults to the GPU path.  Views that are all `bytes` (image
     files) go to the same path undecoded: baseline JPEGs are decoded on the GPU (pigeon_amd/jpeg.py: Pillow's pixels, bit for bit),
@@ -99,8 +99,15 @@ def predict_panorama(views: Sequence, model, refiner=None, preprocess: Optional[
     pigeon_amd/explain.py `attribution_json`; on the exact tier when this panorama was re-encoded there).
     spread=True adds how far off the answer may be (`model.spread` at the returned point, SPREAD_QUANTILES): 'expected_km',
     'expected_score' (the GeoGuessr score before its rounding) and 'radius_km': {"0.5": km, "0.9": km}, the radii of the circles
-    around the answer that hold, whole, cells carrying that share of the head's probability."""
+    around the answer that hold, whole, cells carrying that share of the head's probability.
+    best_guess=True answers with the point of the largest expected GeoGuessr score (`model.best_guess` over the geocell centroids, the
+    former answer as the incumbent): 'lat' / 'lng' become the chosen point -- the extension reads nothing else --, the former answer
+    moves to 'argmax_lat' / 'argmax_lng', and 'guess_expected_score' and 'guess_changed' are added.  The `spread` keys, when asked
+    for as well, still describe the former answer."""
     import torch
+    if best_guess and not hasattr(model, "best_guess"):
+        raise ValueError("predict_panorama(best_guess=True): this model has no `best_guess` (it needs SuperGuessr.best_guess)")
+    bg = None
     if spread and not hasattr(model, "spread"):
         raise ValueError("predict_panorama(spread=True): this model has no `spread` (it needs SuperGuessr.spread)")
     sp = None
@@ -139,8 +146,9 @@ def predict_panorama(views: Sequence, model, refiner=None, preprocess: Optional[
             # pigeon_amd.SuperGuessr: the same call with the certainty of every discrete output (top-1 cell AND what the refiner below
             # will pick) checked, and the panorama re-encoded in the exact mode if it is not certain (exact_top1, the default)
             from .evaluate import certain_forward
-            out, info = certain_forward(model, refiner, pixel_values=px, spread=SPREAD_QUANTILES if spread else None)
-            sp = info.get("spread")
+            out, info = certain_forward(model, refiner, pixel_values=px, spread=SPREAD_QUANTILES if spread else None,
+                                        best_guess="score" if best_guess else None)
+            sp, bg = info.get("spread"), info.get("best_guess")
             pred_llh, topk, embedding = out[0], out[1], out[-1]    # multi-task models put preds_mt in between (:463-464)
             if refiner is not None:
                 pred_llh = info["refined_LLH"]                     # the refinement certain_forward ran (once; re-run for re-encoded rows)
@@ -152,8 +160,15 @@ def predict_panorama(views: Sequence, model, refiner=None, preprocess: Optional[
                                          candidate_probs=topk.values)
             if spread:
                 sp = model.spread(points=pred_llh.reshape(-1, 2).to(torch.float64), quantiles=SPREAD_QUANTILES)
+            if best_guess:
+                bg = model.best_guess(objective="score", incumbent=pred_llh.reshape(-1, 2).to(torch.float64))
     lng, lat = (float(v) for v in pred_llh.reshape(-1, 2)[0].tolist())
     res = {"lat": lat, "lng": lng}
+    if bg is not None:                                             # the chosen point answers; the former answer stays readable
+        res["argmax_lat"], res["argmax_lng"] = lat, lng
+        res["lng"], res["lat"] = (float(v) for v in bg.point.reshape(-1, 2)[0].tolist())
+        res["guess_expected_score"] = float(torch.where(bg.taken, bg.expected, bg.incumbent_expected).reshape(-1)[0])
+        res["guess_changed"] = bool(bg.taken.reshape(-1)[0])
     # certainty of the geocell top-1 (pigeon_amd.SuperGuessr, round 4): extra keys, the extension reads lat / lng only
     if getattr(model, "last_certain", None) is not None:
         res["geocell_margin"] = float(model.last_margin.reshape(-1)[0])
@@ -172,10 +187,13 @@ def predict_panorama(views: Sequence, model, refiner=None, preprocess: Optional[
 
 
 def make_app(model, refiner=None, preprocess: Optional[Callable] = None, game_log: Optional[List] = None, encoded: bool = False,
-             spread: bool = False):
+             spread: bool = False, best_guess: bool = False):
     """Starlette application with the two routes the extension calls.  encoded=True: the payloads are handed on as bytes and decoded
     on the GPU (see predict_panorama); the response is the same.  spread=True: every answer carries 'expected_km', 'expected_score'
-    and 'radius_km' (see predict_panorama); a model without `spread` is refused here, not per request."""
+    and 'radius_km' (see predict_panorama); a model without `spread` is refused here, not per request.  best_guess=True: every answer
+    is the point of the largest expected score (see predict_panorama); a model without `best_guess` is refused here as well."""
+    if best_guess and not hasattr(model, "best_guess"):
+        raise ValueError("make_app(best_guess=True): this model has no `best_guess` (it needs SuperGuessr.best_guess)")
     if spread and not hasattr(model, "spread"):
         raise ValueError("make_app(spread=True): this model has no `spread` (it needs SuperGuessr.spread)")
     from starlette.applications import Starlette
@@ -195,7 +213,7 @@ def make_app(model, refiner=None, preprocess: Optional[Callable] = None, game_lo
         # called inline on the event loop, on purpose: the handles behind `model` are one per (device, stream) and not
         # thread-safe, so requests are answered one at a time -- a `def` handler would run in Starlette's pool
         try:
-            res = predict_panorama(views, model, refiner, preprocess, attribution=attribution, spread=spread)
+            res = predict_panorama(views, model, refiner, preprocess, attribution=attribution, spread=spread, best_guess=best_guess)
         except BadRequest as e:                                    # (encoded mode: the payloads are only decoded in there)
             return JSONResponse({"error": str(e)}, status_code=400)
         return JSONResponse({"gameID": body.get("gameID"), "roundID": body.get("roundID"), "results": res})
@@ -214,7 +232,7 @@ def make_app(model, refiner=None, preprocess: Optional[Callable] = None, game_lo
 
 
 def main(argv=None):
-    """python -m pigeon_amd.serve --head <head.model> [--geocells <csv>] [--protos <csv> --dataset <dir>] [--calibration <file>] [--spread] [--port 5000]"""
+    """python -m pigeon_amd.serve --head <head.model> [--geocells <csv>] [--protos <csv> --dataset <dir>] [--calibration <file>] [--spread] [--guess expected-score] [--port 5000]"""
     import os
     ap = _arg_parser()
     args = ap.parse_args(argv)
@@ -242,7 +260,7 @@ def main(argv=None):
               f"{model.certainty.describe()}")
     refiner = ProtoRefiner(proto_path=args.protos, dataset_path=args.dataset) if args.protos else None
     torch.cuda.synchronize()
-    uvicorn.run(make_app(model, refiner, encoded=args.encoded, spread=args.spread), host=args.host, port=args.port)
+    uvicorn.run(make_app(model, refiner, encoded=args.encoded, spread=args.spread, best_guess=args.guess == "expected-score"), host=args.host, port=args.port)
 
 
 def _arg_parser():
@@ -262,6 +280,9 @@ def _arg_parser():
     ap.add_argument("--spread", action="store_true", default=False,
                     help="add to every answer how far off it may be: expected_km, expected_score and radius_km {\"0.5\", \"0.9\"} "
                          "(SuperGuessr.spread at the returned point); the extension reads lat / lng only")
+    ap.add_argument("--guess", choices=("expected-score",), default=None,
+                    help="answer with the point of the largest expected GeoGuessr score under the head's probabilities (SuperGuessr.best_guess "
+                         "over the geocell centroids): lat / lng become that point, the former answer moves to argmax_lat / argmax_lng")
     ap.add_argument("--host", default="127.0.0.1")
     ap.add_argument("--port", type=int, default=5000)
     ap.add_argument("--calibration", default=None, metavar="FILE",

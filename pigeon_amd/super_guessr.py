@@ -33,6 +33,10 @@ MultiTaskPredictions = namedtuple('MultiTaskPredictions', 'loss_reg preds_mt los
 Attribution = namedtuple('Attribution', 'maps offset cells against logits')
 # what `SuperGuessr.spread` returns: expected_km (B,) / (B,G), expected_score likewise, radius_km (B,nq) / (B,G,nq), the quantiles
 Spread = namedtuple('Spread', 'expected_km expected_score radius_km quantiles')
+# what `SuperGuessr.best_guess` returns: index (B,) int64 of the best candidate (-1: none), point (B,2) fp64 the chosen [lng, lat],
+# expected (B,) fp64 the best candidate's expectation, incumbent_expected (B,) fp64 the incumbent's, taken (B,) bool
+BestGuess = namedtuple('BestGuess', 'index point expected incumbent_expected taken')
+GUESS_OBJECTIVES = ('score', 'km')
 NUM_MULTI_TASK_VARIABLES = 6
 REGRESSION_LOSS_SCALING = 8
 NUM_CLIMATES = 28
@@ -147,6 +151,7 @@ class SuperGuessr(nn.Module):
         self._wnorm = {}                                     # exact? -> (key, device tensor): see wstats()
         self._cal_buffer = []                                # pixels of small first batches, until there are enough to calibrate on
         self._engines = {}                                   # refiner -> settle-before-return engine (see `engine`)
+        self._guess_tables = {}                              # objective -> (key, candidates, table): see best_guess()
         self._last_exact = None
         self._rel_tol0 = self.certainty.rel_tol              # the constructor's uncalibrated tolerance: what a weight load goes back to
         if self.exact_top1 and isinstance(self.base_model, HipCLIPVisionModel):
@@ -555,6 +560,54 @@ class SuperGuessr(nn.Module):
         pts = st['preds_LLH'] if points is None else torch.as_tensor(points).to(logits.device, torch.float64)
         ek, es, rk = hip_ops.guess_spread(logits, self.lla_geocells.data, pts.contiguous(), quantiles, extent_km=self.cell_extent_km)
         return Spread(ek, es, rk, tuple(float(q) for q in quantiles))
+
+    def _guess_table(self, candidates, objective: str, device):
+        """(candidates (M,2) fp64 on `device`, table (M,C) fp64) of `best_guess`: pg_score_table, built on first use and kept per
+        objective until the candidate tensor (its identity, version, storage or device) or the centroids change."""
+        src = self.lla_geocells if candidates is None else candidates
+        cen = self.lla_geocells
+        key = (id(src), src._version, src.data_ptr(), tuple(src.shape), src.dtype, str(src.device), cen._version, cen.data_ptr(), str(device))
+        hit = self._guess_tables.get(objective)
+        if hit is not None and hit[0] == key:
+            return hit[2], hit[3]
+        cand = src.detach().to(device, torch.float64).contiguous()
+        if cand.dim() != 2 or cand.shape[1] != 2:
+            raise ValueError(f'SuperGuessr.best_guess: candidates must be (M,2) [lng, lat], got {tuple(cand.shape)}')
+        table = hip_ops.score_table(cand, cen.data.to(device).contiguous(), kind=objective)
+        self._guess_tables[objective] = (key, src, cand, table)          # `src` is kept so that its id stays its own
+        return cand, table
+
+    @torch.no_grad()
+    def best_guess(self, candidates: Tensor = None, objective: str = 'score', incumbent: Tensor = None, state: dict = None) -> BestGuess:
+        """The guess chosen by its expectation under the head's softmax (pg_guess_best; contract: include/pigeon_hip.h), from the
+        geocell logits of `state` -- default `last_state`, with re-encoded rows carrying their exact-tier logits.
+          candidates  (M,2) [lng, lat] shared by the batch: a grid, prototype locations, ...; None: the model's own `lla_geocells`
+          objective   'score': the largest expected GeoGuessr score (5000 exp(-d / 1492.7), before its rounding); 'km': the smallest
+                      expected distance
+          incumbent   (B,2) [lng, lat], the guess to beat; None: the state's own `preds_LLH`.  Its expectation is pg_guess_spread's
+        The candidates x centroids table is built on first use and cached on the model, per objective, keyed by the candidate
+        tensor's identity and version.  Returns BestGuess(index, point, expected, incumbent_expected, taken), device tensors:
+        `taken[b]` where the best candidate's expectation is strictly better than the incumbent's (a NaN on either side keeps the
+        incumbent), `point[b]` the candidate where taken, else the incumbent.  Nothing is synchronised; nothing is computed unless
+        this is called."""
+        if objective not in GUESS_OBJECTIVES:
+            raise ValueError(f"SuperGuessr.best_guess: objective must be 'score' or 'km', got {objective!r}")
+        st = self.last_state if state is None else state
+        if st is None:
+            raise RuntimeError('SuperGuessr.best_guess: no state -- run a forward first, or pass `state`')
+        logits = st['logits']
+        cand, table = self._guess_table(candidates, objective, logits.device)
+        score = objective == 'score'
+        idx, val = hip_ops.guess_best(logits, table, maximize=score)
+        inc = st['preds_LLH'] if incumbent is None else torch.as_tensor(incumbent)
+        inc = inc.to(logits.device, torch.float64).contiguous()
+        ek, es, _ = hip_ops.guess_spread(logits, self.lla_geocells.data, inc, (1.0,), extent_km=self.cell_extent_km)
+        inc_e = es if score else ek
+        taken = ((val > inc_e) if score else (val < inc_e)) & (idx >= 0)          # a NaN compares false: the incumbent stays
+        if cand.shape[0] == 0:
+            return BestGuess(idx, inc, val, inc_e, taken)
+        point = torch.where(taken[:, None], cand[idx.clamp(min=0)], inc)
+        return BestGuess(idx, point, val, inc_e, taken)
 
     def _publish(self, st: dict) -> None:
         if 'certain' not in st:                          # a state straight from `encode_head` (no engine behind it)

@@ -94,6 +94,9 @@ argp.add_argument('--bank-rel-tol', dest='bank_rel_tol', default=None, metavar='
                        "the loaded tower's ends the run).  Default: what the bank records, else exact")
 
 
+argp.add_argument('--guess', choices=('expected-score', 'expected-km'), default=None,
+                  help="evaluate: also choose every guess by its expectation under the head's softmax (SuperGuessr.best_guess over the "
+                       "geocell centroids) and report the _best metrics next to the existing ones")
 argp.add_argument('--spread', action='store_true', default=False,
                   help="evaluate: how far off every guess may be (SuperGuessr.spread: expected km, expected GeoGuessr score, the radii "
                        "holding 0.5 and 0.9 of the head's probability) and, against the labels, how often the truth lies inside them "
@@ -279,7 +282,8 @@ def _dispatch(args, comm):
         results = evaluate(args.name, dataset, yfcc=args.yfcc, base_model=_vision_model(args), refine=True,
                            landmarks=args.landmarks, geocell_path=geocell_path, bank=bank, heading=args.heading,
                            multi_task=args.multitask, calibration=args.calibration, embedding_rel_tol=args.embedding_rel_tol,
-                           country_path=args.countries, bank_rel_tol=args.bank_rel_tol, spread=(0.5, 0.9) if args.spread else None)
+                           country_path=args.countries, bank_rel_tol=args.bank_rel_tol, spread=(0.5, 0.9) if args.spread else None,
+                           best_guess={'expected-score': 'score', 'expected-km': 'km'}.get(args.guess))
         _print_fallbacks(comm)
         if comm.is_main_process:
             print({k: (v if not hasattr(v, 'shape') or v.shape == () else tuple(v.shape)) for k, v in results.items() if k != 'exact_passes'})
@@ -288,6 +292,11 @@ def _dispatch(args, comm):
                       f"{results['Radius_50_coverage']:.1%} of the samples, the 90 % radius (median {results['Median_radius_90_km']:.1f} km) "
                       f"for {results['Radius_90_coverage']:.1%}; mean expected error {results['Mean_expected_km']:.1f} km, mean expected "
                       f"score {results['Mean_expected_score']:.0f}")
+            if 'Geoguessr_score_best' in results:
+                print(f"guess by {args.guess}: {results['Best_guess_changed']:.1%} of the guesses changed; mean error "
+                      f"{results['Mean_km_error']:.1f} -> {results['Mean_km_error_best']:.1f} km, median {results['Median_km_error']:.1f} -> "
+                      f"{results['Median_km_error_best']:.1f} km, GeoGuessr score {results['Geoguessr_score']:.0f} -> "
+                      f"{results['Geoguessr_score_best']:.0f}")
             if 'geocell_certain' in results:
                 # beyond the reference's output: how many samples' discrete outputs are certain to be the fp32 reference's (a z ~ 4
                 # statistical statement, pigeon_amd/certainty.py), and how many are near-ties of the reference itself
