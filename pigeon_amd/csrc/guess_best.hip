@@ -9,9 +9,9 @@
 //
 // pg_guess_best, three kernels on one stream:
 //   1. gb_weights_kernel, one workgroup of 256 threads per row: the row maximum, the NaN / +inf test, w[b,:] and Z[b] into a
-//      stream-ordered scratch.  Z is spread.hip's sum: thread t adds its cells t, t + 256, ... ascending, the 64 lanes of a wave
-//      combine in a butterfly, the four waves as (w0 + w1) + (w2 + w3).  A row the contract answers with NaN (a NaN or +inf logit, -inf
-//      only) gets w = 0 and Z = NaN: every E of that row is then NaN with no branch in the product, and no other row sees it.
+//      stream-ordered scratch.  Z is spread.hip's sum, in row_block.h's summation order.  A row the contract answers with NaN (a NaN
+//      or +inf logit, -inf only) gets w = 0 and Z = NaN: every E of that row is then NaN with no branch in the product, and no other
+//      row sees it.
 //   2. gb_product_kernel<T>, one workgroup of 256 threads per (row tile, candidate tile) of 32T x 32T, T = 1 or 2; each of the four
 //      waves owns a 16T x 16T corner as T x T accumulators of v_mfma_f64_16x16x4_f64.  Both operands are contiguous along c and
 //      staged [row][k] in LDS, GB_KC cells per step, the next step's loads in flight in registers.  One element's sum is ONE
@@ -26,6 +26,7 @@
 #include "common.h"
 #include "pigeon_internal.h"
 #include "haversine.h"
+#include "row_block.h"
 
 #include <cmath>
 
@@ -33,8 +34,6 @@
 #define GB_KC 32                                     // cells staged per K step
 #define GB_LDK (GB_KC + 2)                           // 34 doubles a row: the 16 rows x 2 k of a half wave's read fall on 32 distinct bank pairs
 #define GB_FILL_WGS 256                              // the 64 x 64 form is taken when it alone gives every CU a workgroup
-#define GB_SCORE_MAX 5000.0
-#define GB_DECAY_KM 1492.7                           // pigeon_amd/config.py DECAY_CONSTANT
 
 typedef __attribute__((ext_vector_type(4))) double f64x4;
 
@@ -45,7 +44,7 @@ __global__ __launch_bounds__(256) void score_table_kernel(const double* __restri
     if (i >= n) return;
     const int64_t j = i / C, c = i - j * C;
     const double d = pg_haversine_km<double>(cand[2 * j], cand[2 * j + 1], cen[2 * c], cen[2 * c + 1]);
-    table[i] = kind == 0 ? d : GB_SCORE_MAX * exp(-d / GB_DECAY_KM);
+    table[i] = kind == 0 ? d : PG_SCORE_MAX * exp(-d / PG_SCORE_DECAY_KM);
 }
 
 extern "C" int pg_score_table(const double* candidates, int M, const double* centroids, int C, int kind, double* table, void* stream) {
@@ -53,9 +52,9 @@ extern "C" int pg_score_table(const double* candidates, int M, const double* cen
     if (C < 1) { pg_set_error("score_table: C must be at least 1 (got %d)", C); return PG_EINVAL; }
     if (kind != 0 && kind != 1) { pg_set_error("score_table: kind must be 0 (km) or 1 (score), got %d", kind); return PG_EINVAL; }
     if (M == 0) return PG_OK;
-    if (!candidates) { pg_set_error("score_table: null argument candidates"); return PG_EINVAL; }
-    if (!centroids) { pg_set_error("score_table: null argument centroids"); return PG_EINVAL; }
-    if (!table) { pg_set_error("score_table: null argument table"); return PG_EINVAL; }
+    PG_NEED("score_table", candidates);
+    PG_NEED("score_table", centroids);
+    PG_NEED("score_table", table);
     const int64_t n = (int64_t)M * C, blocks = (n + 255) / 256;
     if (blocks > 0x7fffffffLL) { pg_set_error("score_table: M * C = %lld is more than one launch holds", (long long)n); return PG_EINVAL; }
     hipLaunchKernelGGL(score_table_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, candidates, centroids, C, n, kind, table);
@@ -78,13 +77,7 @@ __global__ __launch_bounds__(GB_THREADS) void gb_weights_kernel(const float* __r
         const float v = row[c];
         bad |= (v != v || v == INFINITY); mx = v > mx ? v : mx;
     }
-    mx = wave_max(mx);
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) bad |= __shfl_xor(bad, o, 64);
-    if ((tid & 63) == 0) { redmax[tid >> 6] = mx; redbad[tid >> 6] = bad; }
-    __syncthreads();
-    mx = fmaxf(fmaxf(redmax[0], redmax[1]), fmaxf(redmax[2], redmax[3]));
-    bad = redbad[0] | redbad[1] | redbad[2] | redbad[3];
+    block_max_flag(mx, bad, redmax, redbad);
     bad |= !(mx > -INFINITY);                          // a row of -inf only
     const double m = (double)mx;
     double acc = 0.0;
@@ -93,11 +86,8 @@ __global__ __launch_bounds__(GB_THREADS) void gb_weights_kernel(const float* __r
         wrow[c] = e;
         acc += e;
     }
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) acc += __shfl_xor(acc, o, 64);
-    if ((tid & 63) == 0) red[tid >> 6] = acc;
-    __syncthreads();
-    if (tid == 0) Z[b] = bad ? (double)NAN : (red[0] + red[1]) + (red[2] + red[3]);
+    block_sum(acc, red);
+    if (tid == 0) Z[b] = bad ? (double)NAN : acc;
 }
 
 // ------------------------------------------------------------------------------------------------ 2. product and tile partials
@@ -242,7 +232,7 @@ static int gb_check_shape(const char* who, int B, int C, int M) {
 }
 
 extern "C" int pg_guess_best_plan(int B, int C, int M, int32_t out[8]) {
-    if (!out) { pg_set_error("guess_best_plan: null argument out"); return PG_EINVAL; }
+    PG_NEED("guess_best_plan", out);
     const int rc = gb_check_shape("guess_best_plan", B, C, M);
     if (rc != PG_OK) return rc;
     const GbPlan p = gb_plan(B, C, M);
@@ -264,10 +254,10 @@ extern "C" int pg_guess_best(const float* logits, int B, int C, const double* ta
     const int rc0 = gb_check_shape("guess_best", B, C, M);
     if (rc0 != PG_OK) return rc0;
     if (B == 0 || M == 0) return PG_OK;                    // nothing to do: the (empty) buffers may be NULL
-    if (!logits) { pg_set_error("guess_best: null argument logits"); return PG_EINVAL; }
-    if (!table) { pg_set_error("guess_best: null argument table"); return PG_EINVAL; }
-    if (!best_idx) { pg_set_error("guess_best: null argument best_idx"); return PG_EINVAL; }
-    if (!best_value) { pg_set_error("guess_best: null argument best_value"); return PG_EINVAL; }
+    PG_NEED("guess_best", logits);
+    PG_NEED("guess_best", table);
+    PG_NEED("guess_best", best_idx);
+    PG_NEED("guess_best", best_value);
     const GbPlan p = gb_plan(B, C, M);
     if (p.row_tiles > 65535) { pg_set_error("guess_best: B = %d is more than one launch holds", B); return PG_EINVAL; }
     hipStream_t s = (hipStream_t)stream;

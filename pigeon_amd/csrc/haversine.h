@@ -7,6 +7,11 @@
 #include <hip/hip_runtime.h>
 #include <cmath>
 
+// the score of a distance d km is PG_SCORE_MAX * exp(-d / PG_SCORE_DECAY_KM).  Constants only: spread.hip and guess_best.hip associate
+// the product differently, and each expression's bits are part of its contract.
+#define PG_SCORE_MAX 5000.0
+#define PG_SCORE_DECAY_KM 1492.7                     // pigeon_amd/config.py DECAY_CONSTANT
+
 // torch.deg2rad multiplies by the double constant pi/180 rounded to the tensor's dtype
 #define DEG2RAD_D 0.017453292519943295769236907684886127134428718885417
 template <typename X> struct Deg;

@@ -11,6 +11,7 @@
 #include "common.h"
 #include "pigeon_internal.h"
 #include "certainty_common.h"   // better(): the selection order
+#include "row_block.h"          // the summation order; the row's probabilities in LDS or in scratch
 #include <cfloat>
 
 #define HT 64
@@ -90,9 +91,10 @@ __device__ __forceinline__ ValIdx block_argbest(ValIdx x, ValIdx* red /*[4]*/) {
     return r;
 }
 
-// one block per batch row; the row's C probabilities live in dynamic LDS (GLOBAL = false: C <= 38 400, every geocell set of the
-// reference) or, for larger heads, in a row of a device scratch matrix (GLOBAL = true, round 4: same arithmetic and selection order,
-// the k selection passes then stream the row from L2 / HBM instead of LDS)
+#define HEAD_LDS_CELLS row_lds_cells(sizeof(float))
+
+// one block per batch row; the row's C probabilities are the cells that row_block.h keeps in LDS (C <= 38 400: every geocell set of
+// the reference) or in scratch (the k selection passes then stream the row from L2 / HBM instead of LDS)
 template <bool GLOBAL>
 __global__ __launch_bounds__(256) void head_row_kernel(const float* __restrict__ logits, int C, int k,
                                                        const double* __restrict__ centroids,
@@ -116,10 +118,7 @@ __global__ __launch_bounds__(256) void head_row_kernel(const float* __restrict__
     // sum of exp(x - max)
     float sm = 0.f;
     for (int c = tid; c < C; c += 256) { const float e = expf(probs[c] - mx); probs[c] = e; sm += e; }
-    sm = wave_sum(sm);
-    if ((tid & 63) == 0) redf[tid >> 6] = sm;
-    __syncthreads();
-    sm = (redf[0] + redf[1]) + (redf[2] + redf[3]);
+    block_sum(sm, redf);
     for (int c = tid; c < C; c += 256) probs[c] = probs[c] / sm;
     __syncthreads();
     // k rounds of selection
@@ -156,28 +155,15 @@ extern "C" int pg_head_forward(const float* emb, int B, int P, const float* W, c
         pg_set_error("head: null pointer argument"); return PG_EINVAL;
     }
     if (P < 1 || C < 1 || k < 1 || k > C) { pg_set_error("head: bad P=%d C=%d k=%d", P, C, k); return PG_EINVAL; }
-    const size_t lds = (size_t)C * sizeof(float);
-    const bool big = lds > 150 * 1024;                     // > 38 400 geocells: probabilities in a stream-ordered device scratch
     dim3 g1((C + HT - 1) / HT, (B + HT - 1) / HT);
     hipLaunchKernelGGL(head_logits_kernel, g1, dim3(256), 0, s, emb, B, P, W, bias, C, logits);
     int rc = pg_check_launch("head_logits");
     if (rc) return rc;
-    if (big) {
-        float* scratch = nullptr;
-        PG_HIP(hipMallocAsync((void**)&scratch, (size_t)B * C * sizeof(float), s));
-        hipLaunchKernelGGL(head_row_kernel<true>, dim3(B), dim3(256), 0, s, logits, C, k, centroids, topk_val, topk_idx, argmax, pred_llh, scratch);
-        rc = pg_check_launch("head_row (large C)");
-        (void)hipFreeAsync(scratch, s);
-        return rc;
-    }
-    static size_t attr_lds = 0;
-    if (lds > attr_lds) {
-        PG_HIP(hipFuncSetAttribute((const void*)head_row_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        attr_lds = lds;
-    }
-    hipLaunchKernelGGL(head_row_kernel<false>, dim3(B), dim3(256), lds, s, logits, C, k, centroids, topk_val, topk_idx, argmax, pred_llh,
-                       (float*)nullptr);
-    return pg_check_launch("head_row");
+    return row_cells_launch<head_row_kernel<false>, head_row_kernel<true>>(
+        "head_row", "head_row (large C)", B, C, HEAD_LDS_CELLS, sizeof(float), s, [&](auto kernel, size_t lds, void* scratch) {
+            hipLaunchKernelGGL(kernel, dim3(B), dim3(256), lds, s, logits, C, k, centroids, topk_val, topk_idx, argmax, pred_llh,
+                               (float*)scratch);
+        });
 }
 
 // ---- certainty of the top-1 (round 4) ----------------------------------------------------------------------------------------
@@ -191,7 +177,7 @@ __global__ __launch_bounds__(256) void head_margin_kernel(const float* __restric
                                                           const float* __restrict__ W, float* __restrict__ margin,
                                                           float* __restrict__ sens, int64_t* __restrict__ top2) {
     __shared__ ValIdx red[4];
-    __shared__ float redf[8];
+    __shared__ float redf[4][2];
     const int b = blockIdx.x, tid = threadIdx.x;
     const float* row = logits + (int64_t)b * C;
     ValIdx b1; b1.v = -FLT_MAX; b1.i = 0x7fffffff;
@@ -224,15 +210,13 @@ __global__ __launch_bounds__(256) void head_margin_kernel(const float* __restric
             if (have2) { const float d = W[(int64_t)t1.i * VIT_HIDDEN + c0 + e] - W[(int64_t)t2.i * VIT_HIDDEN + c0 + e]; sw += d * d; }
         }
     }
-    se = wave_sum(se); sw = wave_sum(sw);
+    // packed only now: accumulating into the array changes which product of a0 a0 + a1 a1 the compiler fuses, and with it sens' last bit
+    float sq[2] = {se, sw};
     __syncthreads();
-    if ((tid & 63) == 0) { redf[tid >> 6] = se; redf[4 + (tid >> 6)] = sw; }
-    __syncthreads();
+    block_sum(sq, redf);
     if (tid == 0) {
-        se = (redf[0] + redf[1]) + (redf[2] + redf[3]);
-        sw = (redf[4] + redf[5]) + (redf[6] + redf[7]);
         margin[b] = have2 ? t1.v - t2.v : INFINITY;
-        sens[b] = have2 ? sqrtf(se) * sqrtf(sw) * (1.0f / 32.0f) : 0.f;
+        sens[b] = have2 ? sqrtf(sq[0]) * sqrtf(sq[1]) * (1.0f / 32.0f) : 0.f;
         if (top2) top2[b] = have2 ? t2.i : t1.i;
     }
 }

@@ -15,10 +15,8 @@
 //        S = sum y_c,  m = max l_c,  e_c = exp(l_c - m),  Z = sum e_c,  T = sum fma(y_c, l_c, .)
 //        loss_rows[b] = S * (m + log(Z)) - T
 //        g[b,c]       = (float)(((S * e_c) / Z - y_c) * grad_scale)                        (e_c is evaluated a second time, same bits)
-//      Every sum over cells is the same sequence of additions: thread t adds its cells t, t + 256, ... in ascending order, the 64
-//      lanes of a wave combine in a butterfly, the four waves as (w0 + w1) + (w2 + w3).  It depends on C only: no atomics, no
-//      dependence on B or the row's position.  The y_c live in LDS up to HT_LDS_CELLS cells (GLOBAL = false) and in a stream-ordered
-//      device scratch above (GLOBAL = true): the same arithmetic in the same order, the same bits.
+//      Every sum over cells is row_block.h's one summation order: it depends on C only, not on B or the row's position.  The y_c are
+//      the cells that row_block.h keeps in LDS or in scratch.
 //      A row whose label point is not finite, or whose labels_clf is outside [0, C), gets loss_rows[b] = NaN and a zero g row and
 //      touches nothing else.  No input value forms an address or bounds a loop.  Non-finite logits propagate as in torch (NaN).
 //
@@ -42,11 +40,12 @@
 #include "common.h"
 #include "pigeon_internal.h"
 #include "haversine.h"
+#include "row_block.h"
 
 #include <cmath>
 
 #define HT_THREADS 256
-#define HT_LDS_CELLS 19200                           // 8 bytes a cell: 150 KB of the CU's 160 KB
+#define HT_LDS_CELLS row_lds_cells(sizeof(double))   // one target y_c a cell
 #define HT_KC 32                                     // reduction rows staged per step
 
 // ------------------------------------------------------------------------------------------------ 1. panel mean
@@ -135,22 +134,6 @@ __global__ __launch_bounds__(HT_THREADS) void ht_logits_kernel(const float* __re
 }
 
 // ------------------------------------------------------------------------------------------------ 3. rows
-// the one summation order: v[0..2] of every thread -> the block's sums, identical in every thread
-__device__ __forceinline__ void ht_block_sum(double v[3], double (*red)[3]) {
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-#pragma unroll
-        for (int o = 32; o >= 1; o >>= 1) v[j] += __shfl_xor(v[j], o, 64);
-    }
-    if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-        for (int j = 0; j < 3; ++j) red[threadIdx.x >> 6][j] = v[j];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int j = 0; j < 3; ++j) v[j] = (red[0][j] + red[1][j]) + (red[2][j] + red[3][j]);
-}
-
 template <bool GLOBAL>
 __global__ __launch_bounds__(HT_THREADS) void ht_row_kernel(float* __restrict__ g, int C, const double* __restrict__ centroids,
                                                             const double* __restrict__ labels_llh, const int64_t* __restrict__ labels_clf,
@@ -230,7 +213,7 @@ __global__ __launch_bounds__(HT_THREADS) void ht_row_kernel(float* __restrict__ 
         acc[1] += exp(l - m);
         acc[2] = fma(yc, l, acc[2]);
     }
-    ht_block_sum(acc, red);
+    block_sum(acc, red);
     const double S = acc[0], Z = acc[1];
     if (tid == 0) loss_rows[b] = S * (m + log(Z)) - acc[2];
     // c. gradient over the logits, in place
@@ -354,13 +337,7 @@ static bool ht_big_tiles(int64_t rows, int64_t cols) { return ((rows + 127) / 12
 static bool ht_pos(double v) { return std::isfinite(v) && v > 0.0; }
 
 extern "C" int pg_head_train_plan(int C, int32_t out[4]) {
-    if (!out) { pg_set_error("head_train_plan: null argument out"); return PG_EINVAL; }
-    if (C < 1) { pg_set_error("head_train_plan: C must be at least 1 (got %d)", C); return PG_EINVAL; }
-    out[0] = C > HT_LDS_CELLS ? 1 : 0;
-    out[1] = C > HT_LDS_CELLS ? 0 : (int32_t)((size_t)C * sizeof(double));
-    out[2] = HT_LDS_CELLS;
-    out[3] = HT_THREADS;
-    return PG_OK;
+    return row_cells_plan("head_train_plan", C, HT_LDS_CELLS, sizeof(double), HT_THREADS, out);
 }
 
 extern "C" int pg_head_train_loss(const float* emb, int B, int P, const float* W, const float* bias, const double* centroids, int C,
@@ -372,14 +349,14 @@ extern "C" int pg_head_train_loss(const float* emb, int B, int P, const float* W
     if (!ht_pos(tau)) { pg_set_error("head_train_loss: tau = %g must be finite and positive", tau); return PG_EINVAL; }
     if (!std::isfinite(grad_scale)) { pg_set_error("head_train_loss: grad_scale = %g must be finite", grad_scale); return PG_EINVAL; }
     if (B == 0) return PG_OK;                              // nothing to do: the (empty) buffers may be NULL
-    if (!emb) { pg_set_error("head_train_loss: null argument emb"); return PG_EINVAL; }
-    if (!W) { pg_set_error("head_train_loss: null argument W"); return PG_EINVAL; }
-    if (!bias) { pg_set_error("head_train_loss: null argument bias"); return PG_EINVAL; }
+    PG_NEED("head_train_loss", emb);
+    PG_NEED("head_train_loss", W);
+    PG_NEED("head_train_loss", bias);
     if (!labels_llh && !labels_clf) { pg_set_error("head_train_loss: null arguments labels_llh and labels_clf (one is needed)"); return PG_EINVAL; }
-    if (labels_llh && !centroids) { pg_set_error("head_train_loss: null argument centroids"); return PG_EINVAL; }
-    if (!xbar) { pg_set_error("head_train_loss: null argument xbar"); return PG_EINVAL; }
-    if (!g) { pg_set_error("head_train_loss: null argument g"); return PG_EINVAL; }
-    if (!loss_rows) { pg_set_error("head_train_loss: null argument loss_rows"); return PG_EINVAL; }
+    if (labels_llh) PG_NEED("head_train_loss", centroids);
+    PG_NEED("head_train_loss", xbar);
+    PG_NEED("head_train_loss", g);
+    PG_NEED("head_train_loss", loss_rows);
     hipStream_t s = (hipStream_t)stream;
     const int64_t n = (int64_t)B * VIT_HIDDEN;
     hipLaunchKernelGGL(ht_xbar_kernel, dim3((unsigned)((n + HT_THREADS - 1) / HT_THREADS)), dim3(HT_THREADS), 0, s, emb, n, P, xbar);
@@ -391,24 +368,12 @@ extern "C" int pg_head_train_loss(const float* emb, int B, int P, const float* W
         hipLaunchKernelGGL(ht_logits_kernel<1>, dim3((C + 63) / 64, (B + 63) / 64), dim3(HT_THREADS), 0, s, xbar, W, bias, B, C, g);
     rc = pg_check_launch("head_train_loss (logits)");
     if (rc) return rc;
-    if (C > HT_LDS_CELLS) {
-        double* scratch = nullptr;
-        PG_HIP(hipMallocAsync((void**)&scratch, (size_t)B * (size_t)C * sizeof(double), s));
-        hipLaunchKernelGGL(ht_row_kernel<true>, dim3(B), dim3(HT_THREADS), 0, s, g, C, centroids, labels_llh, labels_clf, tau, grad_scale,
-                           loss_rows, logits, scratch);
-        rc = pg_check_launch("head_train_loss (rows, large C)");
-        (void)hipFreeAsync(scratch, s);
-        return rc;
-    }
-    const size_t lds = (size_t)C * sizeof(double);
-    static size_t attr_lds = 0;
-    if (lds > attr_lds) {
-        PG_HIP(hipFuncSetAttribute((const void*)ht_row_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        attr_lds = lds;
-    }
-    hipLaunchKernelGGL(ht_row_kernel<false>, dim3(B), dim3(HT_THREADS), lds, s, g, C, centroids, labels_llh, labels_clf, tau, grad_scale,
-                       loss_rows, logits, (double*)nullptr);
-    return pg_check_launch("head_train_loss (rows)");
+    return row_cells_launch<ht_row_kernel<false>, ht_row_kernel<true>>(
+        "head_train_loss (rows)", "head_train_loss (rows, large C)", B, C, HT_LDS_CELLS, sizeof(double), s,
+        [&](auto kernel, size_t lds, void* scratch) {
+            hipLaunchKernelGGL(kernel, dim3(B), dim3(HT_THREADS), lds, s, g, C, centroids, labels_llh, labels_clf, tau, grad_scale, loss_rows,
+                               logits, (double*)scratch);
+        });
 }
 
 extern "C" int pg_head_train_update(const float* g, const float* xbar, int B, int C, float* W, float* bias, float* m_W, float* v_W,
@@ -425,14 +390,14 @@ extern "C" int pg_head_train_update(const float* g, const float* xbar, int B, in
         pg_set_error("head_train_update: weight_decay = %g must be finite and not negative", weight_decay); return PG_EINVAL;
     }
     if (B == 0) return PG_OK;
-    if (!g) { pg_set_error("head_train_update: null argument g"); return PG_EINVAL; }
-    if (!xbar) { pg_set_error("head_train_update: null argument xbar"); return PG_EINVAL; }
-    if (!W) { pg_set_error("head_train_update: null argument W"); return PG_EINVAL; }
-    if (!bias) { pg_set_error("head_train_update: null argument bias"); return PG_EINVAL; }
-    if (!m_W) { pg_set_error("head_train_update: null argument m_W"); return PG_EINVAL; }
-    if (!v_W) { pg_set_error("head_train_update: null argument v_W"); return PG_EINVAL; }
-    if (!m_b) { pg_set_error("head_train_update: null argument m_b"); return PG_EINVAL; }
-    if (!v_b) { pg_set_error("head_train_update: null argument v_b"); return PG_EINVAL; }
+    PG_NEED("head_train_update", g);
+    PG_NEED("head_train_update", xbar);
+    PG_NEED("head_train_update", W);
+    PG_NEED("head_train_update", bias);
+    PG_NEED("head_train_update", m_W);
+    PG_NEED("head_train_update", v_W);
+    PG_NEED("head_train_update", m_b);
+    PG_NEED("head_train_update", v_b);
     HtAdam A;
     A.decay = (float)(1.0 - lr * weight_decay);
     A.b1 = (float)beta1; A.omb1 = (float)(1.0 - beta1);

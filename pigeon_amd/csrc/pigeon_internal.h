@@ -54,6 +54,12 @@ enum PgGemmKernel { PG_GK_NONE = -1, PG_GK_PP6 = 0, PG_GK_PP = 1, PG_GK_MID = 2,
         }                                                                                     \
     } while (0)
 
+// a required pointer argument of entry point `who` (a string literal): PG_EINVAL naming it
+#define PG_NEED(who, p)                                                                       \
+    do {                                                                                      \
+        if (!(p)) { pg_set_error(who ": null argument " #p); return PG_EINVAL; }              \
+    } while (0)
+
 // fingerprint.hip: the digests (definition: that file's header) of n device buffers on the current device -- 16-byte aligned, or
 // PG_EINVAL before any launch -- in two launches and one copy back for all of them; out[2 i], out[2 i + 1] (HOST) = buffer i's.
 // Synchronises `stream`.  pg_fingerprint_host: the same function of a HOST buffer (pg_vit_fingerprint folds its table with it).

@@ -15,45 +15,26 @@
 //      a monotone step function of that integer (every addition of a fixed-order sum of non-negative terms is monotone).  All nq
 //      quantiles bisect [0, bits(+inf)] together, one masked sum per quantile and step, at most 63 steps; the smallest pattern with
 //      M >= q Z is a key.
-// Every sum over cells -- Z, the two numerators, every M -- is the same sequence of additions: thread t adds its cells in ascending
-// order, the 64 lanes of a wave combine in a butterfly, the four waves as (w0 + w1) + (w2 + w3).  It depends on C only: no atomics, no
-// dependence on B, G, the row's position or its alignment (step 1 decides where a load goes, never what is added to what).  A masked
-// cell adds +0.0, which leaves a non-negative partial sum unchanged, so M(+inf) is Z bit for bit and q = 1 needs no tolerance.
-// The (key, weight) pairs live in LDS up to SPREAD_LDS_CELLS cells (GLOBAL = false) and in a stream-ordered device scratch above
-// (GLOBAL = true, as pg_head_forward's row kernel): the same arithmetic in the same order, the same bits.
+// Every sum over cells -- Z, the two numerators, every M -- is row_block.h's one summation order: it depends on C only, not on B, G,
+// the row's position or its alignment (step 1 decides where a load goes, never what is added to what).  A masked cell adds +0.0, so
+// M(+inf) is Z bit for bit and q = 1 needs no tolerance.  The (key, weight) pairs are the cells that row_block.h keeps in LDS or in
+// scratch.
 // No input value forms an address or bounds a loop: a NaN or +inf logit, a row of -inf only, a non-finite point, and a key that is
 // not a finite non-negative number (non-finite centroid or extent) give NaN in every output of that (row, point) and nothing else.
 #include "common.h"
 #include "pigeon_internal.h"
 #include "haversine.h"
+#include "row_block.h"
 
 #include <cmath>
 
 #define SPREAD_THREADS 256
-#define SPREAD_LDS_CELLS 9600                        // 16 bytes a cell: 150 KB of the CU's 160 KB, as the head's row kernel
+#define SPREAD_CELL_BYTES (2 * sizeof(double))       // key and weight
+#define SPREAD_LDS_CELLS row_lds_cells(SPREAD_CELL_BYTES)
 #define SPREAD_MAX_Q 4
-#define SPREAD_SCORE_MAX 5000.0
-#define SPREAD_DECAY_KM 1492.7                       // pigeon_amd/config.py DECAY_CONSTANT
 #define SPREAD_INF_BITS 0x7ff0000000000000ull
 
 struct SpreadQuantiles { double q[SPREAD_MAX_Q]; };
-
-// the one summation order: v[0..3] of every thread -> the block's sums, identical in every thread.  `red` alternates between two
-// buffers (slot), so one barrier per call is enough: a wave reaches the second next call only after every wave has read this one.
-__device__ __forceinline__ void spread_block_sum(double v[SPREAD_MAX_Q], double (*red)[4][SPREAD_MAX_Q], int slot) {
-#pragma unroll
-    for (int j = 0; j < SPREAD_MAX_Q; ++j) {
-#pragma unroll
-        for (int o = 32; o >= 1; o >>= 1) v[j] += __shfl_xor(v[j], o, 64);
-    }
-    if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-        for (int j = 0; j < SPREAD_MAX_Q; ++j) red[slot][threadIdx.x >> 6][j] = v[j];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int j = 0; j < SPREAD_MAX_Q; ++j) v[j] = (red[slot][0][j] + red[slot][1][j]) + (red[slot][2][j] + red[slot][3][j]);
-}
 
 template <bool GLOBAL>
 __global__ __launch_bounds__(SPREAD_THREADS) void guess_spread_kernel(const float* __restrict__ logits, int C,
@@ -63,6 +44,8 @@ __global__ __launch_bounds__(SPREAD_THREADS) void guess_spread_kernel(const floa
                                                                       double* __restrict__ expected_km, double* __restrict__ expected_score,
                                                                       double* __restrict__ radius_km, double* __restrict__ scratch) {
     extern __shared__ __attribute__((aligned(16))) double spread_cells[];
+    // block_sum alternates between the two slots, so its one barrier per call is enough: a wave reaches the second next call only
+    // after every wave has read this one
     __shared__ double red[2][4][SPREAD_MAX_Q];
     __shared__ float redmax[4];
     __shared__ int redbad[2][4];
@@ -98,14 +81,8 @@ __global__ __launch_bounds__(SPREAD_THREADS) void guess_spread_kernel(const floa
     }
     const double plng = points[2 * pair], plat = points[2 * pair + 1];
     bad |= !(fabs(plng) < INFINITY && fabs(plat) < INFINITY);
-    mx = wave_max(mx);
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) bad |= __shfl_xor(bad, o, 64);
-    if ((tid & 63) == 0) { redmax[tid >> 6] = mx; redbad[0][tid >> 6] = bad; }
     if (GLOBAL) __threadfence_block();                 // the staged row is global memory: visible to the block's next pass
-    __syncthreads();
-    mx = fmaxf(fmaxf(redmax[0], redmax[1]), fmaxf(redmax[2], redmax[3]));
-    bad = redbad[0][0] | redbad[0][1] | redbad[0][2] | redbad[0][3];
+    block_max_flag(mx, bad, redmax, redbad[0]);
     bad |= !(mx > -INFINITY);                          // a row of -inf only
     const double m = (double)mx;
 
@@ -121,13 +98,13 @@ __global__ __launch_bounds__(SPREAD_THREADS) void guess_spread_kernel(const floa
             wts[c] = w;
             acc[0] += w;
             acc[1] += w * d;
-            acc[2] += w * SPREAD_SCORE_MAX * exp(-d / SPREAD_DECAY_KM);
+            acc[2] += w * PG_SCORE_MAX * exp(-d / PG_SCORE_DECAY_KM);
         }
     }
 #pragma unroll
     for (int o = 32; o >= 1; o >>= 1) bad |= __shfl_xor(bad, o, 64);
     if ((tid & 63) == 0) redbad[1][tid >> 6] = bad;
-    spread_block_sum(acc, red, 0);
+    block_sum(acc, red[0]);
     bad = redbad[1][0] | redbad[1][1] | redbad[1][2] | redbad[1][3];
     if (bad) {                                         // uniform
         if (tid == 0) { expected_km[pair] = NAN; expected_score[pair] = NAN; }
@@ -159,7 +136,7 @@ __global__ __launch_bounds__(SPREAD_THREADS) void guess_spread_kernel(const floa
 #pragma unroll
             for (int j = 0; j < SPREAD_MAX_Q; ++j) ms[j] += k <= mid[j] ? w : 0.0;
         }
-        spread_block_sum(ms, red, step & 1);
+        block_sum(ms, red[step & 1]);
 #pragma unroll
         for (int j = 0; j < SPREAD_MAX_Q; ++j) {
             if (lo[j] < hi[j]) {
@@ -175,13 +152,7 @@ __global__ __launch_bounds__(SPREAD_THREADS) void guess_spread_kernel(const floa
 }
 
 extern "C" int pg_guess_spread_plan(int C, int32_t out[4]) {
-    if (!out) { pg_set_error("guess_spread_plan: null argument out"); return PG_EINVAL; }
-    if (C < 1) { pg_set_error("guess_spread_plan: C must be at least 1 (got %d)", C); return PG_EINVAL; }
-    out[0] = C > SPREAD_LDS_CELLS ? 1 : 0;
-    out[1] = C > SPREAD_LDS_CELLS ? 0 : (int32_t)((size_t)C * 2 * sizeof(double));
-    out[2] = SPREAD_LDS_CELLS;
-    out[3] = SPREAD_THREADS;
-    return PG_OK;
+    return row_cells_plan("guess_spread_plan", C, SPREAD_LDS_CELLS, SPREAD_CELL_BYTES, SPREAD_THREADS, out);
 }
 
 extern "C" int pg_guess_spread(const float* logits, int B, int C, const double* centroids, const double* extent_km, const double* points,
@@ -191,7 +162,7 @@ extern "C" int pg_guess_spread(const float* logits, int B, int C, const double* 
     if (G < 0) { pg_set_error("guess_spread: G = %d", G); return PG_EINVAL; }
     if (C < 1) { pg_set_error("guess_spread: C must be at least 1 (got %d)", C); return PG_EINVAL; }
     if (nq < 1 || nq > SPREAD_MAX_Q) { pg_set_error("guess_spread: nq must be 1 .. %d (got %d)", SPREAD_MAX_Q, nq); return PG_EINVAL; }
-    if (!quantiles) { pg_set_error("guess_spread: null argument quantiles"); return PG_EINVAL; }
+    PG_NEED("guess_spread", quantiles);
     SpreadQuantiles Q = {{1.0, 1.0, 1.0, 1.0}};
     for (int j = 0; j < nq; ++j) {
         if (!(quantiles[j] > 0.0 && quantiles[j] <= 1.0)) {
@@ -200,31 +171,19 @@ extern "C" int pg_guess_spread(const float* logits, int B, int C, const double* 
         Q.q[j] = quantiles[j];
     }
     if (B == 0 || G == 0) return PG_OK;                    // nothing to do: the (empty) buffers may be NULL
-    if (!logits) { pg_set_error("guess_spread: null argument logits"); return PG_EINVAL; }
-    if (!centroids) { pg_set_error("guess_spread: null argument centroids"); return PG_EINVAL; }
-    if (!points) { pg_set_error("guess_spread: null argument points"); return PG_EINVAL; }
-    if (!expected_km) { pg_set_error("guess_spread: null argument expected_km"); return PG_EINVAL; }
-    if (!expected_score) { pg_set_error("guess_spread: null argument expected_score"); return PG_EINVAL; }
-    if (!radius_km) { pg_set_error("guess_spread: null argument radius_km"); return PG_EINVAL; }
+    PG_NEED("guess_spread", logits);
+    PG_NEED("guess_spread", centroids);
+    PG_NEED("guess_spread", points);
+    PG_NEED("guess_spread", expected_km);
+    PG_NEED("guess_spread", expected_score);
+    PG_NEED("guess_spread", radius_km);
     const int64_t pairs = (int64_t)B * G;
     if (pairs > 0x7fffffffLL) { pg_set_error("guess_spread: B * G = %lld exceeds 2^31 - 1", (long long)pairs); return PG_EINVAL; }
     hipStream_t s = (hipStream_t)stream;
-    if (C > SPREAD_LDS_CELLS) {
-        double* scratch = nullptr;
-        PG_HIP(hipMallocAsync((void**)&scratch, (size_t)pairs * 2 * (size_t)C * sizeof(double), s));
-        hipLaunchKernelGGL(guess_spread_kernel<true>, dim3((unsigned)pairs), dim3(SPREAD_THREADS), 0, s, logits, C, centroids, extent_km,
-                           points, G, Q, nq, expected_km, expected_score, radius_km, scratch);
-        const int rc = pg_check_launch("guess_spread (large C)");
-        (void)hipFreeAsync(scratch, s);
-        return rc;
-    }
-    const size_t lds = (size_t)C * 2 * sizeof(double);
-    static size_t attr_lds = 0;
-    if (lds > attr_lds) {
-        PG_HIP(hipFuncSetAttribute((const void*)guess_spread_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        attr_lds = lds;
-    }
-    hipLaunchKernelGGL(guess_spread_kernel<false>, dim3((unsigned)pairs), dim3(SPREAD_THREADS), lds, s, logits, C, centroids, extent_km,
-                       points, G, Q, nq, expected_km, expected_score, radius_km, (double*)nullptr);
-    return pg_check_launch("guess_spread");
+    return row_cells_launch<guess_spread_kernel<false>, guess_spread_kernel<true>>(
+        "guess_spread", "guess_spread (large C)", pairs, C, SPREAD_LDS_CELLS, SPREAD_CELL_BYTES, s,
+        [&](auto kernel, size_t lds, void* scratch) {
+            hipLaunchKernelGGL(kernel, dim3((unsigned)pairs), dim3(SPREAD_THREADS), lds, s, logits, C, centroids, extent_km, points, G, Q, nq,
+                               expected_km, expected_score, radius_km, (double*)scratch);
+        });
 }
