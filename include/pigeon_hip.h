@@ -55,7 +55,9 @@ extern "C" {
                               *    + pg_equirect_plan, pg_equirect_forward, pg_eq_view and pg_eq_item, additive;
                               *    + pg_guess_spread, pg_guess_spread_plan, additive;
                               *    + pg_head_train_loss, pg_head_train_update, pg_head_train_plan, additive;
-                              *    + pg_score_table, pg_guess_best, pg_guess_best_plan, additive) */
+                              *    + pg_score_table, pg_guess_best, pg_guess_best_plan, additive;
+                              *    + pg_knn_prepare, pg_knn_workspace_bytes, pg_knn_search, pg_knn_plan, pg_tune_knn_spans and pg_knn_bank,
+                              *      additive) */
 
 const char* pg_last_error(void);
 int pg_abi_version(void);
@@ -775,6 +777,59 @@ int pg_guess_best(const float* logits, int B, int C, const double* table, int M,
  *   out[6]  threads of a workgroup
  *   out[7]  candidate tiles = partials per row that the second pass reads */
 int pg_guess_best_plan(int B, int C, int M, int32_t out[8]);
+
+/* ------------------------------------------------------------------------------------------------
+ * The k nearest rows of an embedding bank, exactly (csrc/knn.hip; restated in tests/_knnref.py).
+ *
+ * Distance.  For a query q and a bank row x, 1024 fp32 each:
+ *     acc = 0.f;  for j = 0 .. 1023 ascending:  t = q[j] - x[j] (one fp32 rounding);  acc = fmaf(t, t, acc);     d2(q, x) = acc
+ * One fixed order: a pair's bits depend on nothing else (not on B, n, the pair's position, the launch geometry or the path taken);
+ * identical rows give exactly 0.f.  It is the square of the refiner's L2.
+ * Result.  Per query the k rows of smallest d2, ascending; ties go to the lower row; a NaN distance ranks after every number (after
+ * +inf), ties again by row, and is returned as a NaN.  idx (B,k) int64, d2 (B,k) fp32; positions past min(k, n - excluded) hold
+ * -1 / +inf.  exclude (B) int64 or NULL: a row that query b must not return (any value that is no row, -1 for instance: none).
+ * The result is ALWAYS that, the top k of the exact distance over the whole bank; how it is reached is mode's business:
+ *   mode 0  a 16-bit MFMA pass over x16 keeps the 128 rows of smallest a(q,x) = hn[x] - q16 . x16 per query (never a B x n matrix),
+ *           d2 is computed for those and sorted, and a query is CERTIFIED when its k-th d2 is strictly below what any other row could
+ *           reach given a rigorous bound on the 16-bit pass's error (derivation: knn.hip); the exact tier, d2 over every
+ *           row, is enqueued behind it and its workgroups return at once for certified queries.  No host synchronisation.
+ *           certified[b] = 1 where the certificate held, 0 where the exact tier answered.  n <= 128 certifies every query.
+ *   mode 1  the exact tier only (bank->x16, hn and stats may be NULL); certified = 1.
+ *   mode 2  a diagnostic: what the 16-bit pass and the rerank alone return, with their flags; an uncertified answer may be wrong.
+ * pg_knn_prepare: x DEVICE (n,1024) fp32 -> x16 DEVICE (n,1024) fp16 (round to nearest even), hn DEVICE (n) fp32 = 0.5 sum x_j^2
+ * (summed in fp64, rounded once), stats DEVICE uint64[4]: [0] the fp32 bits of the largest hn among rows fp16 can hold (xmax^2 / 2),
+ * [1] the number of values that are not finite or exceed 65504 in magnitude, [2] the fp32 bits of the largest magnitude fp16 can
+ * hold, [3] 0.  A bank with stats[1] != 0 is searched by the exact tier only (mode 2 then returns -1 / +inf and no flag).
+ * The stated limit: exact for the embeddings it is given; the encoder's own error is not modelled here.
+ * Limits: 1 <= k <= 64, 0 <= B <= 262144, 0 <= n <= 2^31 - 16; B == 0 is a no-op; n == 0 fills -1 / +inf.  x, x16, q 16-byte and the
+ * workspace 256-byte aligned.  Every refusal is PG_EINVAL naming the argument, before any HIP call: a null bank, q, idx, d2, a null
+ * array of the bank that the mode reads, a null or short workspace (pg_knn_workspace_bytes of the same n, B, k).  certified may be
+ * NULL.  Asynchronous on `stream`. */
+typedef struct pg_knn_bank {
+    const float* x;          /* (n,1024) fp32 */
+    const void* x16;         /* (n,1024) fp16, pg_knn_prepare's */
+    const float* hn;         /* (n) fp32, pg_knn_prepare's */
+    const uint64_t* stats;   /* uint64[4], pg_knn_prepare's */
+    int64_t n;
+} pg_knn_bank;
+int pg_knn_prepare(const float* x, int64_t n, void* x16, float* hn, uint64_t* stats, void* stream);
+int pg_knn_workspace_bytes(int64_t n, int B, int k, size_t* bytes);
+int pg_knn_search(const pg_knn_bank* bank, const float* q, int B, int k, const int64_t* exclude, int mode, int64_t* idx, float* d2,
+                  uint8_t* certified, void* workspace, size_t workspace_bytes, void* stream);
+/* What pg_knn_search does with these sizes (host arithmetic, no GPU; PG_EINVAL as pg_knn_search's for the three sizes):
+ *   out[0]  K' = 128, the candidates kept per query
+ *   out[1]  bank rows per tile of the 16-bit pass (a wave owns 32 consecutive rows of it)
+ *   out[2]  queries per workgroup of the 16-bit pass; the bank is streamed once per ceil(B / out[2])
+ *   out[3]  spans = workgroups per query tile; span s owns tiles [s out[5], (s + 1) out[5]), those past the last tile own nothing
+ *   out[4]  bytes of dynamic LDS of the 16-bit pass
+ *   out[5]  tiles per span
+ *   out[6]  bank rows per tile of the exact tier
+ *   out[7]  spans of the exact tier */
+int pg_knn_plan(int64_t n, int B, int k, int32_t out[8]);
+/* Forces the number of spans of both passes (0 = the defaults: one per tile up to 256 and 512), so that a small bank exercises several
+ * tiles per span, more spans than tiles and the span edges.  The result is the same bits.  PG_EINVAL outside 0 .. 4096.  It changes
+ * pg_knn_workspace_bytes: size the workspace after it. */
+int pg_tune_knn_spans(int spans);
 
 /* ------------------------------------------------------------------------------------------------
  * Training the geocell head on embeddings (csrc/head_train.hip): one step of cell_layer = Linear(1024 -> C) under the reference's

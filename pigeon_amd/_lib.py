@@ -32,6 +32,11 @@ class Bank(C.Structure):
                 ("num_cells", C.c_int64), ("num_protos", C.c_int64), ("num_train", C.c_int64)]
 
 
+class KnnBank(C.Structure):
+    """pg_knn_bank (include/pigeon_hip.h): the fp32 bank, pg_knn_prepare's three arrays, the row count."""
+    _fields_ = [("x", C.c_void_p), ("x16", C.c_void_p), ("hn", C.c_void_p), ("stats", C.c_void_p), ("n", C.c_int64)]
+
+
 class RegionBankStruct(C.Structure):
     """pg_region_bank (include/pigeon_hip.h): five device arrays, the host copies of the two offset arrays, three counts."""
     _fields_ = [("region_off", C.c_void_p), ("ring_off", C.c_void_p), ("xy", C.c_void_p), ("ring_bbox", C.c_void_p),
@@ -156,6 +161,11 @@ SIGNATURES = {
     "pg_score_table": (_I, [_P, _I, _P, _I, _I, _P, _P]),
     "pg_guess_best": (_I, [_P, _I, _I, _P, _I, _I, _P, _P, _P, _P]),
     "pg_guess_best_plan": (_I, [_I, _I, _I, C.POINTER(C.c_int32)]),
+    "pg_knn_prepare": (_I, [_P, _I64, _P, _P, _P, _P]),
+    "pg_knn_workspace_bytes": (_I, [_I64, _I, _I, C.POINTER(_SZ)]),
+    "pg_knn_search": (_I, [C.POINTER(KnnBank), _P, _I, _I, _P, _I, _P, _P, _P, _P, _SZ, _P]),
+    "pg_knn_plan": (_I, [_I64, _I, _I, C.POINTER(C.c_int32)]),
+    "pg_tune_knn_spans": (_I, [_I]),
     "pg_haversine_blocks": (_I, [_P, _P, _P, _I, _D, _P, _P]),
     "pg_optics_graph": (_I, [_P, _P, _P, _I, _I, _P, _P, _P, _P, _P]),
     "pg_optics_plan": (_I, [_I64, _I, C.POINTER(C.c_int32)]),

@@ -114,6 +114,21 @@ def best_guess_metrics(best_llh, distances_fn, labels, taken) -> Dict[str, float
             'Best_guess_changed': float(np.mean(np.asarray(taken, dtype=bool)))}
 
 
+def neighbour_metrics(nn_lnglat, distances_fn, labels, preds) -> Dict[str, float]:
+    """The retrieval baseline: the existing km and score metrics with the NEAREST training row's coordinates (`nn_lnglat` (N,K,2),
+    column 0) as the guess, and the share of items on which that guess is closer to the truth than the model's final one."""
+    labels = np.asarray(labels)
+    d = distances_fn(np.asarray(nn_lnglat)[:, 0, :].astype(np.float64), labels)
+    return {'Mean_km_error_nn': np.mean(d), 'Median_km_error_nn': np.median(d), 'Geoguessr_score_nn': geoguessr_score(d),
+            'NN_beats_model': float(np.mean(d < distances_fn(np.asarray(preds), labels)))}
+
+
+def _neighbour_index(refiner, neighbours):
+    """`neighbours=K` of evaluate_model / serve: K checked, and the search index over the refiner's bank (borrowed fp32 rows)."""
+    from .neighbours import index_of
+    return int(neighbours), index_of(refiner, neighbours, 'neighbours=K')
+
+
 def _class_labels(labels) -> np.ndarray:
     labels = np.asarray(labels)
     return np.argmax(labels, axis=-1) if labels.ndim > 1 else labels          # (N, classes) one-hot / probabilities, or (N,) indices
@@ -282,7 +297,7 @@ class ImageEvalDataset:
 
 def evaluate_model(model: SuperGuessr, dataset, metrics: Optional[Callable] = None, train_args=None,
                    refiner: Optional[ProtoRefiner] = None, yfcc: bool = False, writer=None, step: int = 0,
-                   batch_size: Optional[int] = None, num_workers: int = 0, spread=None, best_guess=None):
+                   batch_size: Optional[int] = None, num_workers: int = 0, spread=None, best_guess=None, neighbours=None):
     """reference training/train_eval_loop.py:35-161 (eval loop :77-112).
 
     dataset items are dicts of forward() keyword arguments (pixel_values | pixel_bytes | embedding, labels, labels_clf, ...), or
@@ -298,8 +313,14 @@ def evaluate_model(model: SuperGuessr, dataset, metrics: Optional[Callable] = No
     ['best_index'], ['best_expected'], ['best_taken'] (N,); when the dataset has a `labels` column also Mean_km_error_best,
     Median_km_error_best, Geoguessr_score_best (the existing metric functions on best_LLH) and Best_guess_changed, the share of rows
     taken.  Every other key is computed as without it.
+    `neighbours` (K in 1..64; default None: nothing is computed, nothing is launched): the K nearest rows of the refiner's bank of
+    training embeddings for every finished batch's final embedding (`pigeon_amd.neighbours`, exact for the embedding it is given),
+    on device tensors without a host synchronisation: results['nn_rows'], ['nn_distance'] (N,K), ['nn_lnglat'] (N,K,2),
+    ['nn_certified'] (N,); when the dataset has a `labels` column also Mean_km_error_nn, Median_km_error_nn, Geoguessr_score_nn (the
+    nearest row's coordinates as the guess) and NN_beats_model.  Needs a refiner (ValueError without).
     """
     from torch.utils.data import DataLoader
+    nn_k, nn_index = _neighbour_index(refiner, neighbours) if neighbours is not None else (None, None)
     logger.warning('Starting evaluation ...')
     if batch_size is None:
         batch_size = getattr(train_args, 'per_device_eval_batch_size', EVAL_BATCH_SIZE_PER_GPU)
@@ -317,6 +338,7 @@ def evaluate_model(model: SuperGuessr, dataset, metrics: Optional[Callable] = No
     combined_certain = []
     combined_spread = []
     combined_best = []
+    combined_nn = []
     n_seen = 0
     # The reference's loop (:77-112) computes a batch and appends its predictions; the predictions are only read after the loop
     # (:114-140).  Here a batch's rows that the 16-bit encoder cannot settle are queued on the device and re-encoded by the exact
@@ -353,6 +375,8 @@ def evaluate_model(model: SuperGuessr, dataset, metrics: Optional[Callable] = No
                 combined_spread.append(_final_spread(model, res['state'], res['state'].get('refined_LLH') if refiner is not None else None, spread))
             if best_guess is not None:
                 combined_best.append(_final_best_guess(model, res['state'], res['state'].get('refined_LLH') if refiner is not None else None, best_guess))
+            if nn_index is not None:
+                combined_nn.append(nn_index.search(res['state']['embedding'], k=nn_k))
             n_seen += outputs.preds_geocell.shape[0]
 
     with torch.no_grad():
@@ -405,6 +429,16 @@ def evaluate_model(model: SuperGuessr, dataset, metrics: Optional[Callable] = No
         best_extra = {}
         if true_lla is not None and len(true_lla) == len(preds):
             best_extra = best_guess_metrics(results['best_LLH'], haversine_np, true_lla, results['best_taken'])
+    nn_extra = {}
+    if nn_index is not None:
+        results.update(nn_rows=to_np([n.rows for n in combined_nn]), nn_distance=to_np([n.distance for n in combined_nn]),
+                       nn_lnglat=to_np([n.lnglat for n in combined_nn]), nn_certified=to_np([n.certified for n in combined_nn]))
+        try:
+            true_lla = np.asarray(dataset['labels'])
+        except (KeyError, IndexError, TypeError, ValueError):
+            true_lla = None
+        if true_lla is not None and len(true_lla) == len(preds) and len(preds):
+            nn_extra = neighbour_metrics(results['nn_lnglat'], haversine_np, true_lla, preds)
     if metrics is not None:                                                       # :122-140
         labels_lla, labels_cell = dataset['labels'], dataset['labels_clf']
         if isinstance(labels_lla, np.ndarray) == False:
@@ -417,6 +451,7 @@ def evaluate_model(model: SuperGuessr, dataset, metrics: Optional[Callable] = No
                                 labels_lla, labels_cell, labels_mt, labels_climate, labels_month)))
     if best_guess is not None:
         results.update(best_extra)
+    results.update(nn_extra)
     model.train()
     logger.warning('Back to training ...')
     return results
@@ -426,7 +461,7 @@ def evaluate(model: str, dataset, yfcc: bool, landmarks: bool, base_model=None, 
              refine: bool = True, geocell_path: Optional[str] = None, proto_path: Optional[str] = None,
              dataset_path=None, bank=None, head_state: Optional[str] = None, multi_task: bool = False,
              calibration: Optional[str] = None, embedding_rel_tol: Optional[float] = None, country_path: Optional[str] = None,
-             bank_rel_tol=None, spread=None, best_guess=None):
+             bank_rel_tol=None, spread=None, best_guess=None, neighbours=None):
     """reference evaluation/evaluate.py:10-85.
 
     `base_model`: as in the reference a STRING -- config.CLIP_MODEL for the pretrained tower, or the path of a checkpoint whose
@@ -456,6 +491,7 @@ def evaluate(model: str, dataset, yfcc: bool, landmarks: bool, base_model=None, 
     config.COUNTRY_PATH names if it exists, else the key is left out as before; a path given explicitly must exist.
     `spread`: quantiles handed to `evaluate_model(spread=...)`; None (default): no spread is computed.
     `best_guess`: 'score' | 'km', handed to `evaluate_model(best_guess=...)`; None (default): nothing is computed.
+    `neighbours`: K, handed to `evaluate_model(neighbours=...)` (needs refine=True); None (default): nothing is computed.
     """
     import os
     from . import config as cfg
@@ -540,7 +576,7 @@ def evaluate(model: str, dataset, yfcc: bool, landmarks: bool, base_model=None, 
         if refiner.bank_rel_tol > 0:
             print(f'Prototype bank declared at a relative error of {refiner.bank_rel_tol:.3g}: the refiner\'s certainty accounts for it')
     metrics = compute_geoguessr_metrics if countries is None else (lambda r: compute_geoguessr_metrics(r, countries=countries))
-    results = evaluate_model(full_model, dataset, metrics, None, refiner, spread=spread, best_guess=best_guess)
+    results = evaluate_model(full_model, dataset, metrics, None, refiner, spread=spread, best_guess=best_guess, neighbours=neighbours)
     if write_calibration:
         if full_model.base_model is not None and full_model.certainty.calibrated:
             full_model.save_calibration(calibration, source=f'evaluate, first batch, {full_model.certainty.stats.get("samples")} samples')

@@ -345,6 +345,111 @@ def guess_best_plan(B: int, C_cells: int, M: int) -> dict:
             "workgroups": int(o[4]), "scratch_bytes": int(o[5]), "threads": int(o[6]), "candidate_tiles": int(o[7])}
 
 
+# ----------------------------------------------------------------------------------------- nearest rows of the embedding bank
+KNN_MODES = {"auto": 0, "exact": 1, "filter": 2}
+
+
+class KnnBank:
+    """What pg_knn_search reads of a bank: the caller's fp32 rows (borrowed, not copied) and pg_knn_prepare's fp16 copy, half
+    squared norms and statistics.  `bad_values`, `xmax` and `max_abs` read the statistics back (one host synchronisation each)."""
+
+    def __init__(self, x: torch.Tensor, x16: Optional[torch.Tensor], hn: Optional[torch.Tensor], stats: Optional[torch.Tensor]):
+        self.x, self.x16, self.hn, self.stats = x, x16, hn, stats
+        self.n = int(x.shape[0])
+
+    def struct(self) -> _lib.KnnBank:
+        return _lib.KnnBank(x=self.x.data_ptr() if self.n else None, x16=None if self.x16 is None else self.x16.data_ptr(),
+                            hn=None if self.hn is None else self.hn.data_ptr(), stats=None if self.stats is None else self.stats.data_ptr(),
+                            n=self.n)
+
+    def _stat_f32(self, i: int) -> float:
+        return float(self.stats[i:i + 1].to(torch.int32).view(torch.float32).item())
+
+    @property
+    def bad_values(self) -> int:
+        return int(self.stats[1].item())
+
+    @property
+    def xmax(self) -> float:
+        """The largest row norm among the rows fp16 can hold (from the fp32 half squared norm)."""
+        return (2.0 * self._stat_f32(0)) ** 0.5
+
+    @property
+    def max_abs(self) -> float:
+        return self._stat_f32(2)
+
+
+def knn_prepare(x: torch.Tensor) -> KnnBank:
+    """pg_knn_prepare: x (N,1024) fp32 -> KnnBank with x16 (N,1024) fp16, hn (N,) fp32 and stats (4,) int64 on x's device; another
+    N * 2052 bytes.  x is kept by reference.  No host synchronisation."""
+    _dev(x, torch.float32); _shape(x, "x", None, HIDDEN)
+    N = int(x.shape[0])
+    x16 = torch.empty((N, HIDDEN), dtype=torch.float16, device=x.device)
+    hn = torch.empty((N,), dtype=torch.float32, device=x.device)
+    stats = torch.empty((4,), dtype=torch.int64, device=x.device)
+    with torch.cuda.device(x.device):
+        check(load().pg_knn_prepare(_p(x), N, _p(x16), _p(hn), _p(stats), _stream()), "pg_knn_prepare")
+    return KnnBank(x, x16, hn, stats)
+
+
+def knn_workspace_bytes(n: int, B: int, k: int) -> int:
+    out = C.c_size_t(0)
+    check(load().pg_knn_workspace_bytes(int(n), int(B), int(k), C.byref(out)), "pg_knn_workspace_bytes")
+    return int(out.value)
+
+
+def knn_search(bank: KnnBank, q: torch.Tensor, k: int, exclude: Optional[torch.Tensor] = None, mode: str = "auto",
+               workspace: Optional[torch.Tensor] = None):
+    """pg_knn_search: q (B,1024) fp32 -> (idx (B,k) int64, d2 (B,k) fp32, certified (B,) uint8): the k bank rows of smallest exact
+    d2 per query, ascending, ties to the lower row, -1 / +inf past the bank's end.  exclude (B,) int64: a row query b must not
+    return.  mode 'auto' (16-bit pass, certificate, exact tier for the rest), 'exact' (the exact tier only) or 'filter' (the 16-bit
+    pass alone: a diagnostic).  The contract is include/pigeon_hip.h's.  No host synchronisation."""
+    if not isinstance(bank, KnnBank):
+        raise _lib.PigeonHipError(f"knn_search: bank must be a KnnBank (knn_prepare), got {type(bank).__name__}")
+    if mode not in KNN_MODES:
+        raise _lib.PigeonHipError(f"knn_search: mode must be one of {sorted(KNN_MODES)}, got {mode!r}")
+    _dev(q, torch.float32); _shape(q, "q", None, HIDDEN)
+    _dev(bank.x, torch.float32); _shape(bank.x, "bank.x", None, HIDDEN)
+    _same_device("knn_search", "bank.x", bank.x, q=q, exclude=exclude, x16=bank.x16, hn=bank.hn, stats=bank.stats, workspace=workspace)
+    B, k = int(q.shape[0]), int(k)
+    if mode != "exact" and (bank.x16 is None or bank.hn is None or bank.stats is None):
+        raise _lib.PigeonHipError(f"knn_search: mode {mode!r} needs a bank from knn_prepare (x16, hn, stats)")
+    if bank.x16 is not None:
+        _dev(bank.x16, torch.float16); _shape(bank.x16, "bank.x16", bank.n, HIDDEN)
+        _dev(bank.hn, torch.float32); _shape(bank.hn, "bank.hn", bank.n)
+        _dev(bank.stats, torch.int64); _shape(bank.stats, "bank.stats", 4)
+    if exclude is not None:
+        _dev(exclude, torch.int64); _shape(exclude, "exclude", B)
+    need = knn_workspace_bytes(bank.n, B, k)                  # refuses k, B and n by name
+    if workspace is None:
+        workspace = torch.empty((need + 256,), dtype=torch.uint8, device=q.device)
+    else:
+        _dev(workspace, torch.uint8)
+    off = (-workspace.data_ptr()) % 256
+    ws_bytes = max(0, workspace.numel() - off)
+    idx = torch.empty((B, k), dtype=torch.int64, device=q.device)
+    d2 = torch.empty((B, k), dtype=torch.float32, device=q.device)
+    cert = torch.empty((B,), dtype=torch.uint8, device=q.device)
+    s = bank.struct()
+    with torch.cuda.device(q.device):
+        check(load().pg_knn_search(C.byref(s), _p(q), B, k, _p(exclude), KNN_MODES[mode], _p(idx), _p(d2), _p(cert),
+                                   C.c_void_p(workspace.data_ptr() + off), ws_bytes, _stream()), "pg_knn_search")
+    return idx, d2, cert
+
+
+def knn_plan(n: int, B: int, k: int) -> dict:
+    """pg_knn_plan: what pg_knn_search does with n rows, B queries and k neighbours (host arithmetic, no GPU)."""
+    o = (C.c_int32 * 8)()
+    check(load().pg_knn_plan(int(n), int(B), int(k), o), "pg_knn_plan")
+    return {"candidates": int(o[0]), "rows_per_tile": int(o[1]), "queries_per_tile": int(o[2]), "spans": int(o[3]), "lds_bytes": int(o[4]),
+            "tiles_per_span": int(o[5]), "exact_rows_per_tile": int(o[6]), "exact_spans": int(o[7])}
+
+
+def tune_knn_spans(spans: int) -> None:
+    """pg_tune_knn_spans: force the number of spans of both passes (0 = the defaults)."""
+    check(load().pg_tune_knn_spans(int(spans)), "pg_tune_knn_spans")
+
+
 # ----------------------------------------------------------------------------------------- training the head
 def _same_device(who: str, ref_name: str, ref: torch.Tensor, **tensors):
     for name, t in tensors.items():

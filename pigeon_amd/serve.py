@@ -90,7 +90,7 @@ def panorama_from_request(body: Dict, encoded: bool = False):
 
 
 def predict_panorama(views: Sequence, model, refiner=None, preprocess: Optional[Callable] = None, attribution: bool = False,
-                     spread: bool = False, best_guess: bool = False) -> Dict:
+                     spread: bool = False, best_guess: bool = False, neighbours: Optional[int] = None) -> Dict:
     """views: four PIL images (or the EquirectRequest of a `panorama` body) -> {'lat', 'lng'} (+ 'geocell_margin', 'geocell_certain', 'reencoded_exact' when the model exposes the
     certainty of its top-1).  `preprocess(list of PIL) -> (4,3,336,336)` defaults to the GPU path.  Views that are all `bytes` (image
     files) go to the same path undecoded: baseline JPEGs are decoded on the GPU (pigeon_amd/jpeg.py: Pillow's pixels, bit for bit),
@@ -103,8 +103,14 @@ def predict_panorama(views: Sequence, model, refiner=None, preprocess: Optional[
     best_guess=True answers with the point of the largest expected GeoGuessr score (`model.best_guess` over the geocell centroids, the
     former answer as the incumbent): 'lat' / 'lng' become the chosen point -- the extension reads nothing else --, the former answer
     moves to 'argmax_lat' / 'argmax_lng', and 'guess_expected_score' and 'guess_changed' are added.  The `spread` keys, when asked
-    for as well, still describe the former answer."""
+    for as well, still describe the former answer.
+    neighbours=K (1..64) adds 'neighbours': [{'lat', 'lng', 'distance', 'row'}, ...], the K training panoramas whose embeddings are
+    nearest to this one's (exact search over the refiner's bank, pigeon_amd/neighbours.py), nearest first; it needs a refiner."""
     import torch
+    nn_index = None
+    if neighbours is not None:
+        from .neighbours import index_of
+        nn_index = index_of(refiner, neighbours, "predict_panorama(neighbours=K)")
     if best_guess and not hasattr(model, "best_guess"):
         raise ValueError("predict_panorama(best_guess=True): this model has no `best_guess` (it needs SuperGuessr.best_guess)")
     bg = None
@@ -178,6 +184,11 @@ def predict_panorama(views: Sequence, model, refiner=None, preprocess: Optional[
         res["expected_km"] = float(sp.expected_km.reshape(-1)[0])
         res["expected_score"] = float(sp.expected_score.reshape(-1)[0])
         res["radius_km"] = {f"{q:g}": float(r) for q, r in zip(sp.quantiles, sp.radius_km.reshape(-1, len(sp.quantiles))[0].tolist())}
+    if nn_index is not None:
+        nn = nn_index.search(embedding.reshape(1, -1, embedding.shape[-1]) if embedding.dim() > 2 else embedding.reshape(1, -1), k=neighbours)
+        rows, dist, ll = nn.rows[0].tolist(), nn.distance[0].tolist(), nn.lnglat[0].tolist()
+        res["neighbours"] = [{"lat": float(p[1]), "lng": float(p[0]), "distance": float(d), "row": int(r)}
+                             for r, d, p in zip(rows, dist, ll) if r >= 0]
     if attribution:
         from .explain import attribution_json
         with torch.no_grad():
@@ -187,11 +198,15 @@ def predict_panorama(views: Sequence, model, refiner=None, preprocess: Optional[
 
 
 def make_app(model, refiner=None, preprocess: Optional[Callable] = None, game_log: Optional[List] = None, encoded: bool = False,
-             spread: bool = False, best_guess: bool = False):
+             spread: bool = False, best_guess: bool = False, neighbours: Optional[int] = None):
     """Starlette application with the two routes the extension calls.  encoded=True: the payloads are handed on as bytes and decoded
     on the GPU (see predict_panorama); the response is the same.  spread=True: every answer carries 'expected_km', 'expected_score'
     and 'radius_km' (see predict_panorama); a model without `spread` is refused here, not per request.  best_guess=True: every answer
-    is the point of the largest expected score (see predict_panorama); a model without `best_guess` is refused here as well."""
+    is the point of the largest expected score (see predict_panorama); a model without `best_guess` is refused here as well.  neighbours=K: every answer carries its K nearest
+    training panoramas (see predict_panorama); refused here without a refiner bank, and the search index is built here, not per request."""
+    if neighbours is not None:
+        from .neighbours import index_of
+        index_of(refiner, neighbours, "make_app(neighbours=K)")
     if best_guess and not hasattr(model, "best_guess"):
         raise ValueError("make_app(best_guess=True): this model has no `best_guess` (it needs SuperGuessr.best_guess)")
     if spread and not hasattr(model, "spread"):
@@ -213,7 +228,8 @@ def make_app(model, refiner=None, preprocess: Optional[Callable] = None, game_lo
         # called inline on the event loop, on purpose: the handles behind `model` are one per (device, stream) and not
         # thread-safe, so requests are answered one at a time -- a `def` handler would run in Starlette's pool
         try:
-            res = predict_panorama(views, model, refiner, preprocess, attribution=attribution, spread=spread, best_guess=best_guess)
+            res = predict_panorama(views, model, refiner, preprocess, attribution=attribution, spread=spread, best_guess=best_guess,
+                                   neighbours=neighbours)
         except BadRequest as e:                                    # (encoded mode: the payloads are only decoded in there)
             return JSONResponse({"error": str(e)}, status_code=400)
         return JSONResponse({"gameID": body.get("gameID"), "roundID": body.get("roundID"), "results": res})
@@ -232,10 +248,14 @@ def make_app(model, refiner=None, preprocess: Optional[Callable] = None, game_lo
 
 
 def main(argv=None):
-    """python -m pigeon_amd.serve --head <head.model> [--geocells <csv>] [--protos <csv> --dataset <dir>] [--calibration <file>] [--spread] [--guess expected-score] [--port 5000]"""
+    """python -m pigeon_amd.serve --head <head.model> [--geocells <csv>] [--protos <csv> --dataset <dir>] [--calibration <file>] [--spread] [--guess expected-score] [--neighbours K] [--port 5000]"""
     import os
     ap = _arg_parser()
     args = ap.parse_args(argv)
+    if args.neighbours is not None and not args.protos:
+        ap.error("--neighbours K searches the refiner's bank of training embeddings: give --protos and --dataset")
+    if args.neighbours is not None and not 1 <= args.neighbours <= 64:
+        ap.error(f"--neighbours must be in 1..64, got {args.neighbours}")
     if args.calibration and not os.path.exists(args.calibration):
         ap.error(f"--calibration {args.calibration}: no such file (the server only loads a calibration; write one with "
                  "`python -m pigeon_amd.calibrate` or `run.py evaluate --calibration`)")
@@ -260,7 +280,8 @@ def main(argv=None):
               f"{model.certainty.describe()}")
     refiner = ProtoRefiner(proto_path=args.protos, dataset_path=args.dataset) if args.protos else None
     torch.cuda.synchronize()
-    uvicorn.run(make_app(model, refiner, encoded=args.encoded, spread=args.spread, best_guess=args.guess == "expected-score"), host=args.host, port=args.port)
+    uvicorn.run(make_app(model, refiner, encoded=args.encoded, spread=args.spread, best_guess=args.guess == "expected-score",
+                         neighbours=args.neighbours), host=args.host, port=args.port)
 
 
 def _arg_parser():
@@ -283,6 +304,9 @@ def _arg_parser():
     ap.add_argument("--guess", choices=("expected-score",), default=None,
                     help="answer with the point of the largest expected GeoGuessr score under the head's probabilities (SuperGuessr.best_guess "
                          "over the geocell centroids): lat / lng become that point, the former answer moves to argmax_lat / argmax_lng")
+    ap.add_argument("--neighbours", type=int, default=None, metavar="K",
+                    help="add to every answer its K (1..64) nearest training panoramas, neighbours: [{lat, lng, distance, row}, ...] "
+                         "(exact search over the refiner's bank of training embeddings); needs --protos and --dataset")
     ap.add_argument("--host", default="127.0.0.1")
     ap.add_argument("--port", type=int, default=5000)
     ap.add_argument("--calibration", default=None, metavar="FILE",

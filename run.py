@@ -101,6 +101,9 @@ argp.add_argument('--spread', action='store_true', default=False,
                   help="evaluate: how far off every guess may be (SuperGuessr.spread: expected km, expected GeoGuessr score, the radii "
                        "holding 0.5 and 0.9 of the head's probability) and, against the labels, how often the truth lies inside them "
                        "(Radius_50_coverage / Radius_90_coverage, to be read against 0.5 and 0.9)")
+argp.add_argument('--neighbours', type=int, default=None, metavar='K',
+                  help="evaluate: also the K (1..64) nearest training embeddings of every item (exact search over the refiner's bank, "
+                       "pigeon_amd.neighbours) and the retrieval baseline's _nn metrics: the nearest row's coordinates as the guess")
 argp.add_argument('--countries', default=None, metavar='FILE',
                   help="evaluate: GeoJSON of country polygons (Polygon / MultiPolygon features) for `Country_accuracy`; default: "
                        "config.COUNTRY_PATH if that file exists, else the key is left out")
@@ -283,7 +286,7 @@ def _dispatch(args, comm):
                            landmarks=args.landmarks, geocell_path=geocell_path, bank=bank, heading=args.heading,
                            multi_task=args.multitask, calibration=args.calibration, embedding_rel_tol=args.embedding_rel_tol,
                            country_path=args.countries, bank_rel_tol=args.bank_rel_tol, spread=(0.5, 0.9) if args.spread else None,
-                           best_guess={'expected-score': 'score', 'expected-km': 'km'}.get(args.guess))
+                           best_guess={'expected-score': 'score', 'expected-km': 'km'}.get(args.guess), neighbours=args.neighbours)
         _print_fallbacks(comm)
         if comm.is_main_process:
             print({k: (v if not hasattr(v, 'shape') or v.shape == () else tuple(v.shape)) for k, v in results.items() if k != 'exact_passes'})
@@ -297,6 +300,10 @@ def _dispatch(args, comm):
                       f"{results['Mean_km_error']:.1f} -> {results['Mean_km_error_best']:.1f} km, median {results['Median_km_error']:.1f} -> "
                       f"{results['Median_km_error_best']:.1f} km, GeoGuessr score {results['Geoguessr_score']:.0f} -> "
                       f"{results['Geoguessr_score_best']:.0f}")
+            if 'Geoguessr_score_nn' in results:
+                print(f"nearest training row as the guess: mean error {results['Mean_km_error_nn']:.1f} km, median "
+                      f"{results['Median_km_error_nn']:.1f} km, GeoGuessr score {results['Geoguessr_score_nn']:.0f}; closer than the "
+                      f"model's guess on {results['NN_beats_model']:.1%} of the items")
             if 'geocell_certain' in results:
                 # beyond the reference's output: how many samples' discrete outputs are certain to be the fp32 reference's (a z ~ 4
                 # statistical statement, pigeon_amd/certainty.py), and how many are near-ties of the reference itself
