@@ -57,7 +57,8 @@ extern "C" {
                               *    + pg_head_train_loss, pg_head_train_update, pg_head_train_plan, additive;
                               *    + pg_score_table, pg_guess_best, pg_guess_best_plan, additive;
                               *    + pg_knn_prepare, pg_knn_workspace_bytes, pg_knn_search, pg_knn_plan, pg_tune_knn_spans and pg_knn_bank,
-                              *      additive) */
+                              *      additive;
+                              *    + pg_temper_stats, pg_temper_logits, pg_temper_plan, additive) */
 
 const char* pg_last_error(void);
 int pg_abi_version(void);
@@ -777,6 +778,50 @@ int pg_guess_best(const float* logits, int B, int C, const double* table, int M,
  *   out[6]  threads of a workgroup
  *   out[7]  candidate tiles = partials per row that the second pass reads */
 int pg_guess_best_plan(int B, int C, int M, int32_t out[8]);
+
+/* ------------------------------------------------------------------------------------------------
+ * Calibrated head probabilities (csrc/temper.hip): the statistics a temperature is fitted with, and the calibrated logits.  The
+ * reference has no code for it; the contract is this project's own and is restated in tests/_tempref.py.  With beta = 1 / T the
+ * calibrated probabilities are softmax(beta * l); the total negative log-likelihood of the labels is convex in beta.
+ *
+ * pg_temper_stats.  logits DEVICE (N,C) fp32; labels DEVICE (N,) int64; betas HOST K doubles, K 1 .. 16, each finite and positive;
+ * row_stats DEVICE (N,K,3) fp64 or NULL; conf DEVICE (N,K) fp64 or NULL; state DEVICE (N,) uint8 or NULL; totals DEVICE (K,3) fp64;
+ * counts DEVICE (2,) int64.  Per row n with label y = labels[n], all arithmetic in float64:
+ *   m = max_c l[n,c]      a = the first index that attains it (torch.argmax's order)      x_c = (double)l[n,c] - (double)m
+ *   per beta_k:  w_c = exp(beta_k * x_c)      Z = sum_c w_c      A = sum_c w_c * x_c      Q = sum_c (w_c * x_c) * x_c
+ *   row_stats[n,k,0] = log(Z) - beta_k * x_y                           the negative log-likelihood of the label
+ *   row_stats[n,k,1] = A / Z - x_y                                     its first derivative in beta
+ *   row_stats[n,k,2] = max(0, Q / Z - (A / Z) * (A / Z))               its second derivative in beta
+ *   conf[n,k]        = 1.0 / Z                                         the probability of the argmax
+ *   state[n]         = 0: valid, a != y;  1: valid, a == y;  2: invalid
+ * A -inf logit is a cell of weight +0.0 (a masked cell): it adds +0.0 to every sum, never 0 * inf.  A row is invalid when its label
+ * is outside [0, C), when a logit is NaN or +inf, when every logit is -inf, or when the label's logit is -inf; an invalid row gets NaN
+ * row_stats and conf and touches no other row.  x_y is picked by the comparison c == y: no input value forms an address or bounds a
+ * loop.
+ *   totals[k,j] = sum over the valid rows of row_stats[n,k,j]          an invalid row adds +0.0
+ *   counts      = { valid rows, valid rows of state 1 }
+ * totals and counts are written whether or not row_stats and state are given (the per-row values then live in stream-ordered
+ * scratch, pg_temper_plan's out[3] bytes at the most).
+ * Every sum over cells is taken in one fixed order that depends on C only, and the sum over rows in one that depends on N only (no
+ * atomics): a row's outputs are the same bits alone, inside any batch, at any position, at any position of its beta inside betas,
+ * with any K and with or without the optional outputs.  The order over rows: thread t of 256 adds rows t, t + 256, ... ascending,
+ * the 64 lanes of a wave combine as v += v(lane xor o), o = 32 .. 1, and the four waves as (w0 + w1) + (w2 + w3).
+ * N == 0 writes zero totals and counts.  PG_EINVAL, naming the argument and before any HIP call, for a negative N (or one above
+ * 2^31 - 1), C < 1, K outside 1 .. 16, a beta that is not finite and positive, and a null logits, labels, betas, totals or counts.
+ *
+ * pg_temper_logits.  out[n,c] = l[n,c] * (float)beta: one correctly rounded fp32 multiplication; -inf, NaN and +inf pass through.
+ * logits, out DEVICE (N,C) fp32, out may alias logits.  N == 0 is a no-op.  PG_EINVAL for a negative N, C < 1, a beta that is not
+ * finite and positive and a null pointer.
+ * ------------------------------------------------------------------------------------------------ */
+int pg_temper_stats(const float* logits, int64_t N, int C, const int64_t* labels, const double* betas, int K, double* row_stats,
+                    double* conf, uint8_t* state, double* totals, int64_t* counts, void* stream);
+int pg_temper_logits(const float* logits, int64_t N, int C, double beta, float* out, void* stream);
+/* What pg_temper_stats does with these shapes (host arithmetic, no GPU; PG_EINVAL as pg_temper_stats's for the three sizes):
+ *   out[0]  threads of a workgroup; there is one workgroup per row
+ *   out[1]  betas per pass over a row: the row is read 1 + ceil(K / out[1]) times (the bits do not depend on the grouping)
+ *   out[2]  workgroups of the totals pass: one per (k, j) and one for the counts
+ *   out[3]  bytes of stream-ordered scratch of a call without row_stats and state (saturates at 2^31 - 1) */
+int pg_temper_plan(int64_t N, int C, int K, int32_t out[4]);
 
 /* ------------------------------------------------------------------------------------------------
  * The k nearest rows of an embedding bank, exactly (csrc/knn.hip; restated in tests/_knnref.py).

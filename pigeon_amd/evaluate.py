@@ -461,7 +461,7 @@ def evaluate(model: str, dataset, yfcc: bool, landmarks: bool, base_model=None, 
              refine: bool = True, geocell_path: Optional[str] = None, proto_path: Optional[str] = None,
              dataset_path=None, bank=None, head_state: Optional[str] = None, multi_task: bool = False,
              calibration: Optional[str] = None, embedding_rel_tol: Optional[float] = None, country_path: Optional[str] = None,
-             bank_rel_tol=None, spread=None, best_guess=None, neighbours=None):
+             bank_rel_tol=None, spread=None, best_guess=None, neighbours=None, temperature=None):
     """reference evaluation/evaluate.py:10-85.
 
     `base_model`: as in the reference a STRING -- config.CLIP_MODEL for the pretrained tower, or the path of a checkpoint whose
@@ -492,6 +492,10 @@ def evaluate(model: str, dataset, yfcc: bool, landmarks: bool, base_model=None, 
     `spread`: quantiles handed to `evaluate_model(spread=...)`; None (default): no spread is computed.
     `best_guess`: 'score' | 'km', handed to `evaluate_model(best_guess=...)`; None (default): nothing is computed.
     `neighbours`: K, handed to `evaluate_model(neighbours=...)` (needs refine=True); None (default): nothing is computed.
+    `temperature`: a number, or the path of the sidecar `python -m pigeon_amd.temperature` wrote for this head (loaded AFTER the
+    weights; another head's raises, both fingerprints named): `SuperGuessr.temperature`, so the spread and best-guess metrics are
+    computed under the calibrated probabilities, and results['Temperature'] is printed with the metrics.  None (default): nothing
+    changes.  The accuracy and distance metrics of the model's own guess do not depend on it.
     """
     import os
     from . import config as cfg
@@ -544,6 +548,9 @@ def evaluate(model: str, dataset, yfcc: bool, landmarks: bool, base_model=None, 
             print(f'Loaded calibration {calibration} (fingerprint {header["fingerprint"]}, {header["samples"]} samples; {header["source"]})')
         else:
             write_calibration = int(os.environ.get('RANK', '0')) == 0
+    if temperature is not None:
+        full_model.load_temperature(temperature)
+        print(f'Temperature {full_model.temperature:.6g}: spread and best-guess metrics under softmax(logits / T)')
     refiner = None
     bank_tol = _resolve_bank_rel_tol(bank_rel_tol, full_model)
     if refine:
@@ -577,6 +584,9 @@ def evaluate(model: str, dataset, yfcc: bool, landmarks: bool, base_model=None, 
             print(f'Prototype bank declared at a relative error of {refiner.bank_rel_tol:.3g}: the refiner\'s certainty accounts for it')
     metrics = compute_geoguessr_metrics if countries is None else (lambda r: compute_geoguessr_metrics(r, countries=countries))
     results = evaluate_model(full_model, dataset, metrics, None, refiner, spread=spread, best_guess=best_guess, neighbours=neighbours)
+    if temperature is not None:
+        results['Temperature'] = full_model.temperature
+        print(f"Temperature: {results['Temperature']:.6g}")
     if write_calibration:
         if full_model.base_model is not None and full_model.certainty.calibrated:
             full_model.save_calibration(calibration, source=f'evaluate, first batch, {full_model.certainty.stats.get("samples")} samples')

@@ -345,6 +345,62 @@ def guess_best_plan(B: int, C_cells: int, M: int) -> dict:
             "workgroups": int(o[4]), "scratch_bytes": int(o[5]), "threads": int(o[6]), "candidate_tiles": int(o[7])}
 
 
+# ----------------------------------------------------------------------------------------- calibrated head probabilities
+def temper_stats(logits: torch.Tensor, labels: torch.Tensor, betas, row_stats: bool = False, conf: bool = False, state: bool = False,
+                 out: Optional[Dict[str, torch.Tensor]] = None) -> Dict[str, torch.Tensor]:
+    """pg_temper_stats: logits (N,C) fp32, labels (N,) int64, betas 1 .. 16 finite positive numbers (host) -> dict(totals (K,3) fp64,
+    counts (2,) int64) plus, where asked for, row_stats (N,K,3) fp64, conf (N,K) fp64 and state (N,) uint8.  The contract is
+    include/pigeon_hip.h's.  `out` supplies output tensors by those names (a name in `out` is asked for).  No host synchronisation."""
+    _dev(logits, torch.float32); _shape(logits, "logits", None, None)
+    N, Cn = int(logits.shape[0]), int(logits.shape[1])
+    _dev(labels, torch.int64); _shape(labels, "labels", N)
+    if labels.device != logits.device:
+        raise _lib.PigeonHipError(f"temper_stats: labels is on {labels.device}, logits on {logits.device}")
+    bs = [float(b) for b in betas]
+    K = len(bs)
+    if not 1 <= K <= 16:
+        raise _lib.PigeonHipError(f"temper_stats: betas must hold 1 .. 16 numbers, got {K}")
+    out = dict(out) if out is not None else {}
+    shapes = {"totals": ((K, 3), torch.float64), "counts": ((2,), torch.int64)}
+    for name, want, shape, dt in (("row_stats", row_stats, (N, K, 3), torch.float64), ("conf", conf, (N, K), torch.float64),
+                                  ("state", state, (N,), torch.uint8)):
+        if want or name in out:
+            shapes[name] = (shape, dt)
+    for name, (shape, dt) in shapes.items():
+        if name not in out:
+            out[name] = torch.empty(shape, dtype=dt, device=logits.device)
+        _dev(out[name], dt); _shape(out[name], name, *shape)
+        if out[name].device != logits.device:
+            raise _lib.PigeonHipError(f"temper_stats: {name} is on {out[name].device}, logits on {logits.device}")
+    barr = (C.c_double * K)(*bs)
+    with torch.cuda.device(logits.device):
+        check(load().pg_temper_stats(_p(logits), N, Cn, _p(labels), barr, K, _p(out.get("row_stats")), _p(out.get("conf")),
+                                     _p(out.get("state")), _p(out["totals"]), _p(out["counts"]), _stream()), "pg_temper_stats")
+    return {k: out[k] for k in shapes}
+
+
+def temper_logits(logits: torch.Tensor, beta: float, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """pg_temper_logits: logits (N,C) fp32 -> logits * float32(beta), one rounded multiplication an element; `out` may be `logits`.
+    No host synchronisation."""
+    _dev(logits, torch.float32); _shape(logits, "logits", None, None)
+    N, Cn = int(logits.shape[0]), int(logits.shape[1])
+    if out is None:
+        out = torch.empty_like(logits)
+    _dev(out, torch.float32); _shape(out, "out", N, Cn)
+    if out.device != logits.device:
+        raise _lib.PigeonHipError(f"temper_logits: out is on {out.device}, logits on {logits.device}")
+    with torch.cuda.device(logits.device):
+        check(load().pg_temper_logits(_p(logits), N, Cn, float(beta), _p(out), _stream()), "pg_temper_logits")
+    return out
+
+
+def temper_plan(N: int, C_cells: int, K: int) -> dict:
+    """pg_temper_plan: what pg_temper_stats does with N rows, C cells and K betas (host arithmetic, no GPU)."""
+    o = (C.c_int32 * 4)()
+    check(load().pg_temper_plan(int(N), int(C_cells), int(K), o), "pg_temper_plan")
+    return {"threads": int(o[0]), "betas_per_pass": int(o[1]), "totals_workgroups": int(o[2]), "scratch_bytes": int(o[3])}
+
+
 # ----------------------------------------------------------------------------------------- nearest rows of the embedding bank
 KNN_MODES = {"auto": 0, "exact": 1, "filter": 2}
 

@@ -90,7 +90,7 @@ def panorama_from_request(body: Dict, encoded: bool = False):
 
 
 def predict_panorama(views: Sequence, model, refiner=None, preprocess: Optional[Callable] = None, attribution: bool = False,
-                     spread: bool = False, best_guess: bool = False, neighbours: Optional[int] = None) -> Dict:
+                     spread: bool = False, best_guess: bool = False, neighbours: Optional[int] = None, confidence: bool = False) -> Dict:
     """views: four PIL images (or the EquirectRequest of a `panorama` body) -> {'lat', 'lng'} (+ 'geocell_margin', 'geocell_certain', 'reencoded_exact' when the model exposes the
     certainty of its top-1).  `preprocess(list of PIL) -> (4,3,336,336)` defaults to the GPU path.  Views that are all `bytes` (image
     files) go to the same path undecoded: baseline JPEGs are decoded on the GPU (pigeon_amd/jpeg.py: Pillow's pixels, bit for bit),
@@ -105,8 +105,12 @@ def predict_panorama(views: Sequence, model, refiner=None, preprocess: Optional[
     moves to 'argmax_lat' / 'argmax_lng', and 'guess_expected_score' and 'guess_changed' are added.  The `spread` keys, when asked
     for as well, still describe the former answer.
     neighbours=K (1..64) adds 'neighbours': [{'lat', 'lng', 'distance', 'row'}, ...], the K training panoramas whose embeddings are
-    nearest to this one's (exact search over the refiner's bank, pigeon_amd/neighbours.py), nearest first; it needs a refiner."""
+    nearest to this one's (exact search over the refiner's bank, pigeon_amd/neighbours.py), nearest first; it needs a refiner.
+    confidence=True adds 'confidence', a float: the probability of the top-1 geocell under softmax(logits / model.temperature)
+    (`model.confidence`, one pg_temper_stats row pass); `spread` and `best_guess` integrate over the same calibrated probabilities."""
     import torch
+    if confidence and not hasattr(model, "confidence"):
+        raise ValueError("predict_panorama(confidence=True): this model has no `confidence` (it needs SuperGuessr.confidence)")
     nn_index = None
     if neighbours is not None:
         from .neighbours import index_of
@@ -180,6 +184,8 @@ def predict_panorama(views: Sequence, model, refiner=None, preprocess: Optional[
         res["geocell_margin"] = float(model.last_margin.reshape(-1)[0])
         res["geocell_certain"] = bool(model.last_certain.reshape(-1)[0])
         res["reencoded_exact"] = bool(getattr(model, "last_reencoded", None) is not None and model.last_reencoded.numel() > 0)
+    if confidence:
+        res["confidence"] = float(model.confidence().reshape(-1)[0])
     if sp is not None:                                             # extra keys as well: the extension reads lat / lng only
         res["expected_km"] = float(sp.expected_km.reshape(-1)[0])
         res["expected_score"] = float(sp.expected_score.reshape(-1)[0])
@@ -198,12 +204,15 @@ def predict_panorama(views: Sequence, model, refiner=None, preprocess: Optional[
 
 
 def make_app(model, refiner=None, preprocess: Optional[Callable] = None, game_log: Optional[List] = None, encoded: bool = False,
-             spread: bool = False, best_guess: bool = False, neighbours: Optional[int] = None):
+             spread: bool = False, best_guess: bool = False, neighbours: Optional[int] = None, confidence: bool = False):
     """Starlette application with the two routes the extension calls.  encoded=True: the payloads are handed on as bytes and decoded
     on the GPU (see predict_panorama); the response is the same.  spread=True: every answer carries 'expected_km', 'expected_score'
     and 'radius_km' (see predict_panorama); a model without `spread` is refused here, not per request.  best_guess=True: every answer
     is the point of the largest expected score (see predict_panorama); a model without `best_guess` is refused here as well.  neighbours=K: every answer carries its K nearest
-    training panoramas (see predict_panorama); refused here without a refiner bank, and the search index is built here, not per request."""
+    training panoramas (see predict_panorama); refused here without a refiner bank, and the search index is built here, not per request.
+    confidence=True: every answer carries 'confidence', the calibrated top-1 probability (see predict_panorama)."""
+    if confidence and not hasattr(model, "confidence"):
+        raise ValueError("make_app(confidence=True): this model has no `confidence` (it needs SuperGuessr.confidence)")
     if neighbours is not None:
         from .neighbours import index_of
         index_of(refiner, neighbours, "make_app(neighbours=K)")
@@ -229,7 +238,7 @@ def make_app(model, refiner=None, preprocess: Optional[Callable] = None, game_lo
         # thread-safe, so requests are answered one at a time -- a `def` handler would run in Starlette's pool
         try:
             res = predict_panorama(views, model, refiner, preprocess, attribution=attribution, spread=spread, best_guess=best_guess,
-                                   neighbours=neighbours)
+                                   neighbours=neighbours, confidence=confidence)
         except BadRequest as e:                                    # (encoded mode: the payloads are only decoded in there)
             return JSONResponse({"error": str(e)}, status_code=400)
         return JSONResponse({"gameID": body.get("gameID"), "roundID": body.get("roundID"), "results": res})
@@ -248,7 +257,7 @@ def make_app(model, refiner=None, preprocess: Optional[Callable] = None, game_lo
 
 
 def main(argv=None):
-    """python -m pigeon_amd.serve --head <head.model> [--geocells <csv>] [--protos <csv> --dataset <dir>] [--calibration <file>] [--spread] [--guess expected-score] [--neighbours K] [--port 5000]"""
+    """python -m pigeon_amd.serve --head <head.model> [--geocells <csv>] [--protos <csv> --dataset <dir>] [--calibration <file>] [--spread] [--guess expected-score] [--neighbours K] [--temperature FILE|NUMBER] [--port 5000]"""
     import os
     ap = _arg_parser()
     args = ap.parse_args(argv)
@@ -278,10 +287,13 @@ def main(argv=None):
         header = model.load_calibration(args.calibration)
         print(f"[serve] calibration {args.calibration}: fingerprint {header['fingerprint']}, {header['samples']} samples; "
               f"{model.certainty.describe()}")
+    if args.temperature is not None:                                   # after the weights: a sidecar is keyed to the head
+        model.load_temperature(args.temperature)
+        print(f"[serve] temperature {model.temperature:.6g}: spread, best guess and `confidence` under softmax(logits / T)")
     refiner = ProtoRefiner(proto_path=args.protos, dataset_path=args.dataset) if args.protos else None
     torch.cuda.synchronize()
     uvicorn.run(make_app(model, refiner, encoded=args.encoded, spread=args.spread, best_guess=args.guess == "expected-score",
-                         neighbours=args.neighbours), host=args.host, port=args.port)
+                         neighbours=args.neighbours, confidence=args.temperature is not None), host=args.host, port=args.port)
 
 
 def _arg_parser():
@@ -307,6 +319,10 @@ def _arg_parser():
     ap.add_argument("--neighbours", type=int, default=None, metavar="K",
                     help="add to every answer its K (1..64) nearest training panoramas, neighbours: [{lat, lng, distance, row}, ...] "
                          "(exact search over the refiner's bank of training embeddings); needs --protos and --dataset")
+    ap.add_argument("--temperature", default=None, metavar="FILE|NUMBER",
+                    help="the temperature of the head's probabilities: a number, or the sidecar `python -m pigeon_amd.temperature` wrote "
+                         "for this head (as in `run.py evaluate --temperature`); every answer gains `confidence`, the calibrated "
+                         "top-1 probability, and --spread / --guess use the calibrated probabilities")
     ap.add_argument("--host", default="127.0.0.1")
     ap.add_argument("--port", type=int, default=5000)
     ap.add_argument("--calibration", default=None, metavar="FILE",

@@ -11,6 +11,7 @@ neither (models/README.md).  Training is out of scope: the losses are computed f
 """
 from __future__ import annotations
 
+import math
 import os
 from collections import namedtuple
 
@@ -152,6 +153,8 @@ class SuperGuessr(nn.Module):
         self._cal_buffer = []                                # pixels of small first batches, until there are enough to calibrate on
         self._engines = {}                                   # refiner -> settle-before-return engine (see `engine`)
         self._guess_tables = {}                              # objective -> (key, candidates, table): see best_guess()
+        self._temperature = 1.0                              # see `temperature`
+        self.temperature_fit = None                          # the TemperatureFit behind it, when it came from a sidecar
         self._last_exact = None
         self._rel_tol0 = self.certainty.rel_tol              # the constructor's uncalibrated tolerance: what a weight load goes back to
         if self.exact_top1 and isinstance(self.base_model, HipCLIPVisionModel):
@@ -192,6 +195,53 @@ class SuperGuessr(nn.Module):
     @embedding_rel_tol.setter
     def embedding_rel_tol(self, v):
         self._embedding_rel_tol = None if v is None else float(v)
+
+    @property
+    def temperature(self) -> float:
+        """The temperature T of the calibrated probabilities softmax(logits / T) that `spread` and `best_guess` integrate over
+        (pigeon_amd/temperature.py fits it; default 1.0: the head's own softmax, and nothing new runs).  Unchanged at any
+        temperature, and reference-parity: the argmax, the top-k indices, the `topk_values` the reference's outputs carry, the
+        refiner's inputs and every certainty computation -- they read the head's own logits."""
+        return self._temperature
+
+    @temperature.setter
+    def temperature(self, v: float):
+        v = float(v)
+        if not (math.isfinite(v) and v > 0):
+            raise ValueError(f'SuperGuessr.temperature must be a finite positive number, got {v!r}')
+        self._temperature = v
+        self.temperature_fit = None
+
+    def load_temperature(self, path_or_number) -> float:
+        """Set `temperature` from a number or from the sidecar `pigeon_amd.temperature.save` wrote for THIS head (ValueError naming
+        both fingerprints for another head's).  Load it after the weights."""
+        from . import temperature as _temperature
+        if isinstance(path_or_number, (int, float)):
+            self.temperature = path_or_number
+            return self._temperature
+        try:
+            number = float(path_or_number)
+        except (TypeError, ValueError):
+            number = None
+        if number is not None:
+            self.temperature = number
+            return self._temperature
+        fit = _temperature.load(path_or_number, self)
+        self.temperature = fit.temperature
+        self.temperature_fit = fit
+        return self._temperature
+
+    def _calibrated_logits(self, st: dict) -> Tensor:
+        """The logits `spread` and `best_guess` integrate over: the state's own at temperature 1.0 (nothing runs, nothing is kept),
+        else logits * float32(1 / T) -- one pg_temper_logits launch per state and temperature, cached in the state."""
+        logits = st['logits']
+        if self._temperature == 1.0:
+            return logits
+        key = (self._temperature, logits.data_ptr(), tuple(logits.shape), logits._version)
+        hit = st.get('calibrated_logits')
+        if hit is None or hit[0] != key:
+            hit = st['calibrated_logits'] = (key, hip_ops.temper_logits(logits, 1.0 / self._temperature))
+        return hit[1]
 
     def _set_hidden_size(self):
         if self.base_model is not None:
@@ -251,6 +301,8 @@ class SuperGuessr(nn.Module):
         self._cal_buffer = []
         self._engines = {}
         self._aux_pack = None
+        if self.temperature_fit is not None:             # a sidecar's temperature is keyed to the head that has just been replaced
+            self._temperature, self.temperature_fit = 1.0, None
 
     def state_dict(self, *args, **kwargs):
         sd = super().state_dict(*args, **kwargs)
@@ -544,7 +596,9 @@ class SuperGuessr(nn.Module):
     @torch.no_grad()
     def spread(self, points: Tensor = None, quantiles=(0.5, 0.9), state: dict = None) -> Spread:
         """How far off a guess may be (pg_guess_spread; contract: include/pigeon_hip.h), from the geocell logits of `state` -- default
-        `last_state`, what the last forward left behind, with re-encoded rows carrying their exact-tier logits.
+        `last_state`, what the last forward left behind, with re-encoded rows carrying their exact-tier logits.  With a `temperature`
+        other than 1.0 the probabilities are the calibrated softmax(logits / T); the argmax, the top-k, `topk_values`, the refiner's
+        inputs and the certainty computations stay the head's own (reference-parity).
           points     (B,2) or (B,G,2) [lng, lat], G candidate guesses per sample; None: the state's own `preds_LLH`
           quantiles  1 .. 4 numbers in (0, 1]
         Returns Spread(expected_km, expected_score, radius_km, quantiles), float64 device tensors: under the head's softmax, the expected
@@ -556,10 +610,21 @@ class SuperGuessr(nn.Module):
         st = self.last_state if state is None else state
         if st is None:
             raise RuntimeError('SuperGuessr.spread: no state -- run a forward first, or pass `state`')
-        logits = st['logits']
+        logits = self._calibrated_logits(st)
         pts = st['preds_LLH'] if points is None else torch.as_tensor(points).to(logits.device, torch.float64)
         ek, es, rk = hip_ops.guess_spread(logits, self.lla_geocells.data, pts.contiguous(), quantiles, extent_km=self.cell_extent_km)
         return Spread(ek, es, rk, tuple(float(q) for q in quantiles))
+
+    @torch.no_grad()
+    def confidence(self, state: dict = None) -> Tensor:
+        """(B,) fp64: the calibrated probability of the top-1 cell, 1 / sum_c exp((l_c - max l) / T) -- pg_temper_stats's `conf` at
+        beta = 1 / `temperature`, one row pass over the logits of `state` (default `last_state`).  NaN for a row with a NaN or +inf
+        logit.  Nothing is synchronised; nothing is computed unless this is called."""
+        st = self.last_state if state is None else state
+        if st is None:
+            raise RuntimeError('SuperGuessr.confidence: no state -- run a forward first, or pass `state`')
+        r = hip_ops.temper_stats(st['logits'], st['preds_geocell'].contiguous(), [1.0 / self._temperature], conf=True)
+        return r['conf'][:, 0]
 
     def _guess_table(self, candidates, objective: str, device):
         """(candidates (M,2) fp64 on `device`, table (M,C) fp64) of `best_guess`: pg_score_table, built on first use and kept per
@@ -580,7 +645,9 @@ class SuperGuessr(nn.Module):
     @torch.no_grad()
     def best_guess(self, candidates: Tensor = None, objective: str = 'score', incumbent: Tensor = None, state: dict = None) -> BestGuess:
         """The guess chosen by its expectation under the head's softmax (pg_guess_best; contract: include/pigeon_hip.h), from the
-        geocell logits of `state` -- default `last_state`, with re-encoded rows carrying their exact-tier logits.
+        geocell logits of `state` -- default `last_state`, with re-encoded rows carrying their exact-tier logits.  With a `temperature`
+        other than 1.0 the expectations are taken under the calibrated softmax(logits / T); the argmax, the top-k, `topk_values`, the
+        refiner's inputs and the certainty computations stay the head's own (reference-parity).
           candidates  (M,2) [lng, lat] shared by the batch: a grid, prototype locations, ...; None: the model's own `lla_geocells`
           objective   'score': the largest expected GeoGuessr score (5000 exp(-d / 1492.7), before its rounding); 'km': the smallest
                       expected distance
@@ -595,7 +662,7 @@ class SuperGuessr(nn.Module):
         st = self.last_state if state is None else state
         if st is None:
             raise RuntimeError('SuperGuessr.best_guess: no state -- run a forward first, or pass `state`')
-        logits = st['logits']
+        logits = self._calibrated_logits(st)
         cand, table = self._guess_table(candidates, objective, logits.device)
         score = objective == 'score'
         idx, val = hip_ops.guess_best(logits, table, maximize=score)

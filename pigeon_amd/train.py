@@ -234,6 +234,9 @@ def main(argv=None):
     argp.add_argument('--seed', type=int, default=TRAIN_ARGS.seed)
     argp.add_argument('--synthetic', type=int, default=0, help='train on N seeded synthetic samples instead of a dataset')
     argp.add_argument('--geocells', type=int, default=10000, help='synthetic geocell count')
+    argp.add_argument('--temperature', action='store_true', default=False,
+                      help="after training, reload the saved best head, fit its temperature on dataset['val'] (pigeon_amd.temperature) "
+                           "and write <out>.temperature.json")
     args = argp.parse_args(argv)
     logging.basicConfig(level=logging.INFO)
     train_args = TrainArgs(num_train_epochs=args.epochs, learning_rate=args.lr, per_device_train_batch_size=args.batch, seed=args.seed)
@@ -255,6 +258,13 @@ def main(argv=None):
     for row in model.train_log:
         print(row)
     print(f'Best head saved to {args.out}')
+    if args.temperature:
+        from . import temperature
+        model.load_state(args.out)                                   # the best epoch's weights, not the last epoch's
+        val = dataset['val']
+        fit = temperature.fit_temperature(model, torch.as_tensor(val['embedding']), torch.as_tensor(val['labels_clf']))
+        print(temperature.format_fit(fit))
+        print(f"Temperature written to {temperature.save(args.out + '.temperature.json', fit, model)}")
     return model
 
 

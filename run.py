@@ -101,6 +101,10 @@ argp.add_argument('--spread', action='store_true', default=False,
                   help="evaluate: how far off every guess may be (SuperGuessr.spread: expected km, expected GeoGuessr score, the radii "
                        "holding 0.5 and 0.9 of the head's probability) and, against the labels, how often the truth lies inside them "
                        "(Radius_50_coverage / Radius_90_coverage, to be read against 0.5 and 0.9)")
+argp.add_argument('--temperature', default=None, metavar='FILE|NUMBER',
+                  help="evaluate: the temperature of the head's probabilities -- a number, or the sidecar `python -m pigeon_amd.temperature` "
+                       "wrote for this head; --spread and --guess are then computed under softmax(logits / T) and `Temperature` is "
+                       "printed with the metrics.  The model's own guess and its accuracy do not change")
 argp.add_argument('--neighbours', type=int, default=None, metavar='K',
                   help="evaluate: also the K (1..64) nearest training embeddings of every item (exact search over the refiner's bank, "
                        "pigeon_amd.neighbours) and the retrieval baseline's _nn metrics: the nearest row's coordinates as the guess")
@@ -286,7 +290,8 @@ def _dispatch(args, comm):
                            landmarks=args.landmarks, geocell_path=geocell_path, bank=bank, heading=args.heading,
                            multi_task=args.multitask, calibration=args.calibration, embedding_rel_tol=args.embedding_rel_tol,
                            country_path=args.countries, bank_rel_tol=args.bank_rel_tol, spread=(0.5, 0.9) if args.spread else None,
-                           best_guess={'expected-score': 'score', 'expected-km': 'km'}.get(args.guess), neighbours=args.neighbours)
+                           best_guess={'expected-score': 'score', 'expected-km': 'km'}.get(args.guess), neighbours=args.neighbours,
+                           temperature=args.temperature)
         _print_fallbacks(comm)
         if comm.is_main_process:
             print({k: (v if not hasattr(v, 'shape') or v.shape == () else tuple(v.shape)) for k, v in results.items() if k != 'exact_passes'})
