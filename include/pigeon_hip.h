@@ -58,7 +58,8 @@ extern "C" {
                               *    + pg_score_table, pg_guess_best, pg_guess_best_plan, additive;
                               *    + pg_knn_prepare, pg_knn_workspace_bytes, pg_knn_search, pg_knn_plan, pg_tune_knn_spans and pg_knn_bank,
                               *      additive;
-                              *    + pg_temper_stats, pg_temper_logits, pg_temper_plan, additive) */
+                              *    + pg_temper_stats, pg_temper_logits, pg_temper_plan, additive;
+                              *    + pg_bootstrap_indices, pg_bootstrap_means, pg_bootstrap_quantiles, pg_bootstrap_plan, additive) */
 
 const char* pg_last_error(void);
 int pg_abi_version(void);
@@ -822,6 +823,58 @@ int pg_temper_logits(const float* logits, int64_t N, int C, double beta, float* 
  *   out[2]  workgroups of the totals pass: one per (k, j) and one for the counts
  *   out[3]  bytes of stream-ordered scratch of a call without row_stats and state (saturates at 2^31 - 1) */
 int pg_temper_plan(int64_t N, int C, int K, int32_t out[4]);
+
+/* ------------------------------------------------------------------------------------------------
+ * Bootstrap intervals of evaluation statistics (csrc/bootstrap.hip): resampled means and resampled quantiles of per-item columns.
+ * The reference has no code for it; the contract is this project's own and is restated in tests/_bootref.py.
+ *
+ * The resampling contract.  Draws come from Philox4x32-10 with the multipliers 0xD2511F53 and 0xCD9E8D57 and the key increments
+ * 0x9E3779B9 and 0xBB67AE85.  The key is (seed & 0xffffffff, seed >> 32).  For draw j of replicate r the counter is
+ * ((j >> 1) & 0xffffffff, (j >> 1) >> 32, r, 0) and the output words are o0 .. o3; an even j uses u = o0 | o1 << 32, an odd j uses
+ * u = o2 | o3 << 32.  The item index is idx(r, j) = floor(u * N / 2^64), the high 64 bits of the 128-bit product; its bias is at most
+ * N / 2^64.  Known answers (counter / key / output): 0,0,0,0 / 0,0 / 6627e8d5 e169c58d bc57ac4c 9b00dbd8; all ffffffff / all ffffffff /
+ * 408f276d 41c83b0e a20bc7c6 6d5451fd; 243f6a88 85a308d3 13198a2e 03707344 / a4093822 299f31d0 / d16cfe09 94fdcceb 5001e420 24126ea1.
+ * Pairing: one replicate uses the same N indices for every column, which is what makes differences of statistics paired.  Replicate
+ * r's outputs depend on (seed, r, N, the column) only: not on R, not on which other columns are in the call, not on how columns are
+ * grouped into workgroups.  The draws are regenerated wherever they are needed; nothing of size R x N is stored.
+ *
+ * pg_bootstrap_indices.  out DEVICE (count,) int64: out[i] = idx(r, j0 + i).  For tests and the host restatement.  count == 0 is a
+ * no-op.  PG_EINVAL for N < 1, r outside 0 .. 2^32 - 1, a negative j0 or count and a null out.
+ *
+ * pg_bootstrap_means.  x DEVICE (M,N) fp64 row-major, one column of per-item values a row; out DEVICE (R,M) fp64:
+ *   out[r,m] = (sum_j x[m, idx(r,j)]) / N
+ * The sum is taken in one order that depends on N only: thread t of 256 adds j = t, t + 256, ... ascending, the 64 lanes of a wave
+ * combine as v += v(lane xor o), o = 32 .. 1, and the four waves as (w0 + w1) + (w2 + w3).  No atomics.  Non-finite values propagate
+ * into the replicates that drew them.
+ *
+ * pg_bootstrap_quantiles.  rank DEVICE (M,N) int32: rank[m,i] is item i's position in column m sorted ascending (a stable sort: ties
+ * by item index); sorted DEVICE (M,N) fp64: that sorted column (no NaN); q HOST Q doubles in [0, 1], Q 1 .. 16; out DEVICE (R,M,Q)
+ * fp64.  Per replicate and column the multiset is { rank[m, idx(r,j)] } with order statistics rho_(0) <= ... <= rho_(N-1), and
+ *   h = q (N - 1)      lo = floor(h)      t = h - lo      a = sorted[m, rho_(lo)]      b = sorted[m, rho_(min(lo + 1, N - 1))]
+ *   out[r,m,k] = t >= 0.5 ? b - (b - a) * (1 - t) : a + (b - a) * t
+ * which is numpy.quantile(resampled column, q, method='linear') bit for bit.  Integer ranks make the selection exact: counts of
+ * rank >> shift in LDS (integer atomics: the counts do not depend on arrival order), a scan, and further passes over the regenerated
+ * draws that resolve the wanted orders' bins.  No input value forms an address: a rank is bounds-checked before it is counted and
+ * before it indexes `sorted`; a replicate that draws a rank outside [0, N) gets NaN for that column.
+ *
+ * Both: R, M and N of any legal value work (the grid walks the (replicate, column group) pairs).  PG_EINVAL, naming the argument and
+ * before any HIP call, for N < 1 or N above pg_bootstrap_plan's out[6], R < 1 (or above 2^32: r is a 32-bit counter word), M < 1,
+ * Q outside 1 .. 16, a q outside [0, 1] or not finite, and a null pointer.  Asynchronous on `stream`.
+ * ------------------------------------------------------------------------------------------------ */
+int pg_bootstrap_indices(int64_t N, uint64_t seed, int64_t r, int64_t j0, int64_t count, int64_t* out, void* stream);
+int pg_bootstrap_means(const double* x, int M, int64_t N, int64_t R, uint64_t seed, double* out, void* stream);
+int pg_bootstrap_quantiles(const int32_t* rank, const double* sorted, int M, int64_t N, int64_t R, uint64_t seed, const double* q, int Q,
+                           double* out, void* stream);
+/* What the two kernels do with these sizes (host arithmetic, no GPU; PG_EINVAL as theirs for the four sizes):
+ *   out[0]  coarse bins a column
+ *   out[1]  the shift: a coarse bin holds 2^shift ranks; 0 when N <= out[0]
+ *   out[2]  passes of pg_bootstrap_quantiles over a replicate's draws: 1, or 1 + ceil(2 Q / (out[0] >> out[1]))
+ *   out[3]  columns per workgroup: the columns that share one pass over the draws (the bits do not depend on the grouping)
+ *   out[4]  threads of a workgroup
+ *   out[5]  bytes of LDS the counters of a workgroup take
+ *   out[6]  the largest supported N
+ *   out[7]  workgroups: min(R * ceil(M / out[3]), 2^20), each walking the (replicate, column group) pairs with that stride */
+int pg_bootstrap_plan(int64_t N, int64_t R, int M, int Q, int32_t out[8]);
 
 /* ------------------------------------------------------------------------------------------------
  * The k nearest rows of an embedding bank, exactly (csrc/knn.hip; restated in tests/_knnref.py).

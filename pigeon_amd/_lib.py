@@ -164,6 +164,10 @@ SIGNATURES = {
     "pg_temper_stats": (_I, [_P, _I64, _I, _P, C.POINTER(_D), _I, _P, _P, _P, _P, _P, _P]),
     "pg_temper_logits": (_I, [_P, _I64, _I, _D, _P, _P]),
     "pg_temper_plan": (_I, [_I64, _I, _I, C.POINTER(C.c_int32)]),
+    "pg_bootstrap_indices": (_I, [_I64, C.c_uint64, _I64, _I64, _I64, _P, _P]),
+    "pg_bootstrap_means": (_I, [_P, _I, _I64, _I64, C.c_uint64, _P, _P]),
+    "pg_bootstrap_quantiles": (_I, [_P, _P, _I, _I64, _I64, C.c_uint64, C.POINTER(_D), _I, _P, _P]),
+    "pg_bootstrap_plan": (_I, [_I64, _I64, _I, _I, C.POINTER(C.c_int32)]),
     "pg_knn_prepare": (_I, [_P, _I64, _P, _P, _P, _P]),
     "pg_knn_workspace_bytes": (_I, [_I64, _I, _I, C.POINTER(_SZ)]),
     "pg_knn_search": (_I, [C.POINTER(KnnBank), _P, _I, _I, _P, _I, _P, _P, _P, _P, _SZ, _P]),

@@ -10,6 +10,7 @@ polygons are given (pigeon_amd/regions.py: exact point-in-region lookup on the G
 from __future__ import annotations
 
 import logging
+import os
 from typing import Callable, Dict, Optional
 
 import numpy as np
@@ -297,7 +298,8 @@ class ImageEvalDataset:
 
 def evaluate_model(model: SuperGuessr, dataset, metrics: Optional[Callable] = None, train_args=None,
                    refiner: Optional[ProtoRefiner] = None, yfcc: bool = False, writer=None, step: int = 0,
-                   batch_size: Optional[int] = None, num_workers: int = 0, spread=None, best_guess=None, neighbours=None):
+                   batch_size: Optional[int] = None, num_workers: int = 0, spread=None, best_guess=None, neighbours=None,
+                   bootstrap: Optional[int] = None, bootstrap_seed: int = 0, bootstrap_level: float = 0.95, countries=None):
     """reference training/train_eval_loop.py:35-161 (eval loop :77-112).
 
     dataset items are dicts of forward() keyword arguments (pixel_values | pixel_bytes | embedding, labels, labels_clf, ...), or
@@ -318,8 +320,21 @@ def evaluate_model(model: SuperGuessr, dataset, metrics: Optional[Callable] = No
     on device tensors without a host synchronisation: results['nn_rows'], ['nn_distance'] (N,K), ['nn_lnglat'] (N,K,2),
     ['nn_certified'] (N,); when the dataset has a `labels` column also Mean_km_error_nn, Median_km_error_nn, Geoguessr_score_nn (the
     nearest row's coordinates as the guess) and NN_beats_model.  Needs a refiner (ValueError without).
+    `bootstrap` (R replicates; default None: nothing is computed, nothing is launched, no key is added): the paired bootstrap of
+    every metric `metrics` returns and of the best-guess and neighbour metrics (`pigeon_amd.bootstrap`: the per-item columns of
+    `metric_columns`, resampled R times on the GPU with `bootstrap_seed`), stored under results['bootstrap']: key -> dict(estimate,
+    se, lo, hi) at `bootstrap_level`, the paired differences '<key>_best - <key>' / '<key>_nn - <key>' with share_le_zero, plus
+    results['bootstrap_level'].  Needs `metrics`; `countries`: the bank behind `Country_accuracy`, for that metric's column.  In a
+    multi-rank run rank 0 bootstraps.  Every other key is computed as without it.
     """
     from torch.utils.data import DataLoader
+    if bootstrap is not None:
+        if isinstance(bootstrap, bool) or int(bootstrap) != bootstrap or int(bootstrap) < 1:
+            raise ValueError(f'evaluate_model: bootstrap must be a positive number of replicates, got {bootstrap!r}')
+        if metrics is None:
+            raise ValueError('evaluate_model: bootstrap=R resamples the metrics; it needs `metrics`')
+        if not 0.0 < float(bootstrap_level) < 1.0:
+            raise ValueError(f'evaluate_model: bootstrap_level must lie strictly between 0 and 1, got {bootstrap_level!r}')
     nn_k, nn_index = _neighbour_index(refiner, neighbours) if neighbours is not None else (None, None)
     logger.warning('Starting evaluation ...')
     if batch_size is None:
@@ -447,11 +462,21 @@ def evaluate_model(model: SuperGuessr, dataset, metrics: Optional[Callable] = No
         if preds_mt is not None:
             labels_mt, labels_climate = np.asarray(dataset['labels_multi_task']), np.asarray(dataset['labels_climate'])
             labels_month = np.asarray(dataset['labels_month']) if preds_month is not None else None
-        results.update(metrics((preds, preds_geocells, preds_mt, preds_climate, preds_month, top5_geocells,
-                                labels_lla, labels_cell, labels_mt, labels_climate, labels_month)))
+        collected = (preds, preds_geocells, preds_mt, preds_climate, preds_month, top5_geocells,
+                     labels_lla, labels_cell, labels_mt, labels_climate, labels_month)
+        results.update(metrics(collected))
     if best_guess is not None:
         results.update(best_extra)
     results.update(nn_extra)
+    if bootstrap is not None and int(os.environ.get('RANK', '0')) == 0:
+        from . import bootstrap as boot
+        cols, stats = boot.metric_columns(collected, countries=countries, best_LLH=results['best_LLH'] if best_guess is not None and best_extra else None,
+                                          best_taken=results['best_taken'] if best_guess is not None and best_extra else None,
+                                          nn_lnglat=results['nn_lnglat'] if nn_extra else None)
+        stats = {k: s for k, s in stats.items() if k in results or ' - ' in k}      # what this run reports, and the paired differences
+        results['bootstrap'] = boot.bootstrap(cols, stats, R=int(bootstrap), seed=bootstrap_seed, level=bootstrap_level,
+                                              device=model.cell_layer.weight.device)
+        results['bootstrap_level'] = float(bootstrap_level)
     model.train()
     logger.warning('Back to training ...')
     return results
@@ -461,7 +486,8 @@ def evaluate(model: str, dataset, yfcc: bool, landmarks: bool, base_model=None, 
              refine: bool = True, geocell_path: Optional[str] = None, proto_path: Optional[str] = None,
              dataset_path=None, bank=None, head_state: Optional[str] = None, multi_task: bool = False,
              calibration: Optional[str] = None, embedding_rel_tol: Optional[float] = None, country_path: Optional[str] = None,
-             bank_rel_tol=None, spread=None, best_guess=None, neighbours=None, temperature=None):
+             bank_rel_tol=None, spread=None, best_guess=None, neighbours=None, temperature=None, bootstrap=None,
+             bootstrap_seed: int = 0, bootstrap_level: float = 0.95):
     """reference evaluation/evaluate.py:10-85.
 
     `base_model`: as in the reference a STRING -- config.CLIP_MODEL for the pretrained tower, or the path of a checkpoint whose
@@ -496,6 +522,9 @@ def evaluate(model: str, dataset, yfcc: bool, landmarks: bool, base_model=None, 
     weights; another head's raises, both fingerprints named): `SuperGuessr.temperature`, so the spread and best-guess metrics are
     computed under the calibrated probabilities, and results['Temperature'] is printed with the metrics.  None (default): nothing
     changes.  The accuracy and distance metrics of the model's own guess do not depend on it.
+    `bootstrap` / `bootstrap_seed` / `bootstrap_level`: handed to `evaluate_model(bootstrap=...)`: R paired bootstrap replicates of
+    every metric, results['bootstrap'], printed as `value [lo, hi]` with the paired differences below.  None (default): nothing
+    changes -- no output, no key, no launch.
     """
     import os
     from . import config as cfg
@@ -583,7 +612,11 @@ def evaluate(model: str, dataset, yfcc: bool, landmarks: bool, base_model=None, 
         if refiner.bank_rel_tol > 0:
             print(f'Prototype bank declared at a relative error of {refiner.bank_rel_tol:.3g}: the refiner\'s certainty accounts for it')
     metrics = compute_geoguessr_metrics if countries is None else (lambda r: compute_geoguessr_metrics(r, countries=countries))
-    results = evaluate_model(full_model, dataset, metrics, None, refiner, spread=spread, best_guess=best_guess, neighbours=neighbours)
+    results = evaluate_model(full_model, dataset, metrics, None, refiner, spread=spread, best_guess=best_guess, neighbours=neighbours,
+                             bootstrap=bootstrap, bootstrap_seed=bootstrap_seed, bootstrap_level=bootstrap_level, countries=countries)
+    if 'bootstrap' in results:
+        from .bootstrap import report
+        print(report(results['bootstrap'], results['bootstrap_level']))
     if temperature is not None:
         results['Temperature'] = full_model.temperature
         print(f"Temperature: {results['Temperature']:.6g}")

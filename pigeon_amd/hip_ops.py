@@ -401,6 +401,75 @@ def temper_plan(N: int, C_cells: int, K: int) -> dict:
     return {"threads": int(o[0]), "betas_per_pass": int(o[1]), "totals_workgroups": int(o[2]), "scratch_bytes": int(o[3])}
 
 
+# ----------------------------------------------------------------------------------------- bootstrap intervals
+def _boot_seed(seed) -> int:
+    seed = int(seed)
+    if not 0 <= seed < 2 ** 64:
+        raise _lib.PigeonHipError(f"bootstrap: seed must be 0 .. 2^64 - 1, got {seed}")
+    return seed
+
+
+def bootstrap_indices(N: int, seed: int, r: int, j0: int, count: int, device="cuda") -> torch.Tensor:
+    """pg_bootstrap_indices: idx(r, j0 + i) for i < count, (count,) int64 on `device`: the index stream of the resampling contract
+    (include/pigeon_hip.h).  No host synchronisation."""
+    dev = indexed_device(device)
+    if int(count) < 0:
+        raise _lib.PigeonHipError(f"bootstrap_indices: count = {count}")
+    out = torch.empty((int(count),), dtype=torch.int64, device=dev)
+    with torch.cuda.device(dev):
+        check(load().pg_bootstrap_indices(int(N), _boot_seed(seed), int(r), int(j0), int(count), _p(out), _stream()), "pg_bootstrap_indices")
+    return out
+
+
+def bootstrap_means(x: torch.Tensor, R: int, seed: int = 0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """pg_bootstrap_means: x (M,N) fp64, one per-item column a row -> (R,M) fp64, the mean of every column over each of R resamples
+    of the N items (the same items for every column).  No host synchronisation."""
+    _dev(x, torch.float64); _shape(x, "x", None, None)
+    M, N = int(x.shape[0]), int(x.shape[1])
+    if out is None:
+        out = torch.empty((max(int(R), 0), M), dtype=torch.float64, device=x.device)
+    _dev(out, torch.float64); _shape(out, "out", int(R), M)
+    if out.device != x.device:
+        raise _lib.PigeonHipError(f"bootstrap_means: out is on {out.device}, x on {x.device}")
+    with torch.cuda.device(x.device):
+        check(load().pg_bootstrap_means(_p(x), M, N, int(R), _boot_seed(seed), _p(out), _stream()), "pg_bootstrap_means")
+    return out
+
+
+def bootstrap_quantiles(rank: torch.Tensor, sorted_cols: torch.Tensor, R: int, q, seed: int = 0,
+                        out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """pg_bootstrap_quantiles: rank (M,N) int32 (every item's position in its column sorted ascending, stable), sorted_cols (M,N) fp64
+    (the sorted columns), q 1 .. 16 numbers in [0, 1] (host) -> (R,M,Q) fp64: numpy.quantile(..., method='linear') of every column
+    over each of R resamples.  No host synchronisation."""
+    _dev(rank, torch.int32); _shape(rank, "rank", None, None)
+    M, N = int(rank.shape[0]), int(rank.shape[1])
+    _dev(sorted_cols, torch.float64); _shape(sorted_cols, "sorted", M, N)
+    if sorted_cols.device != rank.device:
+        raise _lib.PigeonHipError(f"bootstrap_quantiles: sorted is on {sorted_cols.device}, rank on {rank.device}")
+    qs = [float(v) for v in q]
+    Q = len(qs)
+    if not 1 <= Q <= 16:
+        raise _lib.PigeonHipError(f"bootstrap_quantiles: q must hold 1 .. 16 numbers, got {Q}")
+    if out is None:
+        out = torch.empty((max(int(R), 0), M, Q), dtype=torch.float64, device=rank.device)
+    _dev(out, torch.float64); _shape(out, "out", int(R), M, Q)
+    if out.device != rank.device:
+        raise _lib.PigeonHipError(f"bootstrap_quantiles: out is on {out.device}, rank on {rank.device}")
+    qarr = (C.c_double * Q)(*qs)
+    with torch.cuda.device(rank.device):
+        check(load().pg_bootstrap_quantiles(_p(rank), _p(sorted_cols), M, N, int(R), _boot_seed(seed), qarr, Q, _p(out), _stream()),
+              "pg_bootstrap_quantiles")
+    return out
+
+
+def bootstrap_plan(N: int, R: int, M: int, Q: int = 1) -> dict:
+    """pg_bootstrap_plan: what the bootstrap kernels do with N items, R replicates, M columns and Q quantiles (host arithmetic, no GPU)."""
+    o = (C.c_int32 * 8)()
+    check(load().pg_bootstrap_plan(int(N), int(R), int(M), int(Q), o), "pg_bootstrap_plan")
+    return {"bins": int(o[0]), "shift": int(o[1]), "passes": int(o[2]), "columns_per_workgroup": int(o[3]), "threads": int(o[4]),
+            "lds_bytes": int(o[5]), "max_n": int(o[6]), "workgroups": int(o[7])}
+
+
 # ----------------------------------------------------------------------------------------- nearest rows of the embedding bank
 KNN_MODES = {"auto": 0, "exact": 1, "filter": 2}
 

@@ -276,8 +276,13 @@ def contains(bank: RegionBank, lnglat, region) -> np.ndarray:
 def country_accuracy(predictions, labels, bank: RegionBank) -> float:
     """reference evaluation/metrics.py:74-88: the label's country is find_country(label); the prediction is correct iff that country
     `contains` it.  The mean over the samples."""
+    return float(np.mean(country_hits(predictions, labels, bank)))
+
+
+def country_hits(predictions, labels, bank: RegionBank) -> np.ndarray:
+    """The per-sample hit (0 / 1) whose mean is `country_accuracy`: the column a bootstrap resamples."""
     countries, _ = find_regions(bank, labels)
-    return float(np.mean(contains(bank, predictions, countries).astype(int)))
+    return contains(bank, predictions, countries).astype(int)
 
 
 def assign_geocells(lnglat, bank: RegionBank) -> Tuple[np.ndarray, dict]:

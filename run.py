@@ -105,6 +105,11 @@ argp.add_argument('--temperature', default=None, metavar='FILE|NUMBER',
                   help="evaluate: the temperature of the head's probabilities -- a number, or the sidecar `python -m pigeon_amd.temperature` "
                        "wrote for this head; --spread and --guess are then computed under softmax(logits / T) and `Temperature` is "
                        "printed with the metrics.  The model's own guess and its accuracy do not change")
+argp.add_argument('--bootstrap', type=int, default=None, metavar='R',
+                  help="evaluate: R paired bootstrap replicates of every metric on the GPU (pigeon_amd.bootstrap): the metrics are printed as "
+                       "`value [lo, hi]`, the paired differences (--guess, --neighbours against the model's own guess) below them")
+argp.add_argument('--bootstrap-seed', dest='bootstrap_seed', type=int, default=0, metavar='S')
+argp.add_argument('--bootstrap-level', dest='bootstrap_level', type=float, default=0.95, metavar='L')
 argp.add_argument('--neighbours', type=int, default=None, metavar='K',
                   help="evaluate: also the K (1..64) nearest training embeddings of every item (exact search over the refiner's bank, "
                        "pigeon_amd.neighbours) and the retrieval baseline's _nn metrics: the nearest row's coordinates as the guess")
@@ -291,10 +296,11 @@ def _dispatch(args, comm):
                            multi_task=args.multitask, calibration=args.calibration, embedding_rel_tol=args.embedding_rel_tol,
                            country_path=args.countries, bank_rel_tol=args.bank_rel_tol, spread=(0.5, 0.9) if args.spread else None,
                            best_guess={'expected-score': 'score', 'expected-km': 'km'}.get(args.guess), neighbours=args.neighbours,
-                           temperature=args.temperature)
+                           temperature=args.temperature, bootstrap=args.bootstrap, bootstrap_seed=args.bootstrap_seed,
+                           bootstrap_level=args.bootstrap_level)
         _print_fallbacks(comm)
         if comm.is_main_process:
-            print({k: (v if not hasattr(v, 'shape') or v.shape == () else tuple(v.shape)) for k, v in results.items() if k != 'exact_passes'})
+            print({k: (v if not hasattr(v, 'shape') or v.shape == () else tuple(v.shape)) for k, v in results.items() if k not in ('exact_passes', 'bootstrap', 'bootstrap_level')})
             if 'Radius_50_coverage' in results:
                 print(f"spread: the 50 % radius (median {results['Median_radius_50_km']:.1f} km) holds the truth for "
                       f"{results['Radius_50_coverage']:.1%} of the samples, the 90 % radius (median {results['Median_radius_90_km']:.1f} km) "
