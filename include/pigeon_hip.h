@@ -59,7 +59,8 @@ extern "C" {
                               *    + pg_knn_prepare, pg_knn_workspace_bytes, pg_knn_search, pg_knn_plan, pg_tune_knn_spans and pg_knn_bank,
                               *      additive;
                               *    + pg_temper_stats, pg_temper_logits, pg_temper_plan, additive;
-                              *    + pg_bootstrap_indices, pg_bootstrap_means, pg_bootstrap_quantiles, pg_bootstrap_plan, additive) */
+                              *    + pg_bootstrap_indices, pg_bootstrap_means, pg_bootstrap_quantiles, pg_bootstrap_plan, additive;
+                              *    + pg_refine_sweep, pg_refine_sweep_totals, pg_refine_sweep_plan, additive) */
 
 const char* pg_last_error(void);
 int pg_abi_version(void);
@@ -875,6 +876,48 @@ int pg_bootstrap_quantiles(const int32_t* rank, const double* sorted, int M, int
  *   out[6]  the largest supported N
  *   out[7]  workgroups: min(R * ceil(M / out[3]), 2^20), each walking the (replicate, column group) pairs with that stride */
 int pg_bootstrap_plan(int64_t N, int64_t R, int M, int Q, int32_t out[8]);
+
+/* ------------------------------------------------------------------------------------------------
+ * The refiner's selection at every point of a (topk, temperature, max_km) grid (csrc/refine_sweep.hip; restated in
+ * tests/_refitref.py).  Finding the nearest prototype and farthest member of every candidate depends on none of the three settings:
+ * one pg_refine_forward / pg_refine_forward_ex call at topk = n_eval leaves the records, and the sweep does every selection from them.
+ *
+ * pg_refine_sweep.  scratch DEVICE (B,n_eval,SC) fp32, SC = 4 (pg_refine_forward's records) or 12 (pg_refine_forward_ex's; only the
+ * four leading floats are read); cand_prob DEVICE (B,k) fp32 or NULL (-> [1,0,0,...]); init_llh DEVICE (B,2) fp64; topks HOST nK
+ * int32, each in [1, min(n_eval, 64)]; temps HOST nT floats, each finite and positive; max_kms HOST nR doubles, none NaN (+inf: never
+ * veto); choice DEVICE (G,B) uint8 out, G = nK * nT * nR, g = (iK * nT + iT) * nR + iR; veto_km DEVICE (B,n_eval) fp64 out or NULL.
+ * Per row b and grid point g the arithmetic is refine_select_kernel's (csrc/refine.hip), operation for operation:
+ *   ex_j = expf(score_j / T) in fp32;  sum = the sequential fp32 sum of ex_j over j < topk;  fin_j = cp_j * (ex_j / sum), no max
+ *   shift (underflow, 0/0 and NaN behave as they do there);  refined = the first maximum of fin over j < topk, a NaN counting as the
+ *   maximum (torch.argmax);  the veto fires when haversine_km(init, the refined candidate's point) > max_km, with the fp32 / fp64
+ *   promotion csrc/refine_common.h documents, and then the choice is the first maximum of cp over j < topk.
+ * choice[g * B + b]: the chosen candidate in bits 0-5, bit 7 set when the veto fired.  For every g, choice & 63 is the out_choice of a
+ * pg_refine_forward call with that (topk, T, max_km) on the same inputs, bit for bit.
+ * veto_km[b * n_eval + j]: the veto distance the kernel used for candidate j of row b.
+ * Limits: n_eval 1 .. 64 (and <= k when cand_prob is given), nK, nT, nR >= 1, G <= 2^20.  Every violation is PG_EINVAL, names the
+ * argument and is raised before any HIP call.  B == 0 is a no-op.  Asynchronous on `stream` (the three host arrays are copied before
+ * the call returns).
+ *
+ * pg_refine_sweep_totals.  choice DEVICE (G,B) uint8; values DEVICE (B,n_eval,V) fp64, V 1 .. 16; totals DEVICE (G,V+2) fp64 out:
+ *   totals[g,v]     = sum_b values[b, choice[g,b] & 63, v]
+ *   totals[g,V]     = rows with (choice & 63) != 0            totals[g,V+1] = rows whose veto bit is set
+ * The sum over rows is taken in one order that depends on B only: thread t of 256 adds b = t, t + 256, ... ascending, the 64 lanes of a
+ * wave combine as v += v(lane xor o), o = 32 .. 1, and the four waves as (w0 + w1) + (w2 + w3).  No atomics: a grid point's row of
+ * totals is the same bits alone and inside any grid, at any g.  A choice byte whose index is >= n_eval forms no address: it is read
+ * as candidate 0 and its grid point gets NaN totals.  PG_EINVAL for B < 0, n_eval outside 1 .. 64, G outside 1 .. 2^20, V outside
+ * 1 .. 16 and a null pointer.
+ * ------------------------------------------------------------------------------------------------ */
+int pg_refine_sweep(const float* scratch, int SC, int B, int n_eval, const float* cand_prob, int k, const double* init_llh,
+                    const int32_t* topks, int nK, const float* temps, int nT, const double* max_kms, int nR, uint8_t* choice,
+                    double* veto_km, void* stream);
+int pg_refine_sweep_totals(const uint8_t* choice, int64_t G, int B, int n_eval, const double* values, int V, double* totals,
+                           void* stream);
+/* What the two kernels do with these sizes (host arithmetic, no GPU; PG_EINVAL as theirs for the four sizes):
+ *   out[0]  rows per workgroup of the selection (one per lane; a workgroup owns one temperature of those rows)
+ *   out[1]  bytes of LDS such a workgroup takes
+ *   out[2]  row groups, ceil(B / out[0]): the selection launches out[2] * nT workgroups, the totals G
+ *   out[3]  bytes of choice, G * B */
+int pg_refine_sweep_plan(int B, int n_eval, int64_t G, int V, int64_t out[4]);
 
 /* ------------------------------------------------------------------------------------------------
  * The k nearest rows of an embedding bank, exactly (csrc/knn.hip; restated in tests/_knnref.py).

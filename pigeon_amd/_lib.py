@@ -168,6 +168,9 @@ SIGNATURES = {
     "pg_bootstrap_means": (_I, [_P, _I, _I64, _I64, C.c_uint64, _P, _P]),
     "pg_bootstrap_quantiles": (_I, [_P, _P, _I, _I64, _I64, C.c_uint64, C.POINTER(_D), _I, _P, _P]),
     "pg_bootstrap_plan": (_I, [_I64, _I64, _I, _I, C.POINTER(C.c_int32)]),
+    "pg_refine_sweep": (_I, [_P, _I, _I, _I, _P, _I, _P, C.POINTER(C.c_int32), _I, C.POINTER(_F), _I, C.POINTER(_D), _I, _P, _P, _P]),
+    "pg_refine_sweep_totals": (_I, [_P, _I64, _I, _I, _P, _I, _P, _P]),
+    "pg_refine_sweep_plan": (_I, [_I, _I, _I64, _I, C.POINTER(_I64)]),
     "pg_knn_prepare": (_I, [_P, _I64, _P, _P, _P, _P]),
     "pg_knn_workspace_bytes": (_I, [_I64, _I, _I, C.POINTER(_SZ)]),
     "pg_knn_search": (_I, [C.POINTER(KnnBank), _P, _I, _I, _P, _I, _P, _P, _P, _P, _SZ, _P]),

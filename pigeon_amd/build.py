@@ -16,7 +16,7 @@ OBJ = os.path.join(CSRC, "build")
 LIB = os.path.join(HERE, "libpigeon_hip.so")
 # the product library: production kernels only
 SOURCES = ["abi.hip", "vit_weights.hip", "vit.hip", "vit_precise.hip", "gemm_plan.hip", "gemm_bf16.hip", "gemm_pp.hip", "gemm_pp6.hip", "gemm_tail.hip", "gemm_mid.hip", "attention.hip", "rowops.hip", "precise.hip",
-           "preprocess.hip", "jpeg.hip", "equirect.hip", "geo_proto.hip", "spread.hip", "temper.hip", "bootstrap.hip", "guess_best.hip", "knn.hip", "head.hip", "head_train.hip", "refine.hip", "certainty.hip", "aux_heads.hip", "requeue.hip", "fingerprint.hip", "comm.hip", "optics.hip", "regions.hip", "attribution.hip"]
+           "preprocess.hip", "jpeg.hip", "equirect.hip", "geo_proto.hip", "spread.hip", "temper.hip", "bootstrap.hip", "guess_best.hip", "knn.hip", "head.hip", "head_train.hip", "refine.hip", "refine_sweep.hip", "certainty.hip", "aux_heads.hip", "requeue.hip", "fingerprint.hip", "comm.hip", "optics.hip", "regions.hip", "attribution.hip"]
 # every header under csrc/ plus the public one, from the directory: a header that is not listed here rebuilds nothing when it changes
 HEADERS = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")) + [os.path.join(os.path.dirname(HERE), "include", "pigeon_hip.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"]

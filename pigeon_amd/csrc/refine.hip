@@ -22,6 +22,7 @@
 // farthest members of the chosen cluster.  Same kernels, same arithmetic, same selection: `EXT` only widens the scratch record.
 #include "common.h"
 #include "pigeon_internal.h"
+#include "refine_common.h"
 #include <cmath>
 
 #define RF_DIM 1024
@@ -209,34 +210,7 @@ __global__ __launch_bounds__(256) void refine_candidates_kernel(pg_bank bank, co
     }
 }
 
-// torch.argmax semantics over n <= 64 values: first maximum; a NaN is the maximum (first NaN wins).
-__device__ __forceinline__ int argmax_torch(const float* v, int n) {
-    int bi = 0; float bv = v[0];
-    for (int i = 1; i < n; ++i) {
-        const float x = v[i];
-        if (bv != bv) break;                                // already NaN -> stays
-        if (x != x || x > bv) { bv = x; bi = i; }
-    }
-    return bi;
-}
-
-// The veto distance with the reference's dtype promotion.  models/proto_refiner.py:198-202 calls
-// haversine(initial_LLH, refined_LLH) (preprocessing/geo_utils.py:40-55) with x = the float64 initial prediction and
-// y = torch.tensor(top_preds[...]) = a FLOAT32 tensor: torch.deg2rad(y) and torch.cos(y_rad[:,1]) are evaluated in fp32
-// (deg2rad multiplies by pi/180 rounded to the tensor dtype), `y_rad - x_rad` and everything after promote to float64.
-// cos of the fp32 latitude is taken as the correctly rounded fp32 value (double cos, rounded once): torch's CPU kernel
-// (Sleef, <= 1 ulp) agrees with it except for rare last-bit cases, which no device libm could reproduce anyway.
-__device__ __forceinline__ double haversine_km(double lng1, double lat1, float lng2, float lat2) {
-    const double d2r = 0.017453292519943295769236907684886127134428718885417;   // M_PI / 180
-    const double x0 = lng1 * d2r, x1 = lat1 * d2r;
-    const float y0 = lng2 * (float)d2r, y1 = lat2 * (float)d2r;                  // fp32 deg2rad
-    const double dl = (double)y0 - x0, dp = (double)y1 - x1;
-    const double sp = sin(dp / 2), sl = sin(dl / 2);
-    const float cy = (float)cos((double)y1);                                      // fp32 cos(lat of the refined point)
-    const double a = sp * sp + cos(x1) * (double)cy * (sl * sl);
-    const double c = 2 * asin(sqrt(a));
-    return (6378137.0 * c) / 1000;
-}
+// argmax_torch and haversine_km: refine_common.h (shared with refine_sweep.hip, one definition each)
 
 // n_eval records of SC floats per query in `scratch`; only the first topk take part (pg_refine_forward: n_eval = topk, SC = 4)
 __global__ __launch_bounds__(64) void refine_select_kernel(const float* __restrict__ scratch, int B, int k, int topk, int n_eval, int SC,

@@ -487,7 +487,7 @@ def evaluate(model: str, dataset, yfcc: bool, landmarks: bool, base_model=None, 
              dataset_path=None, bank=None, head_state: Optional[str] = None, multi_task: bool = False,
              calibration: Optional[str] = None, embedding_rel_tol: Optional[float] = None, country_path: Optional[str] = None,
              bank_rel_tol=None, spread=None, best_guess=None, neighbours=None, temperature=None, bootstrap=None,
-             bootstrap_seed: int = 0, bootstrap_level: float = 0.95):
+             bootstrap_seed: int = 0, bootstrap_level: float = 0.95, refiner_settings=None):
     """reference evaluation/evaluate.py:10-85.
 
     `base_model`: as in the reference a STRING -- config.CLIP_MODEL for the pretrained tower, or the path of a checkpoint whose
@@ -525,6 +525,10 @@ def evaluate(model: str, dataset, yfcc: bool, landmarks: bool, base_model=None, 
     `bootstrap` / `bootstrap_seed` / `bootstrap_level`: handed to `evaluate_model(bootstrap=...)`: R paired bootstrap replicates of
     every metric, results['bootstrap'], printed as `value [lo, hi]` with the paired differences below.  None (default): nothing
     changes -- no output, no key, no launch.
+    `refiner_settings`: the refiner's (topk, temperature, max_refinement) -- a triple, the string `TOPK,TEMPERATURE,MAX_KM`, or the path
+    of the sidecar `python -m pigeon_amd.refiner_fit` wrote for this head and this bank (another head's or bank's raises, both
+    fingerprints named).  Applied after the refiner is built and printed; topk above the 50 candidates is refused.  None (default):
+    nothing changes -- the literals below, the same output, no launch.
     """
     import os
     from . import config as cfg
@@ -608,6 +612,9 @@ def evaluate(model: str, dataset, yfcc: bool, landmarks: bool, base_model=None, 
                                    bank_rel_tol=bank_tol)
             os.makedirs(os.path.dirname(packed) or '.', exist_ok=True)
             refiner.host_bank.save(packed)
+        if refiner_settings is not None:
+            from .refiner_fit import apply_to
+            apply_to(refiner, refiner_settings, full_model)
         print(refiner)
         if refiner.bank_rel_tol > 0:
             print(f'Prototype bank declared at a relative error of {refiner.bank_rel_tol:.3g}: the refiner\'s certainty accounts for it')

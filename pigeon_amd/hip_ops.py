@@ -1703,6 +1703,95 @@ def refine_certainty(bank: DeviceBank, q: torch.Tensor, cand: torch.Tensor, cand
     return tol, code
 
 
+# ----------------------------------------------------------------------------------------- refiner grid sweep (csrc/refine_sweep.hip)
+SWEEP_CHOICE_BYTES = 256 << 20                       # refine_sweep keeps a chunk's choice bytes under this
+
+
+def _sweep_grid(topks, temps, max_kms):
+    ks = [int(v) for v in topks]
+    ts = [float(v) for v in temps]
+    rs = [float(v) for v in max_kms]
+    return ks, ts, rs, (C.c_int32 * max(len(ks), 1))(*ks), (C.c_float * max(len(ts), 1))(*ts), (C.c_double * max(len(rs), 1))(*rs)
+
+
+def refine_sweep_choice(scratch: torch.Tensor, cand_prob: Optional[torch.Tensor], init_llh: torch.Tensor, topks, temps, max_kms,
+                        veto_km: bool = False, out: Optional[torch.Tensor] = None):
+    """pg_refine_sweep: the selection of refine_forward at every point of the grid topks x temps x max_kms (host sequences), from the
+    records `scratch` (B,n_eval,4 or 12) fp32 that refine_forward / refine_forward_ex left.  cand_prob (B,k) fp32 or None, init_llh
+    (B,2) fp64.  Returns choice (G,B) uint8 with g = (iK * nT + iT) * nR + iR: the candidate in bits 0-5, bit 7 = the veto fired;
+    with veto_km=True also the (B,n_eval) fp64 veto distances.  A temperature is the float32 the kernel sees.  No host synchronisation."""
+    _arg(scratch, "scratch", torch.float32); _arg(init_llh, "init_llh", torch.float64)
+    if scratch.dim() != 3 or scratch.shape[2] not in (4, 12):
+        raise _lib.PigeonHipError(f"scratch must have shape (B,n_eval,4) or (B,n_eval,12), got {tuple(scratch.shape)}")
+    B, n_eval, SC = (int(v) for v in scratch.shape)
+    _shape(init_llh, "init_llh", B, 2)
+    k = 0
+    if cand_prob is not None:
+        _arg(cand_prob, "cand_prob", torch.float32); _shape(cand_prob, "cand_prob", B, None)
+        k = int(cand_prob.shape[1])
+    ks, ts, rs, ka, ta, ra = _sweep_grid(topks, temps, max_kms)
+    G = len(ks) * len(ts) * len(rs)
+    if out is None:
+        out = torch.empty((G, B), dtype=torch.uint8, device=scratch.device)
+    _arg(out, "out", torch.uint8); _shape(out, "out", G, B)
+    vk = torch.empty((B, n_eval), dtype=torch.float64, device=scratch.device) if veto_km else None
+    for name, t in (("cand_prob", cand_prob), ("init_llh", init_llh), ("out", out)):
+        if t is not None and t.device != scratch.device:
+            raise _lib.PigeonHipError(f"refine_sweep: {name} is on {t.device}, scratch on {scratch.device}")
+    with torch.cuda.device(scratch.device):
+        check(load().pg_refine_sweep(_p(scratch), SC, B, n_eval, _p(cand_prob), k, _p(init_llh), ka, len(ks), ta, len(ts), ra, len(rs),
+                                     _p(out), _p(vk), _stream()), "pg_refine_sweep")
+    return (out, vk) if veto_km else out
+
+
+def refine_sweep_totals(choice: torch.Tensor, values: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """pg_refine_sweep_totals: choice (G,B) uint8, values (B,n_eval,V) fp64 with V 1 .. 16 -> (G,V+2) fp64: per grid point the sum over
+    rows of the chosen candidate's values, the rows whose choice is not candidate 0 and the vetoed rows.  No host synchronisation."""
+    _arg(choice, "choice", torch.uint8); _arg(values, "values", torch.float64)
+    _shape(choice, "choice", None, None)
+    G, B = int(choice.shape[0]), int(choice.shape[1])
+    _shape(values, "values", B, None, None)
+    n_eval, V = int(values.shape[1]), int(values.shape[2])
+    if out is None:
+        out = torch.empty((G, V + 2), dtype=torch.float64, device=choice.device)
+    _arg(out, "out", torch.float64); _shape(out, "out", G, V + 2)
+    if values.device != choice.device or out.device != choice.device:
+        raise _lib.PigeonHipError(f"refine_sweep_totals: values on {values.device}, out on {out.device}, choice on {choice.device}")
+    with torch.cuda.device(choice.device):
+        check(load().pg_refine_sweep_totals(_p(choice), G, B, n_eval, _p(values), V, _p(out), _stream()), "pg_refine_sweep_totals")
+    return out
+
+
+def refine_sweep_plan(B: int, n_eval: int, G: int, V: int) -> dict:
+    """pg_refine_sweep_plan: what the sweep does with B rows, n_eval candidates, G grid points and V columns (host arithmetic, no GPU)."""
+    o = (C.c_int64 * 4)()
+    check(load().pg_refine_sweep_plan(int(B), int(n_eval), int(G), int(V), o), "pg_refine_sweep_plan")
+    return {"rows_per_workgroup": int(o[0]), "lds_bytes": int(o[1]), "row_groups": int(o[2]), "choice_bytes": int(o[3])}
+
+
+def refine_sweep(scratch: torch.Tensor, cand_prob: Optional[torch.Tensor], init_llh: torch.Tensor, values: torch.Tensor, topks, temps,
+                 max_kms, max_choice_bytes: int = SWEEP_CHOICE_BYTES) -> torch.Tensor:
+    """The totals (G,V+2) fp64 of every grid point over all B rows: refine_sweep_choice + refine_sweep_totals over chunks of rows, a
+    multiple of the workgroup's rows each, sized so that a chunk's G x rows choice bytes stay under `max_choice_bytes`; the chunks'
+    totals are added in chunk order in fp64.  No host synchronisation."""
+    B, n_eval = int(scratch.shape[0]), int(scratch.shape[1])
+    ks, ts, rs = list(topks), list(temps), list(max_kms)
+    G = len(ks) * len(ts) * len(rs)
+    V = int(values.shape[2]) if values.dim() == 3 else 0
+    if B == 0 or G == 0:
+        return refine_sweep_totals(refine_sweep_choice(scratch, cand_prob, init_llh, ks, ts, rs), values)
+    unit = refine_sweep_plan(B, n_eval, G, V)["rows_per_workgroup"]
+    rows = max(unit, (int(max_choice_bytes) // G) // unit * unit)
+    total = None
+    for s in range(0, B, rows):
+        e = min(B, s + rows)
+        ch = refine_sweep_choice(scratch[s:e], None if cand_prob is None else cand_prob[s:e], init_llh[s:e], ks, ts, rs)
+        part = refine_sweep_totals(ch, values[s:e])
+        total = part if total is None else total + part
+        del ch
+    return total
+
+
 def tune_gemm_raster(gn: int) -> None:
     """pg_tune_gemm_raster: N tiles per raster group of the 384 x 256 GEMM (0 default, -1 all).  Timing only."""
     check(load().pg_tune_gemm_raster(int(gn)), "pg_tune_gemm_raster")

@@ -307,6 +307,23 @@ class ProtoRefiner(nn.Module):
         this costs nothing; on a device it is one scalar D2H read per forward."""
         return float(self.temperature.data)
 
+    def apply_settings(self, topk, temperature, max_refinement, num_candidates=None):
+        """Validate and set `topk`, `temperature` and `max_refinement` (pigeon_amd/refiner_fit.py `check_settings`: topk 1 .. 64, and at
+        most `num_candidates` when given; a finite positive temperature; max_refinement >= 0, inf = never veto).  ValueError otherwise,
+        with nothing changed.  The temperature is written through the Parameter's `.data`."""
+        from .refiner_fit import apply_settings
+        return apply_settings(self, topk, temperature, max_refinement, num_candidates)
+
+    @torch.no_grad()
+    def sweep(self, embedding: Tensor, initial_preds: Tensor, candidate_cells: Tensor, candidate_probs: Tensor, labels: Tensor,
+              topks, temps, max_kms):
+        """The metrics of this refiner at every point of the grid topks x temps x max_kms, as a dict of (nK,nT,nR) arrays: Mean_km_error,
+        Geoguessr_score, Under_{1,5,10,25,50,100,200,750,1000,2500}_km, Changed, Vetoed.  The candidates are evaluated once (one
+        `refine_forward` at topk = max(topks)); pg_refine_sweep does every point's selection from those records, bit-identical to a
+        `forward` with that point's settings.  `labels` (B,2): the true [lng, lat].  The refiner's own settings are not touched."""
+        from .refiner_fit import sweep
+        return sweep(self, embedding, initial_preds, candidate_cells, candidate_probs, labels, topks, temps, max_kms)
+
     def _device_bank(self, device) -> hip_ops.DeviceBank:
         if self._dbank is None:
             self._dbank = hip_ops.DeviceBank(self.host_bank, device=device)

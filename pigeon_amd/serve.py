@@ -257,7 +257,7 @@ def make_app(model, refiner=None, preprocess: Optional[Callable] = None, game_lo
 
 
 def main(argv=None):
-    """python -m pigeon_amd.serve --head <head.model> [--geocells <csv>] [--protos <csv> --dataset <dir>] [--calibration <file>] [--spread] [--guess expected-score] [--neighbours K] [--temperature FILE|NUMBER] [--port 5000]"""
+    """python -m pigeon_amd.serve --head <head.model> [--geocells <csv>] [--protos <csv> --dataset <dir>] [--calibration <file>] [--spread] [--guess expected-score] [--neighbours K] [--temperature FILE|NUMBER] [--refiner FILE|TOPK,TEMPERATURE,MAX_KM] [--port 5000]"""
     import os
     ap = _arg_parser()
     args = ap.parse_args(argv)
@@ -271,7 +271,6 @@ def main(argv=None):
     import torch
     import uvicorn
     from .clip_embedder import HipCLIPVisionModel
-    from .proto_refiner import ProtoRefiner
     from .super_guessr import SuperGuessr
     kw = {"geocell_path": args.geocells} if args.geocells else {}
     from .clip_embedder import load_pretrained_clip
@@ -290,10 +289,28 @@ def main(argv=None):
     if args.temperature is not None:                                   # after the weights: a sidecar is keyed to the head
         model.load_temperature(args.temperature)
         print(f"[serve] temperature {model.temperature:.6g}: spread, best guess and `confidence` under softmax(logits / T)")
-    refiner = ProtoRefiner(proto_path=args.protos, dataset_path=args.dataset) if args.protos else None
+    refiner = build_refiner(args, model)
     torch.cuda.synchronize()
     uvicorn.run(make_app(model, refiner, encoded=args.encoded, spread=args.spread, best_guess=args.guess == "expected-score",
                          neighbours=args.neighbours, confidence=args.temperature is not None), host=args.host, port=args.port)
+
+
+def build_refiner(args, model):
+    """The server's refiner: the constructor defaults over --protos / --dataset (a packed .npz bank is taken as it is), then --refiner
+    (FILE | TOPK,TEMPERATURE,MAX_KM; pigeon_amd/refiner_fit.py) applied and printed.  None without --protos."""
+    from .proto_refiner import ProtoRefiner
+    if not args.protos:
+        if getattr(args, "refiner", None) is not None:
+            raise ValueError("--refiner sets the refiner's topk, temperature and max_km: give --protos and --dataset")
+        return None
+    if str(args.protos).endswith(".npz"):
+        refiner = ProtoRefiner(bank=args.protos)
+    else:
+        refiner = ProtoRefiner(proto_path=args.protos, dataset_path=args.dataset)
+    if getattr(args, "refiner", None) is not None:
+        from .refiner_fit import apply_to
+        apply_to(refiner, args.refiner, model, prefix="[serve] ")
+    return refiner
 
 
 def _arg_parser():
@@ -323,6 +340,9 @@ def _arg_parser():
                     help="the temperature of the head's probabilities: a number, or the sidecar `python -m pigeon_amd.temperature` wrote "
                          "for this head (as in `run.py evaluate --temperature`); every answer gains `confidence`, the calibrated "
                          "top-1 probability, and --spread / --guess use the calibrated probabilities")
+    ap.add_argument("--refiner", default=None, metavar="FILE|TOPK,TEMPERATURE,MAX_KM",
+                    help="the refiner's topk, temperature and veto radius: three numbers, or the sidecar `python -m pigeon_amd.refiner_fit` "
+                         "wrote for this head and these prototypes (as in `run.py evaluate --refiner`); needs --protos")
     ap.add_argument("--host", default="127.0.0.1")
     ap.add_argument("--port", type=int, default=5000)
     ap.add_argument("--calibration", default=None, metavar="FILE",

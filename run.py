@@ -105,6 +105,10 @@ argp.add_argument('--temperature', default=None, metavar='FILE|NUMBER',
                   help="evaluate: the temperature of the head's probabilities -- a number, or the sidecar `python -m pigeon_amd.temperature` "
                        "wrote for this head; --spread and --guess are then computed under softmax(logits / T) and `Temperature` is "
                        "printed with the metrics.  The model's own guess and its accuracy do not change")
+argp.add_argument('--refiner', default=None, metavar='FILE|TOPK,TEMPERATURE,MAX_KM',
+                  help="evaluate: the refiner's topk, temperature and veto radius -- three numbers, or the sidecar "
+                       "`python -m pigeon_amd.refiner_fit` wrote for this head and this prototype bank; applied after the refiner is built "
+                       "and printed.  Without the flag the built-in settings are used, as before")
 argp.add_argument('--bootstrap', type=int, default=None, metavar='R',
                   help="evaluate: R paired bootstrap replicates of every metric on the GPU (pigeon_amd.bootstrap): the metrics are printed as "
                        "`value [lo, hi]`, the paired differences (--guess, --neighbours against the model's own guess) below them")
@@ -297,7 +301,7 @@ def _dispatch(args, comm):
                            country_path=args.countries, bank_rel_tol=args.bank_rel_tol, spread=(0.5, 0.9) if args.spread else None,
                            best_guess={'expected-score': 'score', 'expected-km': 'km'}.get(args.guess), neighbours=args.neighbours,
                            temperature=args.temperature, bootstrap=args.bootstrap, bootstrap_seed=args.bootstrap_seed,
-                           bootstrap_level=args.bootstrap_level)
+                           bootstrap_level=args.bootstrap_level, refiner_settings=args.refiner)
         _print_fallbacks(comm)
         if comm.is_main_process:
             print({k: (v if not hasattr(v, 'shape') or v.shape == () else tuple(v.shape)) for k, v in results.items() if k not in ('exact_passes', 'bootstrap', 'bootstrap_level')})
